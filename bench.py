@@ -14,11 +14,18 @@ once when the block is made resident: --storage; the fp32-resident form is the l
 itself; or torchrun), clips sharded by rank (weak scaling), RCCL reduce-scatter /
 all-gather of the flat gradient buffer's buckets overlapped with backward.
 
-Prints ONE JSON line on rank 0 with the throughput, a `roofline` object for the
-dominant kernel (per-call-site device time from HIP events on the launch stream,
-collected in a separate pass after the timed region) and a `cpu_baseline` object
-(the CPU oracle -- a torch-CPU restatement of the reference, pinned to it by golden
-vectors -- timed on the host cores on a bounded sample of the same workload).
+Prints ONE JSON line on rank 0 with the throughput (`value`, `ms_per_step` of the
+--steps timed steps).  A plain run does only that: set-up, warm-up, the timed steps.
+With --full it also reports a `roofline` object for the dominant kernel (per-call-site
+device time from HIP events on the launch stream, collected in a separate pass after
+the timed region), the first-step parity check, the un-headlined legs and configurations,
+and a `cpu_baseline` object (the CPU oracle -- a torch-CPU restatement of the reference,
+pinned to it by golden vectors -- timed on the host cores on a bounded sample of the
+same workload).
+
+--dump-outputs DIR writes what the last timed step handed its caller (rank 0): the loss,
+the updated parameters and their gradients, float32 .npy files (dump_outputs).  Inputs,
+initial parameters and dropout keys are seeded: the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -101,7 +108,45 @@ def parse():
     ap.add_argument('--cpu-batch', type=int, default=64)
     ap.add_argument('--batch-sweep', default='256', help='N > 1 only: extra clips-per-GPU sizes timed after the main run (comma list)')
     ap.add_argument('--gemm-mode', type=int, default=None, help='0 f32-input MFMA, 2 split bf16x3 MFMA (default: library default)')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: parity check, per-kernel roofline passes, host enqueue time, the other legs and '
+                         'configurations, data-parallel diagnostics and the CPU baseline (each subject to its --no-* option); '
+                         'without it the run is set-up, warm-up and the timed steps only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the loss, parameters and gradients after the last timed step to DIR/<name>.npy (float32)')
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
+    if not a.full:
+        # (the plain run: everything that is not the headline figure is off)
+        a.no_cpu_baseline = a.no_parity_check = a.no_profile = a.no_dense = a.no_pcie = a.no_eval = a.no_strict = a.no_configs = True
+    return a
+
+
+DUMP_SAMPLE = 1 << 18             # --dump-outputs: a tensor of more elements is written as a fixed sample of this many
+
+
+def dump_outputs(out_dir, model, loss_value):
+    """--dump-outputs: what the last timed train step handed its caller -- the loss (loss.npy), every updated parameter
+    (param.<name>.npy) and its gradient (grad.<name>.npy), flattened, float32.  A tensor of more than DUMP_SAMPLE elements is
+    written as the DUMP_SAMPLE flat indices drawn without replacement by numpy.random.default_rng(<its position in
+    named_parameters()>), in ascending order: the same sample on every run (~34 MB in all at the bench shape)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    params = list(model.named_parameters())          # (joins the side stream the last step's update may still be running on)
+    torch.cuda.synchronize()
+    np.save(os.path.join(out_dir, 'loss.npy'), loss_value.detach().reshape(-1).float().cpu().numpy())
+    for i, (name, p) in enumerate(params):
+        n = p.numel()
+        pick = None
+        if n > DUMP_SAMPLE:
+            pick = torch.from_numpy(np.sort(np.random.default_rng(i).choice(n, DUMP_SAMPLE, replace=False))).to(p.device)
+        for kind, t in (('param', p.detach()), ('grad', p.grad)):
+            flat = t.detach().reshape(-1) if t is not None else torch.zeros(n, device=p.device)
+            if pick is not None:
+                flat = flat[pick]
+            np.save(os.path.join(out_dir, '%s.%s.npy' % (kind, name)), flat.float().cpu().numpy())
 
 
 def cpu_baseline(T, R, B, budget_s=25.0):
@@ -635,20 +680,24 @@ def main():
     if a.host_profile:
         pr.disable()
         pstats.Stats(pr, stream=sys.stderr).sort_stats('cumulative').print_stats(60)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, model, cur['loss'])          # (before any further step)
     # host time to issue one step: a SHORT burst from an idle GPU (over the whole timed loop the launch queue fills up and the
     # host is throttled to the GPU's pace, so that loop's own enqueue time says nothing about the host's cost)
-    sync()
-    t0 = time.perf_counter()
-    for _ in range(8):
-        step()
-    host_ms = (time.perf_counter() - t0) / 8 * 1e3
-    sync()
+    host_ms = None
+    if a.full:
+        sync()
+        t0 = time.perf_counter()
+        for _ in range(8):
+            step()
+        host_ms = (time.perf_counter() - t0) / 8 * 1e3
+        sync()
     host_loop_ms = cur['host_s'] / a.steps * 1e3
 
     # data-parallel diagnostics (every rank takes part; rank 0 reports): the gradient buckets all-reduced ALONE, five times
     # each, so that a scaling result can be read against what the fabric does for these sizes without any compute beside it
     dp_info = None
-    if dp:
+    if dp and a.full:
         sync_obj = model.grad_sync
         g = model.flat_grads(attach=False)
         W = dist.get_world_size()
@@ -1171,7 +1220,7 @@ def main():
     if rank == 0:
         clips = B * world * a.steps
         res = {'metric': 'clips/sec fwd+bwd at 16 tracks×2048-d', 'value': round(clips / dt, 2), 'unit': 'clips/s',
-               'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': round(dt / a.steps * 1e3, 3), 'host_enqueue_ms_per_step': round(host_ms, 3), 'host_loop_ms_per_step': round(host_loop_ms, 3),
+               'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': round(dt / a.steps * 1e3, 3), 'host_enqueue_ms_per_step': (round(host_ms, 3) if host_ms is not None else None), 'host_loop_ms_per_step': round(host_loop_ms, 3),
                'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
                'dtype': DTYPE_OF_MODE[mode] + (' (features stored as bf16)' if a.feature_dtype == 'bf16' else ''), 'data': 'synthetic',
                'config': {'workload': 'int_rel_ch train step (fwd+loss+bwd+Adam): MidFusionMultiClipMaxTracks '

@@ -36,7 +36,7 @@ def test_self_launch_starts_n_ranks_and_propagates_failure():
 
 @pytest.mark.gpu
 def test_two_rank_bench_branch_on_one_gpu():
-    r = _run(['--gpus', '2', '--steps', '3', '--warmup', '1', '--batch', '8', '--batch-sweep', '16', '--no-cpu-baseline',
+    r = _run(['--gpus', '2', '--steps', '3', '--warmup', '1', '--batch', '8', '--batch-sweep', '16', '--full', '--no-cpu-baseline',
               '--no-strict', '--no-configs', '--no-pcie'], env={'LIREC_BENCH_DEBUG_SAME_GPU': '1'})
     assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -54,7 +54,7 @@ def test_two_rank_bench_branch_on_one_gpu():
 
 @pytest.mark.gpu
 def test_two_rank_bench_branch_eager_launch():
-    r = _run(['--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '8', '--batch-sweep', '', '--launch', 'eager', '--no-cpu-baseline',
+    r = _run(['--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '8', '--batch-sweep', '', '--launch', 'eager', '--full', '--no-cpu-baseline',
               '--no-strict', '--no-configs', '--no-pcie', '--no-dense', '--no-eval', '--no-profile'], env={'LIREC_BENCH_DEBUG_SAME_GPU': '1'})
     assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][0])
@@ -96,7 +96,7 @@ def test_self_launch_ends_its_ranks_when_it_is_stopped(tmp_path):
 def test_n_rank_bench_branch_on_one_gpu(n):
     """bench.py's N > 1 branch with 4 and 8 ranks (all on cuda:0, gloo; B = 4 clips per rank): one JSON line, every rank's
     parameter checksum the same bits after the timed steps."""
-    r = _run(['--gpus', str(n), '--steps', '2', '--warmup', '1', '--settle', '0', '--batch', '4', '--batch-sweep', '', '--no-cpu-baseline',
+    r = _run(['--gpus', str(n), '--steps', '2', '--warmup', '1', '--settle', '0', '--batch', '4', '--batch-sweep', '', '--full', '--no-cpu-baseline',
               '--no-strict', '--no-configs', '--no-pcie', '--no-dense', '--no-eval', '--no-profile'], env={'LIREC_BENCH_DEBUG_SAME_GPU': '1'}, timeout=1500)
     assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -104,3 +104,34 @@ def test_n_rank_bench_branch_on_one_gpu(n):
     j = json.loads(lines[0])
     assert j['n_gpus'] == n and j['config']['parallelism'] == 'dp%d' % n and j['value'] > 0
     assert j['data_parallel']['rccl_ranks'] == n and j['data_parallel']['ranks_in_sync'] is True
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain run (no --full) is the headline alone: one JSON line whose `steps` / `ms_per_step` are the timed steps', none of
+    the --full passes.  --dump-outputs writes the loss, parameters and gradients of the last timed step (float32, 64 MB at most),
+    and a second run with the same arguments writes the same bits."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ('out%d' % i)
+        r = _run(['--steps', '3', '--warmup', '1', '--settle', '0', '--batch', '8', '--dump-outputs', str(d)], timeout=600)
+        assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
+        lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1, r.stdout[-2000:]
+        j = json.loads(lines[0])
+        assert j['steps'] == 3 and j['unit'] == 'clips/s' and j['higher_is_better'] is True and j['ms_per_step'] > 0
+        assert abs(j['value'] - 8 * 1e3 / j['ms_per_step']) <= 0.01 * j['value']
+        assert all(j[k] is None for k in ('roofline', 'parity_check', 'eval', 'configs', 'feature_assembly', 'cpu_baseline', 'data_parallel'))
+        arrays = {f: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))}
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert all(f.endswith('.npy') and a.dtype == np.float32 for f, a in arrays.items())
+        params = [f for f in arrays if f.startswith('param.')]
+        assert len(params) == 38 and all(f.replace('param.', 'grad.', 1) in arrays for f in params)
+        assert all(np.isfinite(a).all() for a in arrays.values())
+        assert any(np.abs(arrays[f.replace('param.', 'grad.', 1)]).max() > 0 for f in params)
+        assert float(arrays['loss.npy'][0]) == pytest.approx(j['config']['last_loss'], abs=2e-5)
+        dumps.append(arrays)
+    assert sorted(dumps[0]) == sorted(dumps[1])
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 for rep in 1 2; do
 for f in "$@"; do
-  python3 $R/bench.py --no-cpu-baseline --no-pcie --no-configs --no-dense --no-parity-check $f 2>/dev/null | python3 -c "
+  python3 $R/bench.py --full --no-cpu-baseline --no-pcie --no-configs --no-dense --no-parity-check $f 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('%-40s %9.1f clips/s  %.3f ms  %s  host %.3f ms' % (sys.argv[1], d['value'], d['ms_per_step'], d['config']['step_launch'], d['host_enqueue_ms_per_step']))" "$f"

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/abfetch; mkdir -p $O; cd /tmp; exp
 i=0
 for f in "$@"; do
   i=$((i+1))
-  timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/p$i -o pmc -- python3 $R/bench.py --no-cpu-baseline --no-profile --no-dense --no-pcie --no-configs --no-parity-check --steps 5 --warmup 3 $f > $O/p$i.log 2>&1
+  timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/p$i -o pmc -- python3 $R/bench.py --full --no-cpu-baseline --no-profile --no-dense --no-pcie --no-configs --no-parity-check --steps 5 --warmup 3 $f > $O/p$i.log 2>&1
   echo "== $f"
   python3 - $O/p$i/pmc_counter_collection.csv <<'P'
 import csv, sys, collections

@@ -2,7 +2,7 @@
 # per-site launch times of the bench step under several flag sets (one GPU visit)
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 for f in "$@"; do
-  python3 $R/bench.py --no-cpu-baseline --no-pcie --no-configs --no-dense --no-parity-check --steps 40 $f 2>/dev/null | python3 -c "
+  python3 $R/bench.py --full --no-cpu-baseline --no-pcie --no-configs --no-dense --no-parity-check --steps 40 $f 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 k=d['kernels']

@@ -13,9 +13,9 @@ O=$R/gpurun_out/profiles
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 B="$R/bench.py"
-Q="--no-cpu-baseline --no-profile --no-dense --no-pcie --no-configs --no-parity-check --no-strict --no-eval"
-timeout 600 python3 $B --no-cpu-baseline --no-dense --no-pcie --no-configs --steps 30 --warmup 10 > /dev/null 2>&1   # page the image in
-timeout 900 python3 $B > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+Q="--full --no-cpu-baseline --no-profile --no-dense --no-pcie --no-configs --no-parity-check --no-strict --no-eval"
+timeout 600 python3 $B --full --no-cpu-baseline --no-dense --no-pcie --no-configs --steps 30 --warmup 10 > /dev/null 2>&1   # page the image in
+timeout 900 python3 $B --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o kt -- python3 $B $Q --steps 50 --warmup 10 > $O/kt.log 2>&1; echo "kernel-trace rc=$?"
 timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -o pmc -- python3 $B $Q --steps 5 --warmup 3 > $O/pmc_fetch.log 2>&1; echo "pmc fetch rc=$?"
 timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -o pmc -- python3 $B $Q --steps 5 --warmup 3 > $O/pmc_write.log 2>&1; echo "pmc write rc=$?"

@@ -29,7 +29,7 @@ for m in "${MICRO[@]}"; do
     && timeout 600 /tmp/$m.bin > $O/$m.txt 2>&1; echo "$m rc=$?"; cat $O/$m.txt
 done
 [ $TRACE -eq 1 ] && bash tools/trace_step.sh $TAG/trace > /dev/null 2>&1 && cat $O/trace/trace.csv
-Q="--no-cpu-baseline --no-configs --no-pcie --no-strict --no-eval --no-dense --no-parity-check"
+Q="--full --no-cpu-baseline --no-configs --no-pcie --no-strict --no-eval --no-dense --no-parity-check"
 : > $O/ab.txt
 for rep in $(seq 1 $REPS); do
   for f in "${AB[@]}"; do

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=${1:-trace}; shift
 O=$R/gpurun_out/$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/kt -o kt -- python3 $R/bench.py --no-cpu-baseline --no-profile --no-dense --no-pcie --no-parity-check --no-configs --steps 6 --warmup 3 "$@" > $O/kt.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/kt -o kt -- python3 $R/bench.py --full --no-cpu-baseline --no-profile --no-dense --no-pcie --no-parity-check --no-configs --steps 6 --warmup 3 "$@" > $O/kt.log 2>&1
 echo "rc=$?"
 python3 - <<PY
 import csv, glob
