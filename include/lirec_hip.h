@@ -38,7 +38,7 @@ extern "C" {
 typedef void* lirec_stream_t;            /* hipStream_t */
 typedef void* lirec_ctx_t;               /* library context (lirec_ctx_create); NULL = the default context */
 
-#define LIREC_VERSION 122                /* 0.1.8 */
+#define LIREC_VERSION 123                /* 0.1.9 */
 #define LIREC_MAX_SEG 4
 
 enum {
@@ -233,7 +233,7 @@ int lirec_compact_rows2(const void* mask, int32_t mask_dtype, int32_t n, int32_t
  *   dW2_s += dZ2_s^T H1_s, db2_s += colsum dZ2_s,
  *   dZ1 = (dZ2_s W2_s) * [H1 > 0] / (1-p)   (into workspace, rows*nseg*J floats)
  *   dW1_s += dZ1_s^T X_s,  db1_s += colsum dZ1_s.
- * dX is never formed: the features do not require grad.
+ * dX is not formed here: a caller whose features require grad asks lirec_embed_dx for it once this call has run (ABI 123).
  * Pooled form (mask != NULL; rows = n*R, dZ2 is [n, sum out_dim]):
  *   dW2_s += dZ2_s^T Hbar_s, db2_s += sum_c f[c] dZ2_s[c,:], dHbar = dZ2_s W2_s  (n rows),
  *   dZ1[c,r,:] = dHbar[c,:] * mask[c,r]/div[c] * [H1[c,r,:] > 0] / (1-p), then dW1/db1 as above. */
@@ -291,6 +291,27 @@ int lirec_embed_bwd(const lirec_embed_bwd_args* a, lirec_stream_t stream);
 /* Both heads in one call: dW2 of both heads in one grouped launch, likewise the hidden-layer gradients; the two
  * first-layer weight gradients stay separate launches (a's first). */
 int lirec_embed_bwd2(const lirec_embed_bwd_args* a, const lirec_embed_bwd_args* b, lirec_stream_t stream);
+/* Input-feature gradient (ABI 123): dX = d loss / d X of the (n, rp1, D) block the forward read, from the hidden-layer gradients
+ * the backward left in the heads' workspaces.  For head h and segment i, row L of the head (physical row (L / group) * group_stride
+ * + group_off + L % group; the compact rows of the context head through its row map):
+ *   dX[row(L), in_off[i] .. + in_dim[i]) = dZ1_i[L, :] W1[h][i]        (K = J; one grouped launch over head x segment)
+ * and every element that no problem writes -- rows of a head that is absent, context rows whose mask is 0 (not computed under
+ * compaction), columns of unused segments -- is set to 0 (a second launch).  No accumulation: the block is overwritten.
+ * heads: the argument structs of the lirec_embed_bwd2 (nh = 2, in its order) or lirec_embed_bwd (nh = 1) call that ran the
+ * whole backward (parts 0, or 2 after 1) -- the same workspaces, planes and GEMM core; nothing may have written the workspaces
+ * since.  W1[h][i]: the first-layer weights [J][in_dim] of that head's segment i as the forward read them (issue the call before
+ * any update of the weights).  group_stride must be rp1, the heads' row ranges disjoint, segments in column order, J and in_dim multiples of 4.
+ * GEMM core: modes 0 and 1 the exact f32-input MFMA; modes 2 and 3 bf16x3 (three passes on both operands; in mode 3 the context
+ * head's dZ1 exists only as its bf16 hi plane, so those rows multiply dZ1 rounded to bf16).
+ * out_bf16: the block is bf16 (round to nearest even), else fp32.  ldx (elements, multiple of 4) >= D; dX 16-byte aligned. */
+typedef struct {
+  const lirec_embed_bwd_args* heads[2];
+  int32_t nh, out_bf16;
+  const float* W1[2][LIREC_MAX_SEG];
+  void* dX; int64_t ldx;
+  int32_t n, rp1, D, reserved_;
+} lirec_embed_dx_args;
+int lirec_embed_dx(const lirec_embed_dx_args* a, lirec_stream_t stream);
 /* First-layer weight gradients from the unique pieces (the backward of lirec_embed_l1_indexed):
  *   dW1_seg += sum over pieces u of ( sum of the dZ1 rows whose index names u ) (x) piece_u ,  db1_seg += sum of the dZ1 rows.
  * The inner sums are  S = P^T dZ1  with P the 0/1 incidence matrix of the index (written by the call), an ordinary weight-
@@ -591,7 +612,7 @@ int lirec_dropout_mask(uint8_t* keep, int32_t rows, int32_t cols, const lirec_dr
                        int32_t site, lirec_stream_t stream);
 int lirec_version(void);
 /* sizeof() of ABI struct `which` (5 = eval; 0 embed_fwd, 1 embed_bwd, 2 margin_loss, 3 dropout,
- * 4 rowsel) so a binding can verify its mirror; -1 if unknown */
+ * 4 rowsel, 6 linear_fwd, 7 linear_bwd, 8 embed_dx) so a binding can verify its mirror; -1 if unknown */
 int lirec_abi_sizeof(int which);
 /* GEMM core: 0 exact f32-input MFMA   1 one-thread-per-output HIP GEMM (bring-up cross-check)
  *            2 split-precision bf16x3 MFMA (fp32 in/out, ~2^-16 per product, up to 5.3x the f32 core)

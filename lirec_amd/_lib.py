@@ -17,7 +17,7 @@ MAX_SEG = 4
 DEFAULT_GEMM_MODE = 2          # 0 exact f32-input MFMA, 1 naive cross-check, 2 split-precision bf16x3 MFMA (default), 3 single-pass bf16 on the large GEMMs
 
 SITE_H1_INTS, SITE_H1_CTX, SITE_E_INTS, SITE_E_CTX, SITE_GATE, SITE_TRACK_SAMPLE = 0, 1, 2, 3, 4, 5
-ABI_VERSION = 122
+ABI_VERSION = 123
 LIREC_EINVAL = 10001
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -64,6 +64,12 @@ class FusedAdamArgs(C.Structure):
     _fields_ = [('p', _vp), ('g', _vp), ('m', _vp), ('v', _vp), ('wq', _vp), ('wq_first', _i64), ('n', _i64), ('n_params', _i64),
                 ('step', _i32), ('lr', _f32), ('beta1', _f32), ('beta2', _f32), ('eps', _f32), ('weight_decay', _f32),
                 ('grad_scale', _f32), ('step_dev', _vp)]
+
+
+class EmbedDxArgs(C.Structure):
+    """lirec_embed_dx_args (ABI 123): the input-feature gradient of the first layers"""
+    _fields_ = [('heads', C.POINTER(EmbedBwdArgs) * 2), ('nh', _i32), ('out_bf16', _i32), ('W1', (_vp * MAX_SEG) * 2),
+                ('dX', _vp), ('ldx', _i64), ('n', _i32), ('rp1', _i32), ('D', _i32), ('reserved_', _i32)]
 
 
 class MarginLossArgs(C.Structure):
@@ -149,6 +155,7 @@ _PROTOS = {
     'lirec_embed_dw1_indexed': (_i32, [C.POINTER(C.POINTER(EmbedBwdArgs)), _i32, C.POINTER(Pieces), C.POINTER(_vp), C.POINTER(_vp), _vp]),
     'lirec_embed_l1_indexed': (_i32, [C.POINTER(C.POINTER(EmbedFwdArgs)), _i32, C.POINTER(Pieces), C.POINTER(_vp), C.POINTER(_vp), _vp]),
     'lirec_embed_bwd2': (_i32, [C.POINTER(EmbedBwdArgs), C.POINTER(EmbedBwdArgs), _vp]),
+    'lirec_embed_dx': (_i32, [C.POINTER(EmbedDxArgs), _vp]),
     'lirec_linear_fwd_group': (_i32, [C.POINTER(LinearFwdArgs), _i32, _vp]),
     'lirec_linear_bwd_group': (_i32, [C.POINTER(LinearBwdArgs), _i32, _vp]),
     'lirec_compact_rows': (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
@@ -220,7 +227,7 @@ def lib():
     for name, (res, args) in _PROTOS.items():
         fn = getattr(L, name)          # AttributeError if the symbol is missing
         fn.restype, fn.argtypes = res, args
-    for which, st in enumerate((EmbedFwdArgs, EmbedBwdArgs, MarginLossArgs, Dropout, RowSel)):
+    for which, st in list(enumerate((EmbedFwdArgs, EmbedBwdArgs, MarginLossArgs, Dropout, RowSel))) + [(8, EmbedDxArgs)]:
         if L.lirec_abi_sizeof(which) != C.sizeof(st):
             raise LirecError('ABI mismatch for %s: library %d bytes, binding %d bytes'
                              % (st.__name__, L.lirec_abi_sizeof(which), C.sizeof(st)))

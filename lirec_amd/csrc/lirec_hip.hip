@@ -12,6 +12,7 @@
 #include "gemm.hpp"
 #include "gemm_launch.hpp"
 #include "kernels.hpp"
+#include "gemm_dx.hpp"
 
 using namespace lirec;
 
@@ -968,6 +969,7 @@ int lirec_abi_sizeof(int which) {
     case 5: return (int)sizeof(lirec_eval_args);
     case 6: return (int)sizeof(lirec_linear_fwd_args);
     case 7: return (int)sizeof(lirec_linear_bwd_args);
+    case 8: return (int)sizeof(lirec_embed_dx_args);
     default: return -1;
   }
 }
@@ -1723,6 +1725,85 @@ int lirec_embed_bwd2(const lirec_embed_bwd_args* a, const lirec_embed_bwd_args* 
   if (rc || parts == 3) return rc;
   const lirec_embed_bwd_args* hs[2] = {a, b};
   return embed_bwd_tail_heads(hs, gw1, 2, s);
+}
+
+// Input-feature gradient (gemm_dx.hpp): dX = dZ1_s W1_s of every (head, segment) problem, scattered into the caller's
+// (n, rp1, D) block, and zeros wherever no problem writes.  dZ1 is read where the backward call left it: fp32 in the
+// workspace (plain heads always; pooled heads off the q32b path), or -- a pooled head on the q32b path -- the bf16 hi / lo planes
+// the un-pooling pass wrote over the same bytes (hi only in the single-pass mode).
+int lirec_embed_dx(const lirec_embed_dx_args* a, lirec_stream_t stream) {
+  if (!a || a->nh < 1 || a->nh > 2 || !a->dX || a->n < 0 || a->rp1 < 1 || a->rp1 > 1024 || a->D < 1 || a->ldx < a->D ||
+      (a->ldx & 3) != 0 || (reinterpret_cast<uintptr_t>(a->dX) & 15) != 0 || (a->out_bf16 != 0 && a->out_bf16 != 1))
+    return LIREC_EINVAL;
+  const int nh = a->nh;
+  for (int h = 0; h < nh; ++h) {
+    const lirec_embed_bwd_args* b = a->heads[h];
+    if (!b || b->pieces || !b->workspace || b->nseg < 1 || b->nseg > LIREC_MAX_SEG || b->J < 4 || (b->J & 3) != 0) return LIREC_EINVAL;
+    const lirec_rowsel& sel = b->sel;
+    if (sel.group < 1 || sel.group_off < 0 || sel.group_off + sel.group > a->rp1 || sel.group_stride != a->rp1) return LIREC_EINVAL;
+    if (b->rows != a->n * sel.group) return LIREC_EINVAL;
+    const bool pooled = b->mask != nullptr || b->rowmap != nullptr;
+    if (pooled && (b->R != sel.group || (b->rowmap && (!b->count || !b->cstart)))) return LIREC_EINVAL;
+    if (b->workspace_bytes < lirec_workspace_bytes(b->rows + (pooled ? a->n : 0), b->nseg, b->J)) return LIREC_EWORKSPACE;
+    for (int i = 0; i < b->nseg; ++i) {
+      const float* w = a->W1[h][i];
+      if (!w || (reinterpret_cast<uintptr_t>(w) & 15) != 0 || b->in_dim[i] < 1 || (b->in_dim[i] & 3) != 0 || b->in_off[i] < 0 ||
+          b->in_off[i] + b->in_dim[i] > a->D)
+        return LIREC_EINVAL;
+    }
+    if (h == 1) {
+      const lirec_rowsel& s0 = a->heads[0]->sel;
+      if (sel.group_off < s0.group_off + s0.group && s0.group_off < sel.group_off + sel.group) return LIREC_EINVAL;   // one writer per row
+    }
+  }
+  if (a->n == 0) return LIREC_OK;
+  hipStream_t s = (hipStream_t)stream;
+  PlaneLayout L[2];
+  const bool planes = planes_for_heads(a->heads, nh, L);     // (the decision embed_bwd_tail_heads took for the same heads)
+  DxGroup g;
+  memset(&g, 0, sizeof(g));
+  g.C = a->dX; g.ldc = a->ldx; g.out_bf16 = a->out_bf16;
+  DxZero z;
+  memset(&z, 0, sizeof(z));
+  z.nh = nh; z.rp1 = a->rp1; z.D = a->D; z.C = a->dX; z.ldc = a->ldx; z.out_bf16 = a->out_bf16;
+  int tiles = 0;
+  for (int h = 0; h < nh; ++h) {
+    const lirec_embed_bwd_args* b = a->heads[h];
+    for (int i = 1; i < b->nseg; ++i) if (b->in_off[i] < b->in_off[i - 1]) return LIREC_EINVAL;   // (segments in column order)
+    const bool pooled = b->mask != nullptr || b->rowmap != nullptr;
+    const long ldh = (long)b->nseg * b->J, rows32 = (b->rows + 31) / 32 * 32;
+    DxZeroHead& zh = z.h[h];
+    zh.gs = b->sel.group; zh.goff = b->sel.group_off; zh.nseg = b->nseg; zh.computed = 1;
+    zh.rowmap = b->rowmap; zh.cstart = b->cstart;
+    for (int i = 0; i < b->nseg; ++i) {
+      zh.in_off[i] = b->in_off[i]; zh.in_dim[i] = b->in_dim[i];
+      DxProblem& p = g.p[g.nprob++];
+      if (planes && pooled) {
+        const unsigned short* hi = reinterpret_cast<const unsigned short*>(b->workspace);
+        p.A_hi = hi + (long)i * b->J;
+        p.A_lo = g_gemm_mode == 3 ? nullptr : hi + rows32 * ldh + (long)i * b->J;
+      } else {
+        p.A = reinterpret_cast<const float*>(b->workspace) + (long)i * b->J;
+      }
+      p.lda = ldh;
+      p.B = a->W1[h][i]; p.ldb = b->in_dim[i];
+      p.M = b->rows; p.N = b->in_dim[i]; p.K = b->J;
+      p.dyn = b->rowmap ? b->count : nullptr; p.rowmap = b->rowmap;
+      p.gs = b->sel.group; p.gstride = b->sel.group_stride; p.goff = b->sel.group_off;
+      p.c_off = b->in_off[i];
+      p.tiles_n = (p.N + 127) / 128;
+      p.tile_start = tiles;
+      tiles += ((p.M + 127) / 128) * p.tiles_n;
+    }
+  }
+  lirec::launch(dx_zero_kernel, dim3(a->n), dim3(256), 0, s, z);
+  LIREC_CHECK_LAUNCH();
+  if (tiles > 0) {
+    if (g_bf_core) lirec::launch(HIP_KERNEL_NAME(dx_gemm_kernel<1>), dim3(tiles), dim3(256), 0, s, g);
+    else lirec::launch(HIP_KERNEL_NAME(dx_gemm_kernel<0>), dim3(tiles), dim3(256), 0, s, g);
+    LIREC_CHECK_LAUNCH();
+  }
+  return LIREC_OK;
 }
 
 static int compact_rows_impl(const void* mask, int32_t mask_dtype, int32_t n, int32_t R, int32_t* rowmap, int32_t* cstart,

@@ -24,6 +24,7 @@ from __future__ import annotations
 import torch
 
 from . import ops
+from ._lib import LirecError
 
 
 _STAGE_LANES = {}
@@ -163,6 +164,12 @@ class RecordedTrainStep:
         filled -- its rows are staged DURING the current call.  Same numbers as the plain form, bit for bit."""
         if not model.training:
             raise ValueError('RecordedTrainStep records a TRAIN step: call model.train() first')
+        for b in (batch, next_batch):
+            f = b.get('features') if isinstance(b, dict) else None
+            if torch.is_tensor(f) and f.requires_grad:
+                # (a replay re-issues the recorded launches and returns no autograd graph: the features' gradient would be dropped)
+                raise LirecError('RecordedTrainStep: the batch features require grad -- a recorded step computes no input gradient; '
+                                 'run the eager step (model(batch) -> loss -> backward) instead')
         self.model, self.loss, self.optim, self.batch = model, loss, optimizer, batch
         self.batches = [batch, next_batch] if next_batch is not None else [batch]
         self.sync = getattr(model, 'grad_sync', None)

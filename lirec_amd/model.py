@@ -85,9 +85,26 @@ class _HotPathFn(torch.autograd.Function):
             gi = gouts.pop(0)
         if ctx.has[1]:
             gr = gouts.pop(0)
-        ctx.model._run_backward(ctx.st, gi, gr)
+        # the features' gradient (lirec_embed_dx) only when the caller's features require it: otherwise not a launch more
+        dX = ctx.model._run_backward(ctx.st, gi, gr, want_dx=bool(ctx.needs_input_grad[1]))
         ctx.st = None
-        return (None,) * (6 + len(ctx.model._plist))
+        return (None, dX) + (None,) * (4 + len(ctx.model._plist))
+
+
+class _StageFn(torch.autograd.Function):
+    """The staging of features that require grad (``_HotPathModule._stage_features``): forward is the usual staging (H2D copy,
+    f64 -> f32 cast), backward brings the gradient of the staged block back to the caller's leaf -- its dtype, its device -- as
+    the reference's differentiable ``.float()`` / ``.cuda()`` do (mlp/model.py:279-280)."""
+
+    @staticmethod
+    def forward(ctx, f, model):
+        ctx.dtype, ctx.device = f.dtype, f.device
+        X = model._stage_plain(f)
+        return X.view_as(X) if X is f else X
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.to(device=ctx.device).to(ctx.dtype), None
 
 
 class _HotPathModule(nn.Module):
@@ -243,6 +260,14 @@ class _HotPathModule(nn.Module):
         """features -> contiguous fp32 (or bf16) device tensor.  A resident fp32 / bf16 tensor is used in place;
         the loader's CPU float64 batch (mlp/model.py:279 `.float()`, :280 `.cuda()`) is copied
         H2D once and converted by the cast kernel."""
+        if torch.is_tensor(f) and f.requires_grad and torch.is_grad_enabled():
+            if f.dtype not in (torch.float64, torch.float32, torch.bfloat16):
+                raise LirecError('features that require grad: float64, float32 or bfloat16 only (got %s)' % f.dtype)
+            self._device()
+            return _StageFn.apply(f, self)
+        return self._stage_plain(f)
+
+    def _stage_plain(self, f):
         dev = self._device()
         if isinstance(f, ops.Q32Block):
             # the block stored as q32b (lirec_amd.data.to_device_batch(feature_dtype='q32')): layer 1 gathers its rows from it
@@ -339,6 +364,9 @@ class _HotPathModule(nn.Module):
         stages (RecordedTrainStep puts the step's stream behind the staging stream in front of that launch)."""
         if not (self.training and self._has_ints and self._has_ctx and getattr(opt, 'layer1_planes', False)):
             raise LirecError('prestage: training steps of the mixed recipe on the q32b layer-1 kernels only')
+        f = x.get('features') if isinstance(x, dict) else None
+        if torch.is_tensor(f) and f.requires_grad:
+            raise LirecError('prestage: the features require grad -- prestaged rows carry no autograd graph (run the eager step)')
         X, mask, n, R, clamp = self._prep_inputs(x)
         # (r6: or features stored as q32b -- the pass then writes no rows, only what the step's head would have written for them: the
         #  compaction tables, the row lists, the dropout keep bytes of the step's key, the partition bound)
@@ -594,7 +622,12 @@ class _HotPathModule(nn.Module):
             self._sides[which] = _SIDE_LANES[key]
         return self._sides[which]
 
-    def _run_backward(self, st, d_inters, d_rels):
+    def _run_backward(self, st, d_inters, d_rels, want_dx=False):
+        """The hand-written backward; returns d loss / d X (the staged (n, R+1, D) block, X's dtype) when ``want_dx``, else None."""
+        if want_dx and (not torch.is_tensor(st['X']) or st.get('pieces') is not None or st.get('pieces_gather') is not None
+                        or st.get('prestaged')):
+            raise LirecError('the features\' gradient is formed for a feature block (a tensor) only -- not for q32b storage, '
+                             'piece tables or prestaged rows')
         self.flat_grads(attach=True)
         pieces = st.get('pieces')
         lane = self._wgrad_lane()
@@ -723,6 +756,8 @@ class _HotPathModule(nn.Module):
         # the first-layer parameters' update folded into the launch that finishes their gradients (armed by the optimiser for a
         # step issued as a unit: FusedAdam.arm_first_layer_update): both heads' tails must be the ONE gemm_p2 launch
         adam = self.__dict__.pop('_dw1_adam', None)
+        if want_dx:
+            adam = None          # (the features' gradient reads the first-layer weights after the tail: no update folded into it)
         if adam is not None and not (has_i and has_c and pieces is None and st.get('planes_i') is not None
                                      and st.get('planes_c') is not None and self.grad_sync is None):
             adam = None
@@ -783,12 +818,22 @@ class _HotPathModule(nn.Module):
             # (data parallel or not: both heads' tails share their launches -- the first-layer weight gradients of the two
             #  heads are ONE persistent launch, so their bucket is announced once, at the end)
             run(2)
+        dX = None
+        if want_dx:
+            # dX = dZ1 W1 per (head, segment), on this stream right behind the tail that left dZ1 in the workspaces, with the weights
+            # the forward read (nothing has updated them yet), and before the last bucket is announced -- a data-parallel update of
+            # that bucket starts only after this launch
+            dX = ops.new(X.shape, dtype=X.dtype, device=dev)
+            hs = [(a, mods) for a, mods in ((args_i, getattr(self, '_mods_i', None)), (args_c, getattr(self, '_mods_c', None)))
+                  if a is not None]
+            ops.embed_dx([a for a, _ in hs], [[self._W(m1)[0] for m1, _ in mods] for _, mods in hs], dX)
         join_side()
         if self.grad_sync is not None:
             self.grad_sync.bucket_ready(2)
         # (for the optimiser: this backward left the side stream ordered behind every reader of the first bucket's parameters)
         self._side_after_backward = (side_h, main) if (lane is not None and has_g and has_i) else None
         self._side_unjoined = defer
+        return dX
 
     # ---- first-layer weights kept in the q32b form (lirec_embed_fwd_args::W1q) -------------------------------------------------
     def first_layer_range(self):
@@ -1008,6 +1053,9 @@ class MidFusionMultiClipMaxTracks(_MidFusionBase):
             # the batch as de-duplicated piece tables + index (lirec_amd.features.indexed_batch): the block is never built
             if not (self._has_ints and self._has_ctx):
                 raise LirecError('feature_pieces batches need the mixed recipe with both heads')
+            if any(torch.is_tensor(t) and t.requires_grad for t in pcs.values()):
+                raise LirecError('feature_pieces batches: the gradient cannot be returned to piece tables -- pass the feature block '
+                                 '(x[\'features\']) when the features require grad')
             idx = pcs['index']
             B, T, R = idx.shape[0], idx.shape[1], idx.shape[2] - 1
             X = torch.empty((0, R + 1, opt.mlp_dim), dtype=torch.float32, device=idx.device)
@@ -1097,6 +1145,8 @@ def _with_direct_backward(loss, inters, rels, d_ints, d_rels):
     node = _hot_node(inters)
     if node is None or (rels is not None and _hot_node(rels) is not node) or not loss.requires_grad:
         return loss
+    if node.needs_input_grad[1]:
+        return loss          # (the features require grad: the backward goes through autograd, which takes dX on to them)
     out = loss.as_subclass(_LossValue)
 
     def direct():

@@ -13,7 +13,7 @@ import threading
 import torch
 
 from . import _lib
-from ._lib import (Dropout, FusedAdamArgs, EmbedBwdArgs, EmbedFwdArgs, EvalArgs, LinearBwdArgs, LinearFwdArgs, MarginLossArgs, Pieces, RowSel,
+from ._lib import (Dropout, FusedAdamArgs, EmbedBwdArgs, EmbedDxArgs, EmbedFwdArgs, EvalArgs, LinearBwdArgs, LinearFwdArgs, MarginLossArgs, Pieces, RowSel,
                    check, lib)
 
 
@@ -448,6 +448,22 @@ def embed_bwd(*args, **kw):
 
 def embed_bwd2(a, b):
     check(lib().lirec_embed_bwd2(C.byref(a), C.byref(b), _stream()), 'lirec_embed_bwd2')
+
+
+def embed_dx(heads, W1, dX):
+    """Input-feature gradient (lirec_embed_dx): ``heads`` = the EmbedBwdArgs of the backward call that just ran (both heads in
+    the order given to embed_bwd2, or the one head of embed_bwd), ``W1`` = per head the first-layer weights of its segments,
+    ``dX`` = the contiguous (n, R+1, D) fp32 / bf16 device block to overwrite."""
+    assert dX.is_cuda and dX.is_contiguous() and dX.dim() == 3 and dX.dtype in (torch.float32, torch.bfloat16)
+    a = EmbedDxArgs()
+    a.nh = len(heads)
+    for h, (b, ws) in enumerate(zip(heads, W1)):
+        a.heads[h] = C.pointer(b)
+        _fill(a.W1[h], [_p(w) for w in ws])
+    a.out_bf16 = int(dX.dtype == torch.bfloat16)
+    a.dX, a.ldx = _p(dX), dX.shape[2]
+    a.n, a.rp1, a.D = dX.shape[0], dX.shape[1], dX.shape[2]
+    check(lib().lirec_embed_dx(C.byref(a), _stream()), 'lirec_embed_dx')
 
 
 _MASK_DTYPES = {torch.float32: 0, torch.int64: 1, torch.float64: 2}
