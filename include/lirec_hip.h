@@ -38,7 +38,7 @@ extern "C" {
 typedef void* lirec_stream_t;            /* hipStream_t */
 typedef void* lirec_ctx_t;               /* library context (lirec_ctx_create); NULL = the default context */
 
-#define LIREC_VERSION 123                /* 0.1.9 */
+#define LIREC_VERSION 124                /* 0.1.9 */
 #define LIREC_MAX_SEG 4
 
 enum {
@@ -321,6 +321,31 @@ int lirec_embed_dx(const lirec_embed_dx_args* a, lirec_stream_t stream);
  * Scratch: P[h] rows_h x round4((n_clip + 1) + 2 (n_track + 1)) floats, S[h] ((n_clip + 1) + (n_track + 1)) x 2J floats. */
 int lirec_embed_dw1_indexed(const lirec_embed_bwd_args* const* heads, int32_t nh, const lirec_pieces* pieces,
                             float* const* P, float* const* S, lirec_stream_t stream);
+/* Gradient of the piece tables (ABI 124): d loss / d clip and d loss / d track of the de-duplicated tables the batch was given
+ * as, from the per-piece sums S that lirec_embed_dw1_indexed left (S_h[u] = sum of head h's dZ1 rows whose index names piece u;
+ * layer 1 is linear in the pieces).  With v' = n_clip + 1 + v, the row of track piece v in S:
+ *   dClip[u, 0 .. text_dim)                 = sum_h S_h[u, 0 .. J)   W1[h][0]                      (K = nh J)
+ *   dClip[u, text_dim .. + visual_dim)      = sum_h S_h[u, J .. 2J)  W1[h][1]
+ *   dTrack[v, 0 .. track_dim)               = sum_h S_h[v', 0 .. J) W1[h][2] + S_h[v', J .. 2J) W1[h][3]   (K = 2 nh J)
+ * (a track piece may be track-1 of some rows and track-2 of others).  The trailing zero rows dClip[n_clip] and dTrack[n_track]
+ * are set to 0; pieces no row reads -- or only masked context rows -- come out 0 as well.  ONE launch, one writer per element
+ * (the k-loop runs over the (S, W1) chunks in order): deterministic, no accumulation -- both outputs are overwritten.
+ * Run it after lirec_embed_dw1_indexed on the same stream with the same heads, pieces and S; nothing may write S in between.
+ * W1[h][i]: the first-layer weights [J][in_dim] of head h's segment i (text, visual, tracks1, tracks2) as the forward read them.
+ * GEMM core: modes 0 and 1 the exact f32-input MFMA; modes 2 and 3 bf16x3 (S is fp32 in every mode).  Outputs fp32, 16-byte
+ * aligned, ld_clip >= text_dim + visual_dim and ld_track >= track_dim (multiples of 4).  LIREC_EINVAL, before any device call,
+ * for NULL pointers, nh not 1 or 2, nseg != 4, J or the dims not multiples of 4 (or J differing between the heads), segment
+ * dims that disagree with `pieces`, misaligned outputs or strides. */
+typedef struct {
+  const lirec_embed_bwd_args* heads[2];
+  int32_t nh, reserved_;
+  const float* S[2];
+  const float* W1[2][LIREC_MAX_SEG];
+  const lirec_pieces* pieces;
+  float* dClip; int64_t ld_clip;
+  float* dTrack; int64_t ld_track;
+} lirec_embed_dx_indexed_args;
+int lirec_embed_dx_indexed(const lirec_embed_dx_indexed_args* a, lirec_stream_t stream);
 /* scratch lirec_embed_bwd needs: `rows` = the logical row count, plus n for the pooled form
  * (pass rows = n*R + n).  (Twice the fp32 gradient of the hidden layer, rows rounded up to 32: the plain form keeps
  * the fp32 gradient and its bf16 planes side by side when layer 1 runs on planes.) */

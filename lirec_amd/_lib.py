@@ -17,7 +17,7 @@ MAX_SEG = 4
 DEFAULT_GEMM_MODE = 2          # 0 exact f32-input MFMA, 1 naive cross-check, 2 split-precision bf16x3 MFMA (default), 3 single-pass bf16 on the large GEMMs
 
 SITE_H1_INTS, SITE_H1_CTX, SITE_E_INTS, SITE_E_CTX, SITE_GATE, SITE_TRACK_SAMPLE = 0, 1, 2, 3, 4, 5
-ABI_VERSION = 123
+ABI_VERSION = 124
 LIREC_EINVAL = 10001
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -92,6 +92,13 @@ class Pieces(C.Structure):
                 ('clip_q', _vp), ('track_q', _vp), ('clip_rows', _vp), ('track_rows', _vp)]
 
 
+class EmbedDxIndexedArgs(C.Structure):
+    """lirec_embed_dx_indexed_args (ABI 124): the gradient of the piece tables"""
+    _fields_ = [('heads', C.POINTER(EmbedBwdArgs) * 2), ('nh', _i32), ('reserved_', _i32), ('S', _vp * 2),
+                ('W1', (_vp * MAX_SEG) * 2), ('pieces', C.POINTER(Pieces)),
+                ('dClip', _vp), ('ld_clip', _i64), ('dTrack', _vp), ('ld_track', _i64)]
+
+
 class LinearFwdArgs(C.Structure):
     _fields_ = [('A', _vp), ('lda', _i64), ('W', _vp), ('b', _vp), ('Y', _vp), ('ldy', _i64),
                 ('n', _i32), ('K', _i32), ('N', _i32), ('reserved_', _i32)]
@@ -156,6 +163,7 @@ _PROTOS = {
     'lirec_embed_l1_indexed': (_i32, [C.POINTER(C.POINTER(EmbedFwdArgs)), _i32, C.POINTER(Pieces), C.POINTER(_vp), C.POINTER(_vp), _vp]),
     'lirec_embed_bwd2': (_i32, [C.POINTER(EmbedBwdArgs), C.POINTER(EmbedBwdArgs), _vp]),
     'lirec_embed_dx': (_i32, [C.POINTER(EmbedDxArgs), _vp]),
+    'lirec_embed_dx_indexed': (_i32, [C.POINTER(EmbedDxIndexedArgs), _vp]),
     'lirec_linear_fwd_group': (_i32, [C.POINTER(LinearFwdArgs), _i32, _vp]),
     'lirec_linear_bwd_group': (_i32, [C.POINTER(LinearBwdArgs), _i32, _vp]),
     'lirec_compact_rows': (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
@@ -227,7 +235,8 @@ def lib():
     for name, (res, args) in _PROTOS.items():
         fn = getattr(L, name)          # AttributeError if the symbol is missing
         fn.restype, fn.argtypes = res, args
-    for which, st in list(enumerate((EmbedFwdArgs, EmbedBwdArgs, MarginLossArgs, Dropout, RowSel))) + [(8, EmbedDxArgs)]:
+    for which, st in list(enumerate((EmbedFwdArgs, EmbedBwdArgs, MarginLossArgs, Dropout, RowSel))) + [(8, EmbedDxArgs),
+                                                                                                      (9, EmbedDxIndexedArgs)]:
         if L.lirec_abi_sizeof(which) != C.sizeof(st):
             raise LirecError('ABI mismatch for %s: library %d bytes, binding %d bytes'
                              % (st.__name__, L.lirec_abi_sizeof(which), C.sizeof(st)))

@@ -15,6 +15,11 @@
 // split on the fragment read.
 // Output: row m of a problem is logical row L = rowmap ? rowmap[m] : m, physical row (L / gs) * gstride + goff + L % gs of the
 // caller's (n, R+1, D) block (ld = ldc elements); fp32, or bf16 (round to nearest even) for a bf16 leaf.  Vector stores only.
+//
+// The same tiles serve the gradient of de-duplicated piece tables (lirec_embed_dx_indexed, dxi_gemm_kernel): a problem is one
+// table segment, its A operand the per-piece sums S of the hidden-layer gradient that lirec_embed_dw1_indexed left (fp32), and
+// its k-loop runs over a list of up to four (S, W1) chunks of K = J each -- one per (head, segment) that reads the table
+// segment -- so each output element still has one writer.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -55,6 +60,23 @@ struct DxZero {
   void* C; long ldc; int out_bf16;
 };
 
+// lirec_embed_dx_indexed: C[m, c_off + n] = sum over the chunks c of A_c[m, :] B_c[:, n]  (K = J per chunk), rows m < Ma read,
+// rows [Ma, M) written as 0 (the table's trailing zero row); fp32 output, plain row addressing.
+enum { DXI_MAX_PROB = 3, DXI_MAX_CHUNK = 4 };
+
+struct DxiProblem {
+  const float* A[DXI_MAX_CHUNK]; const float* B[DXI_MAX_CHUNK];
+  long lda, ldb;                  // (the same for every chunk: 2J for S, in_dim for W1)
+  int nchunk, M, Ma, N, K;
+  float* C; long ldc; long c_off;
+  int tiles_n, tile_start;
+};
+
+struct DxiGroup {
+  DxiProblem p[DXI_MAX_PROB];
+  int nprob;
+};
+
 typedef float dx_f32x16 __attribute__((ext_vector_type(16)));
 typedef float dx_f32x4 __attribute__((ext_vector_type(4)));
 typedef float dx_f32x2 __attribute__((ext_vector_type(2)));
@@ -91,6 +113,46 @@ __device__ __forceinline__ unsigned short dx_bf16_rne(float x) {
 }
 
 __device__ __forceinline__ float dx_bf(unsigned short h) { return __builtin_bit_cast(float, (unsigned)h << 16); }
+
+// One k-tile (BK = 32) of the 128 x 128 tile from the LDS operands (rows of P = 36 floats, B transposed): each wave adds its
+// 64 x 64 quarter, 2 x 2 blocks of 32 x 32.
+template <int CORE>
+__device__ __forceinline__ void dx_mma_ktile(const float* As, const float* Bs, dx_f32x16 (&acc)[2][2], int wm0, int wn0,
+                                             int l31, int lh) {
+  constexpr int BK = 32, P = BK + 4;
+  if constexpr (CORE == 0) {
+#pragma unroll
+    for (int kk = 0; kk < BK; kk += 2) {
+      float a[2], b[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) a[i] = As[(wm0 + 32 * i + l31) * P + kk + lh];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) b[j] = Bs[(wn0 + 32 * j + l31) * P + kk + lh];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
+    }
+  } else {
+#pragma unroll
+    for (int kk = 0; kk < BK; kk += 16) {
+      dx_bf16x8 ah[2], al[2], bh[2], bl[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) dx_frag(As + (wm0 + 32 * i + l31) * P + kk + 8 * lh, ah[i], al[i]);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) dx_frag(Bs + (wn0 + 32 * j + l31) * P + kk + 8 * lh, bh[j], bl[j]);
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          // (the small terms first, as gemm_bf16x3.hpp)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+        }
+    }
+  }
+}
 
 template <int CORE>
 __global__ void __launch_bounds__(256) dx_gemm_kernel(const DxGroup g) {
@@ -166,38 +228,7 @@ __global__ void __launch_bounds__(256) dx_gemm_kernel(const DxGroup g) {
     store();
     __syncthreads();
     if (kt + 1 < nk) load((kt + 1) * BK);                    // in flight during the MFMA block
-    if constexpr (CORE == 0) {
-#pragma unroll
-      for (int kk = 0; kk < BK; kk += 2) {
-        float a[2], b[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) a[i] = As[(wm0 + 32 * i + l31) * P + kk + lh];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) b[j] = Bs[(wn0 + 32 * j + l31) * P + kk + lh];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
-      }
-    } else {
-#pragma unroll
-      for (int kk = 0; kk < BK; kk += 16) {
-        dx_bf16x8 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) dx_frag(As + (wm0 + 32 * i + l31) * P + kk + 8 * lh, ah[i], al[i]);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) dx_frag(Bs + (wn0 + 32 * j + l31) * P + kk + 8 * lh, bh[j], bl[j]);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            // (the small terms first, as gemm_bf16x3.hpp)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-          }
-      }
-    }
+    dx_mma_ktile<CORE>(As, Bs, acc, wm0, wn0, l31, lh);
     __syncthreads();
   }
 
@@ -270,6 +301,92 @@ __global__ void __launch_bounds__(256) dx_zero_kernel(const DxZero z) {
       if (hh.in_off[s] + hh.in_dim[s] > at) at = hh.in_off[s] + hh.in_dim[s];
     }
     if (at < z.D) dx_zero_span(z, row, at, z.D, tid);
+  }
+}
+
+// The piece-table gradient: dx_gemm_kernel's tile, its k-loop over the problem's chunks in order (nk k-tiles each; the next
+// k-tile's loads -- across a chunk boundary too -- in flight during the MFMA block).  Rows [Ma, M) -- the trailing zero row --
+// are stored as 0 whatever A and B hold.
+template <int CORE>
+__global__ void __launch_bounds__(256) dxi_gemm_kernel(const DxiGroup g) {
+  constexpr int BM = 128, BN = 128, BK = 32, P = BK + 4;
+  __shared__ float As[BM * P];
+  __shared__ float Bs[BN * P];
+  int pi = 0;
+  while (pi + 1 < g.nprob && (int)blockIdx.x >= g.p[pi + 1].tile_start) ++pi;
+  const DxiProblem& p = g.p[pi];
+  const int t = (int)blockIdx.x - p.tile_start;
+  const int tm = t / p.tiles_n, tn = t - tm * p.tiles_n;
+  const int m0 = tm * BM, n0 = tn * BN;
+  const int M = p.M, Ma = p.Ma, N = p.N, K = p.K;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l31 = lane & 31, lh = lane >> 5;
+  const int wm0 = (wave >> 1) * 64, wn0 = (wave & 1) * 64;
+  const int nk = (K + BK - 1) / BK, nt = p.nchunk * nk;
+
+  dx_f32x4 ra[4], rb[4];
+  auto load = [&](int it) {
+    const int c = it / nk, k0 = (it - c * nk) * BK;
+    const float* A = p.A[c];
+    const float* B = p.B[c];
+    const int ka = k0 + 4 * (tid & 7);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int m = m0 + (tid >> 3) + 32 * i;
+      dx_f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (m < Ma && ka < K) v = *reinterpret_cast<const dx_f32x4*>(A + (long)m * p.lda + ka);
+      ra[i] = v;
+    }
+    const int n = n0 + 4 * (tid & 31), kb = k0 + 4 * (tid >> 5);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      dx_f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (n < N && kb + j < K) v = *reinterpret_cast<const dx_f32x4*>(B + (long)(kb + j) * p.ldb + n);
+      rb[j] = v;
+    }
+  };
+  auto store = [&]() {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) *reinterpret_cast<dx_f32x4*>(As + ((tid >> 3) + 32 * i) * P + 4 * (tid & 7)) = ra[i];
+    const int nl = 4 * (tid & 31), kl = 4 * (tid >> 5);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const dx_f32x4 v = {rb[0][c], rb[1][c], rb[2][c], rb[3][c]};
+      *reinterpret_cast<dx_f32x4*>(Bs + (nl + c) * P + kl) = v;
+    }
+  };
+
+  dx_f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  if (nt > 0) load(0);
+  for (int it = 0; it < nt; ++it) {
+    store();
+    __syncthreads();
+    if (it + 1 < nt) load(it + 1);
+    dx_mma_ktile<CORE>(As, Bs, acc, wm0, wn0, l31, lh);
+    __syncthreads();
+  }
+
+  // epilogue as dx_gemm_kernel's: a half-wave stores 32 consecutive elements of one row
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int m = m0 + wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
+      if (m >= M) continue;
+      float* row = p.C + (long)m * p.ldc + p.c_off;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int n = n0 + wn0 + 32 * j + l31;
+        if (n < N) row[n] = m < Ma ? acc[i][j][r] : 0.f;
+      }
+    }
   }
 }
 

@@ -970,6 +970,7 @@ int lirec_abi_sizeof(int which) {
     case 6: return (int)sizeof(lirec_linear_fwd_args);
     case 7: return (int)sizeof(lirec_linear_bwd_args);
     case 8: return (int)sizeof(lirec_embed_dx_args);
+    case 9: return (int)sizeof(lirec_embed_dx_indexed_args);
     default: return -1;
   }
 }
@@ -1803,6 +1804,58 @@ int lirec_embed_dx(const lirec_embed_dx_args* a, lirec_stream_t stream) {
     else lirec::launch(HIP_KERNEL_NAME(dx_gemm_kernel<0>), dim3(tiles), dim3(256), 0, s, g);
     LIREC_CHECK_LAUNCH();
   }
+  return LIREC_OK;
+}
+
+// Gradient of the piece tables (gemm_dx.hpp, dxi_gemm_kernel): three problems -- track, clip-visual, clip-text; the track
+// problem's tiles (twice the k-loop) first -- whose k-loops run over the (S, W1) chunks of every head that reads the segment.
+int lirec_embed_dx_indexed(const lirec_embed_dx_indexed_args* a, lirec_stream_t stream) {
+  if (!a || a->nh < 1 || a->nh > 2 || !a->pieces || !a->dClip || !a->dTrack) return LIREC_EINVAL;
+  const lirec_pieces* pc = a->pieces;
+  const int td = pc->text_dim, vd = pc->visual_dim, kd = pc->track_dim;
+  if (pc->n_clip < 1 || pc->n_track < 1 || td < 4 || vd < 4 || kd < 4 || (td & 3) || (vd & 3) || (kd & 3)) return LIREC_EINVAL;
+  if (a->ld_clip < td + vd || a->ld_track < kd || (a->ld_clip & 3) || (a->ld_track & 3) ||
+      ((reinterpret_cast<uintptr_t>(a->dClip) | reinterpret_cast<uintptr_t>(a->dTrack)) & 15) != 0)
+    return LIREC_EINVAL;
+  const int nh = a->nh;
+  int J = 0;
+  for (int h = 0; h < nh; ++h) {
+    const lirec_embed_bwd_args* b = a->heads[h];
+    if (!b || b->nseg != 4 || b->J < 4 || (b->J & 3) || (J && b->J != J) || b->rows < 0 || !a->S[h] ||
+        (reinterpret_cast<uintptr_t>(a->S[h]) & 15) != 0)
+      return LIREC_EINVAL;
+    if (b->in_dim[0] != td || b->in_dim[1] != vd || b->in_dim[2] != kd || b->in_dim[3] != kd) return LIREC_EINVAL;
+    for (int i = 0; i < 4; ++i)
+      if (!a->W1[h][i] || (reinterpret_cast<uintptr_t>(a->W1[h][i]) & 15) != 0) return LIREC_EINVAL;
+    J = b->J;
+  }
+  const long nc1 = pc->n_clip + 1;
+  DxiGroup g;
+  memset(&g, 0, sizeof(g));
+  int tiles = 0;
+  for (int q = 0; q < 3; ++q) {                  // 0 track, 1 clip-visual, 2 clip-text
+    DxiProblem& p = g.p[g.nprob++];
+    p.lda = 2L * J; p.K = J;
+    p.M = q == 0 ? pc->n_track + 1 : (int)nc1; p.Ma = p.M - 1;
+    p.N = q == 0 ? kd : (q == 1 ? vd : td); p.ldb = p.N;
+    p.C = q == 0 ? a->dTrack : a->dClip; p.ldc = q == 0 ? a->ld_track : a->ld_clip; p.c_off = q == 1 ? td : 0;
+    for (int h = 0; h < nh; ++h) {
+      if (a->heads[h]->rows == 0) continue;      // (lirec_embed_dw1_indexed wrote no S for it: it reads no piece)
+      if (q == 0) {
+        const float* St = a->S[h] + nc1 * 2 * J;     // [n_track + 1, 2J]: tracks1 | tracks2
+        for (int i = 0; i < 2; ++i) { p.A[p.nchunk] = St + (long)i * J; p.B[p.nchunk] = a->W1[h][2 + i]; ++p.nchunk; }
+      } else {
+        p.A[p.nchunk] = a->S[h] + (q == 1 ? J : 0); p.B[p.nchunk] = a->W1[h][q == 1 ? 1 : 0]; ++p.nchunk;
+      }
+    }
+    p.tiles_n = (p.N + 127) / 128;
+    p.tile_start = tiles;
+    tiles += ((p.M + 127) / 128) * p.tiles_n;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (g_bf_core) lirec::launch(HIP_KERNEL_NAME(dxi_gemm_kernel<1>), dim3(tiles), dim3(256), 0, s, g);
+  else lirec::launch(HIP_KERNEL_NAME(dxi_gemm_kernel<0>), dim3(tiles), dim3(256), 0, s, g);
+  LIREC_CHECK_LAUNCH();
   return LIREC_OK;
 }
 

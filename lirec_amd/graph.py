@@ -170,6 +170,11 @@ class RecordedTrainStep:
                 # (a replay re-issues the recorded launches and returns no autograd graph: the features' gradient would be dropped)
                 raise LirecError('RecordedTrainStep: the batch features require grad -- a recorded step computes no input gradient; '
                                  'run the eager step (model(batch) -> loss -> backward) instead')
+            pcs = b.get('feature_pieces') if isinstance(b, dict) else None
+            if isinstance(pcs, dict) and any(torch.is_tensor(pcs.get(k)) and pcs[k].requires_grad for k in ('clip', 'track')):
+                # (likewise for piece tables that require grad: a replay would drop their gradient)
+                raise LirecError('RecordedTrainStep: the batch\'s piece tables require grad -- a recorded step computes no input '
+                                 'gradient; run the eager step (model(batch) -> loss -> backward) instead')
         self.model, self.loss, self.optim, self.batch = model, loss, optimizer, batch
         self.batches = [batch, next_batch] if next_batch is not None else [batch]
         self.sync = getattr(model, 'grad_sync', None)

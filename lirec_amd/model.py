@@ -65,10 +65,11 @@ class _HotPathFn(torch.autograd.Function):
     """inters, rels = f(features; params).  ``params`` are passed only so autograd
     records the dependency; gradients are accumulated by the kernels directly into
     the model's flat gradient buffer (the ``.grad`` views), so backward returns None
-    for them."""
+    for them.  ``clip`` / ``track``: the piece tables of a ``feature_pieces`` batch when they require grad (else None) -- the
+    model reads them through ``_pieces_cur``; they are inputs here so that backward can return their gradients."""
 
     @staticmethod
-    def forward(ctx, model, X, mask, n, R, clamp, *params):
+    def forward(ctx, model, X, mask, n, R, clamp, clip, track, *params):
         st = model._run_forward(X, mask, n, R, clamp)
         ctx.model, ctx.st = model, st
         if model.debug_keep_state:
@@ -85,10 +86,13 @@ class _HotPathFn(torch.autograd.Function):
             gi = gouts.pop(0)
         if ctx.has[1]:
             gr = gouts.pop(0)
-        # the features' gradient (lirec_embed_dx) only when the caller's features require it: otherwise not a launch more
-        dX = ctx.model._run_backward(ctx.st, gi, gr, want_dx=bool(ctx.needs_input_grad[1]))
+        # the features' gradient (lirec_embed_dx) -- or the piece tables' (lirec_embed_dx_indexed) -- only when the caller's
+        # features or tables require it: otherwise not a launch more
+        want_dp = (bool(ctx.needs_input_grad[6]), bool(ctx.needs_input_grad[7]))
+        dX, dClip, dTrack = ctx.model._run_backward(ctx.st, gi, gr, want_dx=bool(ctx.needs_input_grad[1]), want_dp=want_dp)
         ctx.st = None
-        return (None, dX) + (None,) * (4 + len(ctx.model._plist))
+        return ((None, dX) + (None,) * 4 + (dClip if want_dp[0] else None, dTrack if want_dp[1] else None)
+                + (None,) * len(ctx.model._plist))
 
 
 class _StageFn(torch.autograd.Function):
@@ -343,7 +347,7 @@ class _HotPathModule(nn.Module):
         if not self.training and not (q32 or getattr(opt, 'layer1_planes_eval', False)):
             return None
         pcs = getattr(self, '_pieces_cur', None)
-        if pcs is not None and not getattr(opt, 'pieces_q32b', False):
+        if pcs is not None and (not getattr(opt, 'pieces_q32b', False) or pcs.get('requires_grad')):
             return None                                         # first layers on the unique pieces: no rows are staged
         # (rows gathered from q32b storage -- the block itself, or the piece tables: the workspace holds no copy of them)
         gathered = q32 or (pcs is not None and isinstance(pcs['clip'], ops.Q32Block))
@@ -428,12 +432,13 @@ class _HotPathModule(nn.Module):
         Wc = self._segs_c.width if has_c else 0
         # batch given as piece tables + index (lirec_amd.features): with opt.pieces_q32b (training steps) the q32b operand rows
         # of layer 1 are staged STRAIGHT from the tables -- the block is never built, and layer 1 / its weight gradient are the
-        # dense path's persistent kernels; otherwise the first layers run once per piece (lirec_embed_l1_indexed)
+        # dense path's persistent kernels; otherwise the first layers run once per piece (lirec_embed_l1_indexed) -- always so for
+        # tables that require grad: their gradient is formed from the per-piece sums that only the once-per-piece backward keeps
         pieces = getattr(self, '_pieces_cur', None)
         pc = ops.make_pieces(pieces['clip'], pieces['track'], pieces['index'], opt.text_dim, opt.visual_dim,
                              pieces.get('clip_rows'), pieces.get('track_rows')) if pieces is not None else None
         pq = pc if (pc is not None and has_i and has_c and getattr(opt, 'pieces_q32b', False) and getattr(opt, 'layer1_planes', False)
-                    and self.training) else None
+                    and self.training and not pieces.get('requires_grad')) else None
         pre = self._take_prestaged(X, mask, n, R) if (has_i and has_c and pieces is None) else None
         st['prestaged'] = pre is not None
         EE = ops.new((n, Wc + Wi), dtype=torch.float32, device=dev)     # [E_ctx | E_ints]
@@ -622,12 +627,16 @@ class _HotPathModule(nn.Module):
             self._sides[which] = _SIDE_LANES[key]
         return self._sides[which]
 
-    def _run_backward(self, st, d_inters, d_rels, want_dx=False):
-        """The hand-written backward; returns d loss / d X (the staged (n, R+1, D) block, X's dtype) when ``want_dx``, else None."""
+    def _run_backward(self, st, d_inters, d_rels, want_dx=False, want_dp=(False, False)):
+        """The hand-written backward; returns (dX, dClip, dTrack): d loss / d X (the staged (n, R+1, D) block, X's dtype) when
+        ``want_dx``, and d loss / d the piece tables (fp32, their shapes) when ``want_dp`` asks for either; None otherwise."""
         if want_dx and (not torch.is_tensor(st['X']) or st.get('pieces') is not None or st.get('pieces_gather') is not None
                         or st.get('prestaged')):
             raise LirecError('the features\' gradient is formed for a feature block (a tensor) only -- not for q32b storage, '
                              'piece tables or prestaged rows')
+        want_dp = any(want_dp)
+        if want_dp and st.get('pieces') is None:
+            raise LirecError('the piece tables\' gradient is formed on the once-per-piece path only (lirec_embed_l1_indexed)')
         self.flat_grads(attach=True)
         pieces = st.get('pieces')
         lane = self._wgrad_lane()
@@ -803,6 +812,7 @@ class _HotPathModule(nn.Module):
             run(1)
         if self.grad_sync is not None:
             self.grad_sync.bucket_ready(1, also=side2_h if lane2 is not None else side_h)   # second layers of both embeddings: final here
+        dClip = dTrack = None
         if pieces is not None:
             # batch given as unique pieces + index: hidden-layer gradients as usual, the context head's un-pool pass, then
             # the first-layer weight gradients from the pieces (incidence matrix of the index, two small GEMM stages)
@@ -814,6 +824,13 @@ class _HotPathModule(nn.Module):
             Ps = [ops.new((n * ldp,), dtype=torch.float32, device=dev), ops.new((n * R * ldp,), dtype=torch.float32, device=dev)]
             Ss = [ops.new(((nc1 + nt1) * 2 * J,), dtype=torch.float32, device=dev) for _ in range(2)]
             ops.embed_dw1_indexed([args_i, args_c], pc, Ps, Ss)
+            if want_dp:
+                # the tables' gradient from the per-piece sums S just formed (one launch), on this stream right behind them and
+                # with the weights the forward read -- like dX below, before the last bucket is announced
+                dClip = ops.new(pieces['clip'].shape, dtype=torch.float32, device=dev)
+                dTrack = ops.new(pieces['track'].shape, dtype=torch.float32, device=dev)
+                W1 = [[self._W(m1)[0] for m1, _ in mods] for mods in (self._mods_i, self._mods_c)]
+                ops.embed_dx_indexed([args_i, args_c], Ss, W1, pc, dClip, dTrack)
         else:
             # (data parallel or not: both heads' tails share their launches -- the first-layer weight gradients of the two
             #  heads are ONE persistent launch, so their bucket is announced once, at the end)
@@ -833,7 +850,7 @@ class _HotPathModule(nn.Module):
         # (for the optimiser: this backward left the side stream ordered behind every reader of the first bucket's parameters)
         self._side_after_backward = (side_h, main) if (lane is not None and has_g and has_i) else None
         self._side_unjoined = defer
-        return dX
+        return dX, dClip, dTrack
 
     # ---- first-layer weights kept in the q32b form (lirec_embed_fwd_args::W1q) -------------------------------------------------
     def first_layer_range(self):
@@ -927,9 +944,9 @@ class _HotPathModule(nn.Module):
             self._bucket0_end = ranges[0][1] if (stages and stages[0] == 0 and len(ranges) > 1) else 0
         return (side_h, self._bucket0_end) if self._bucket0_end > 0 else None
 
-    def _call_hot_path(self, X, mask, n, R, clamp):
+    def _call_hot_path(self, X, mask, n, R, clamp, tables=(None, None)):
         self._begin_forward()
-        outs = _HotPathFn.apply(self, X, mask, n, R, clamp, *self._plist)
+        outs = _HotPathFn.apply(self, X, mask, n, R, clamp, tables[0], tables[1], *self._plist)
         outs = list(outs)
         inters = outs.pop(0) if self._has_ints else None
         rels = outs.pop(0) if self._has_ctx else None
@@ -1053,16 +1070,25 @@ class MidFusionMultiClipMaxTracks(_MidFusionBase):
             # the batch as de-duplicated piece tables + index (lirec_amd.features.indexed_batch): the block is never built
             if not (self._has_ints and self._has_ctx):
                 raise LirecError('feature_pieces batches need the mixed recipe with both heads')
-            if any(torch.is_tensor(t) and t.requires_grad for t in pcs.values()):
-                raise LirecError('feature_pieces batches: the gradient cannot be returned to piece tables -- pass the feature block '
-                                 '(x[\'features\']) when the features require grad')
+            tables = (None, None)
+            if torch.is_grad_enabled() and any(torch.is_tensor(pcs.get(k)) and pcs[k].requires_grad for k in ('clip', 'track')):
+                # tables that require grad: made contiguous fp32 device tables by differentiable ops (their gradient goes back in
+                # each leaf's dtype and to its device), run on the once-per-piece path whatever opt.pieces_q32b says (its backward
+                # keeps the per-piece sums the tables' gradient is formed from), and handed to autograd as inputs of the hot path
+                if not (torch.is_tensor(pcs['clip']) and torch.is_tensor(pcs['track'])):
+                    raise LirecError('feature_pieces batches: tables that require grad must both be tensors (not q32b storage)')
+                dev = self._device()
+                pcs = dict(pcs, requires_grad=True)
+                for k in ('clip', 'track'):
+                    pcs[k] = pcs[k].to(device=dev, dtype=torch.float32).contiguous()
+                tables = (pcs['clip'], pcs['track'])
             idx = pcs['index']
             B, T, R = idx.shape[0], idx.shape[1], idx.shape[2] - 1
             X = torch.empty((0, R + 1, opt.mlp_dim), dtype=torch.float32, device=idx.device)
             mask = self._stage_mask(x['rels_mask'], idx.device, B * T, R)
             self._pieces_cur = pcs
             try:
-                inters, rels = self._call_hot_path(X, mask, B * T, R, 1)
+                inters, rels = self._call_hot_path(X, mask, B * T, R, 1, tables)
             finally:
                 self._pieces_cur = None
             return {'inters': inters.view(B, -1, self.n_classes), 'rels': rels.view(B, -1, self.n_rels) if rels is not None else None}
@@ -1145,8 +1171,8 @@ def _with_direct_backward(loss, inters, rels, d_ints, d_rels):
     node = _hot_node(inters)
     if node is None or (rels is not None and _hot_node(rels) is not node) or not loss.requires_grad:
         return loss
-    if node.needs_input_grad[1]:
-        return loss          # (the features require grad: the backward goes through autograd, which takes dX on to them)
+    if node.needs_input_grad[1] or node.needs_input_grad[6] or node.needs_input_grad[7]:
+        return loss          # (the features or piece tables require grad: the backward goes through autograd, which takes dX on to them)
     out = loss.as_subclass(_LossValue)
 
     def direct():

@@ -13,8 +13,8 @@ import threading
 import torch
 
 from . import _lib
-from ._lib import (Dropout, FusedAdamArgs, EmbedBwdArgs, EmbedDxArgs, EmbedFwdArgs, EvalArgs, LinearBwdArgs, LinearFwdArgs, MarginLossArgs, Pieces, RowSel,
-                   check, lib)
+from ._lib import (Dropout, FusedAdamArgs, EmbedBwdArgs, EmbedDxArgs, EmbedDxIndexedArgs, EmbedFwdArgs, EvalArgs, LinearBwdArgs,
+                   LinearFwdArgs, MarginLossArgs, Pieces, RowSel, check, lib)
 
 
 class _ThreadCell(threading.local):
@@ -464,6 +464,24 @@ def embed_dx(heads, W1, dX):
     a.dX, a.ldx = _p(dX), dX.shape[2]
     a.n, a.rp1, a.D = dX.shape[0], dX.shape[1], dX.shape[2]
     check(lib().lirec_embed_dx(C.byref(a), _stream()), 'lirec_embed_dx')
+
+
+def embed_dx_indexed(heads, S, W1, pieces, dClip, dTrack):
+    """Gradient of the piece tables (lirec_embed_dx_indexed): ``heads``, ``pieces`` and ``S`` = what the embed_dw1_indexed call
+    that just ran was given, ``W1`` = per head the first-layer weights of its four segments, ``dClip`` / ``dTrack`` = contiguous
+    fp32 device tensors of the tables' shapes (zero rows included) to overwrite."""
+    for t in (dClip, dTrack):
+        assert t.is_cuda and t.is_contiguous() and t.dim() == 2 and t.dtype == torch.float32
+    a = EmbedDxIndexedArgs()
+    a.nh = len(heads)
+    for h, (b, s, ws) in enumerate(zip(heads, S, W1)):
+        a.heads[h] = C.pointer(b)
+        a.S[h] = _p(s)
+        _fill(a.W1[h], [_p(w) for w in ws])
+    a.pieces = C.pointer(pieces)
+    a.dClip, a.ld_clip = _p(dClip), dClip.shape[1]
+    a.dTrack, a.ld_track = _p(dTrack), dTrack.shape[1]
+    check(lib().lirec_embed_dx_indexed(C.byref(a), _stream()), 'lirec_embed_dx_indexed')
 
 
 _MASK_DTYPES = {torch.float32: 0, torch.int64: 1, torch.float64: 2}
