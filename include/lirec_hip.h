@@ -479,6 +479,9 @@ int lirec_linear_bwd_group(const lirec_linear_bwd_args* v, int32_t count, lirec_
  *   max variant: sum_t relu(m - pos + max_c S*mask)            (:483-486,:557-562)
  * loss = lymbda * mean_b(ints part) + mean(rels part), the latter over B clips or,
  * with rels_mean_valid, over the clips whose label != NR (:407-418).
+ * Size limit: one workgroup per clip keeps the clip's sigmoid tables in LDS, 4 * (T*C + T*(NR+1) + 2*T + C + 20) bytes (the NR term
+ * only with rels), which must not exceed 160 KiB -- LIREC_EINVAL before any device call otherwise (C = 101, NR = 15: T <= 343).
+ * Any T within it is supported: the track softmax / sampler / argmax walk the tracks in steps of 64 lanes.
  */
 typedef struct {
   float* ints; int64_t ld_ints;           /* [B*T, C] logits (modified in place when mask_inplace) */
@@ -579,7 +582,9 @@ int lirec_counter_add(int64_t* ctr, const int64_t* inc_host, int32_t n, lirec_st
  * (mlp/test.py:50-67) and tiles a (B*T, C, NR) tensor in numpy; here one workgroup per clip adds into
  *   counters[0..6] = total, total_cl, total_rels, top1, trks_top1, cls_top1, rels_top1   (int64, device)
  * which the eval loop reads once at the end.  mem, y, r, g: as for the margin loss; with loader_types f64 /
- * i64 are read in place.  just_zeros: [B] bytes, NULL = none. */
+ * i64 are read in place.  just_zeros: [B] bytes, NULL = none.
+ * Size limit: 4 * (2*T*C + T*(2*NR+1) + 512) bytes of LDS per clip (the NR term only with rels) must not exceed 160 KiB --
+ * LIREC_EINVAL otherwise (C = 101, NR = 15: T <= 173 with rels). */
 typedef struct {
   const float* ints; int64_t ld_ints;     /* [B*T, C] logits */
   const float* rels; int64_t ld_rels;     /* [B*T, NR] or NULL */

@@ -1300,7 +1300,8 @@ __global__ __launch_bounds__(256) void margin_loss_kernel(const lirec_margin_los
   }
   __syncthreads();
 
-  // positive track (wave 0; lane t = track t, T <= 64 -- longer track lists take the serial loop below)
+  // positive track (wave 0; lane l holds tracks l, l + 64, ...: every loop below walks the tracks in steps of 64 lanes and
+  // carries its running state -- maxima, sums, cum_base / last_pos / pick, the best score -- from step to step)
   if (tid < 64) {
     const int lane = tid;
     int k = (a.sel && a.sel[b] >= 0) ? a.sel[b] : -1;
@@ -1314,7 +1315,7 @@ __global__ __launch_bounds__(256) void margin_loss_kernel(const lirec_margin_los
       apply_seed_offset(klo, khi, reinterpret_cast<const unsigned long long*>(a.sample_seed_dev));
       philox4((unsigned)b, 0u, (unsigned)LIREC_SITE_TRACK_SAMPLE, 0u, klo, khi, rnd);
       const float u = (float)(rnd[0] >> 8) * (1.0f / 16777216.0f);
-      // pass 1: maxima;  pass 2: sums;  pass 3: probabilities, their total, the pick -- T <= 64 makes every pass one step
+      // pass 1: maxima;  pass 2: sums;  pass 3: probabilities, their total, the pick (T <= 64: every pass is one step)
       float mxi = NEG_INF, mxr = NEG_INF;
       for (int t0 = 0; t0 < T; t0 += 64) {
         const int t = t0 + lane;

@@ -343,10 +343,18 @@ def _mean(v: torch.Tensor, divisor=None) -> torch.Tensor:
     return v.mean() if not divisor else v.sum() / divisor
 
 
+def _logits_dtype(out: dict) -> torch.dtype:
+    """dtype of the logits a loss is given (its value follows them)."""
+    for k in ('inters', 'rels'):
+        if out.get(k) is not None:
+            return out[k].dtype
+    return torch.get_default_dtype()
+
+
 def multitask_maxmargin_loss(cfg: OracleCfg, out: dict, batch: dict, n_rels: int, dp=None) -> torch.Tensor:
     """MultiTaskMaxMargin.forward (mlp/model.py:387-419); returns shape (1,).  ``dp`` = (clips, labelled clips) of the global batch,
     each over world: see ``_mean``; None = the reference's own means."""
-    loss = torch.zeros(1)
+    loss = torch.zeros(1, dtype=_logits_dtype(out))        # (float64 logits: a float64 loss, not a float32 accumulator)
     B = len(batch['rels_label'])
     div_b, div_r = dp if dp is not None else (None, None)
     if cfg.ints == 1:
@@ -457,7 +465,7 @@ def margin_track_rels_loss(cfg: OracleCfg, out: dict, batch: dict, n_rels: int, 
     pos = s[idx, k, y]
     posr = q[idx, k, r0]
     m = cfg.tr_margin
-    loss = torch.zeros(1)
+    loss = torch.zeros(1, dtype=s.dtype)
     if cfg.tr_max_neg and cfg.tr_sum_max_flag:
         nm = (s * mi.to(s.dtype)).max(dim=2)[0]
         nmr = (q * mr.to(q.dtype)).max(dim=2)[0]
