@@ -124,7 +124,7 @@ typedef struct {
                                            * pass + layer 2 (layer 1 done elsewhere: lirec_embed_l1_indexed); 4: stage the ROWS into `planes` and nothing
                                            * else (see rows_staged); lirec_embed_fwd2 wants the same value in both */
   /* Optional workspace (lirec_planes_bytes) for the PRE-SPLIT bf16 operand planes of layer 1.  When given (default GEMM
-   * core, segments adjacent in the feature row, in_dim % 32 == 0, J % 128 == 0, aligned X) the forward first writes the
+   * core, segments adjacent in the feature row, in_dim % 32 == 0, J % 128 == 0, aligned X; pooled form: R <= 64) the forward first writes the
    * selected feature rows as dense hi / lo bf16 planes -- compacted, when the compact form is used -- and the first-layer
    * weights likewise, and layer 1 runs on those planes with LDS-DMA staging (no conversion in the k-loop; same three
    * MFMAs per product, bit-identical results).  The backward call must be handed the same buffer: the weight gradient
@@ -236,7 +236,10 @@ int lirec_compact_rows2(const void* mask, int32_t mask_dtype, int32_t n, int32_t
  * dX is not formed here: a caller whose features require grad asks lirec_embed_dx for it once this call has run (ABI 123).
  * Pooled form (mask != NULL; rows = n*R, dZ2 is [n, sum out_dim]):
  *   dW2_s += dZ2_s^T Hbar_s, db2_s += sum_c f[c] dZ2_s[c,:], dHbar = dZ2_s W2_s  (n rows),
- *   dZ1[c,r,:] = dHbar[c,:] * mask[c,r]/div[c] * [H1[c,r,:] > 0] / (1-p), then dW1/db1 as above. */
+ *   dZ1[c,r,:] = dHbar[c,:] * mask[c,r]/div[c] * [H1[c,r,:] > 0] / (1-p), then dW1/db1 as above.
+ * Workspace layout of the pooled form, with rows32 = rows rounded up to 32 and W = nseg*J: dZ1 [rows, W] fp32 at float 0 (compact
+ * form: one row per valid context row, in rowmap order) -- or, on the `planes` path, its bf16 hi plane [rows32, W] at byte 0 and
+ * the lo plane right behind it; dHbar [n, W] fp32 at float rows32 * W, behind either (parts 3 writes it, parts 4 / 5 read it). */
 typedef struct {
   const float* X; int64_t ldx;
   const float* W2[LIREC_MAX_SEG];

@@ -482,6 +482,9 @@ static bool plane_layout(const Args* a, PlaneLayout& L) {
   if (!((g_gemm_mode == 2 && a->x_q32 != 3) || (g_gemm_mode == 3 && (a->x_q32 == 3 || staged16))) || !a->planes || a->rows < 1 || (g_ablate & 8)) return false;
   if (staged16 && (a->x_q32 != 0 || pieces_of(a) || rows_without_x(a) || !a->X || (reinterpret_cast<uintptr_t>(a->X) & 15) != 0 || ((a->ldx * 2) & 15) != 0))
     return false;
+  // (a pooled head with more than 64 context rows: the streaming un-pool kernel, the only one that writes dZ1 as planes, holds one
+  //  row weight per lane -- forward and backward fall back together, to the per-candidate kernels and the on-the-fly GEMMs)
+  if ((a->mask != nullptr || a->rowmap != nullptr) && a->R > 64) return false;
   const bool gather = rows_gathered(a);
   if (a->x_q32 >= 2 && pieces_of(a)) return false;             // (q16b / q16c storage: the block form only)
   if (const lirec_pieces* pc = pieces_of(a)) {
