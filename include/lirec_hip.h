@@ -559,7 +559,9 @@ int lirec_ce_loss(const float* ints, int64_t ld_ints, const float* rels, int64_t
  * torch.optim.Adam(lr, weight_decay) as configured at mlp/model.py:599-601, fused over
  * one flat fp32 buffer: g += wd*p; m = lerp(m, g, 1-b1); v = b2*v + (1-b2) g^2;
  * p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps).  grad_scale multiplies g first
- * (1/world_size after a summing all-reduce). `step` is 1-based. */
+ * (1/world_size after a summing all-reduce). `step` is 1-based.
+ * p, g, m, v must be 16-byte aligned (the kernel moves them four floats at a time; `n` may be any count): LIREC_EINVAL
+ * otherwise, from lirec_adam_step and lirec_adam_step_counted alike, before any device call. */
 int lirec_adam_step(float* p, const float* g, float* m, float* v, int64_t n, int32_t step,
                     float lr, float beta1, float beta2, float eps, float weight_decay,
                     float grad_scale, const int64_t* step_dev, lirec_stream_t stream);

@@ -2345,10 +2345,17 @@ int lirec_ce_loss(const float* ints, int64_t ld_ints, const float* rels, int64_t
 }
 
 // ---------------------------------------------------------------------------
+// adam_kernel reads and writes p, g, m, v as f32x4 from the pointers it is given
+static bool adam_aligned(const float* p, const float* g, const float* m, const float* v) {
+  return ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+           reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+}
+
 int lirec_adam_step(float* p, const float* g, float* m, float* v, int64_t n, int32_t step,
                     float lr, float beta1, float beta2, float eps, float weight_decay,
                     float grad_scale, const int64_t* step_dev, lirec_stream_t stream) {
   if (!p || !g || !m || !v || n < 0 || (step < 1 && !step_dev)) return LIREC_EINVAL;
+  if (!adam_aligned(p, g, m, v)) return LIREC_EINVAL;
   if (step < 1) step = 1;
   if (n == 0) return LIREC_OK;
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
@@ -2371,6 +2378,7 @@ int lirec_adam_step_counted(float* p, const float* g, float* m, float* v, int64_
                             float lr, float beta1, float beta2, float eps, float weight_decay,
                             float grad_scale, int64_t* count_dev, int32_t* ticket, int32_t advance, lirec_stream_t stream) {
   if (!p || !g || !m || !v || n < 1 || !count_dev || !ticket) return LIREC_EINVAL;
+  if (!adam_aligned(p, g, m, v)) return LIREC_EINVAL;
   long blocks = (n / 4 + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;

@@ -103,10 +103,10 @@ class FusedAdam(torch.optim.Optimizer):
 
     @staticmethod
     def _minus(lo, hi, skip):
-        """[lo, hi) without the ranges in ``skip``: a list of (a, b)"""
+        """[lo, hi) without the ranges in ``skip``: a list of (a, b); a range with b <= a is empty"""
         out, a = [], lo
         for s0, s1 in sorted(skip):
-            if s1 <= a or s0 >= hi:
+            if s1 <= s0 or s1 <= a or s0 >= hi:
                 continue
             if s0 > a:
                 out.append((a, min(s0, hi)))

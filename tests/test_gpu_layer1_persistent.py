@@ -474,9 +474,17 @@ def test_two_heads_one_and_three_segments():
 # ---------------------------------------------------------------------------------------------------------------------------
 # the fused first-layer Adam (lirec_fused_adam) against the unfused gradient + ops.adam_step, and the q32b / q16c shadow of W1
 # ---------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('J,rows,dims,storage,mode', [(256, 33, [256, 512], 'f32', 2), (1024, 257, [256], 'f32', 2),
-                                                      (256, 257, [256, 512], 'q16c', 3)])
-def test_fused_first_layer_adam(J, rows, dims, storage, mode):
+# (the forms of the update itself, at the smallest shape: the first step from zero moments, the step read from a device counter,
+#  a gradient scale, no weight decay, and no shadow of the new weights)
+FUSED_ADAM_FORMS = ['step1', 'step_dev7', 'gs0125', 'wd0', 'nowq']
+
+
+@pytest.mark.parametrize('J,rows,dims,storage,mode,form',
+                         [pytest.param(256, 33, [256, 512], 'f32', 2, None, id='256-33-dims0-f32-2'),
+                          pytest.param(1024, 257, [256], 'f32', 2, None, id='1024-257-dims1-f32-2'),
+                          pytest.param(256, 257, [256, 512], 'q16c', 3, None, id='256-257-dims2-q16c-3')] +
+                         [pytest.param(256, 33, [256, 512], 'f32', 2, f, id='256-33-dims0-f32-2-' + f) for f in FUSED_ADAM_FORMS])
+def test_fused_first_layer_adam(J, rows, dims, storage, mode, form):
     g = torch.Generator().manual_seed(J + rows)
     h = Head('plain', rows, J, dims, 0)
     D = (sum(dims) + 63) // 64 * 64
@@ -501,7 +509,17 @@ def test_fused_first_layer_adam(J, rows, dims, storage, mode):
     gflat0 = (torch.randn(n, generator=g) * 0.01).to(DEV)
     m0 = (torch.randn(n, generator=g) * 0.01).to(DEV)
     v0 = (torch.rand(n, generator=g) * 1e-4).to(DEV)
-    hyper = dict(step=3, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-5)
+    hyper = dict(step=3, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-5, grad_scale=1.0, step_dev=None)
+    if form == 'step1':
+        hyper['step'] = 1
+        m0.zero_(); v0.zero_()
+    elif form == 'step_dev7':
+        hyper.update(step=0, step_dev=torch.tensor([7], dtype=torch.int64, device=DEV))
+    elif form == 'gs0125':
+        hyper['grad_scale'] = 0.125
+    elif form == 'wd0':
+        hyper['weight_decay'] = 0.0
+    shadow = form != 'nowq'
     L = _lib.lib()
     ops.set_gemm_mode(mode)
     try:
@@ -523,9 +541,10 @@ def test_fused_first_layer_adam(J, rows, dims, storage, mode):
                 t.copy_(t0)
             flat.copy_(p0)
             m, v = m0.clone(), v0.clone()
-            wq = torch.zeros(4 * n, dtype=torch.uint8, device=DEV)
+            wq = torch.full((4 * n,), 0 if shadow else 0x5A, dtype=torch.uint8, device=DEV)
             adam = ops.fused_adam_args(flat, gflat, m, v, n_params, hyper['step'], hyper['lr'], hyper['beta1'], hyper['beta2'],
-                                       hyper['eps'], hyper['weight_decay'], wq=wq, wq_first=0) if fused else None
+                                       hyper['eps'], hyper['weight_decay'], grad_scale=hyper['grad_scale'], step_dev=hyper['step_dev'],
+                                       wq=wq if shadow else None, wq_first=0) if fused else None
             ops.profile_enable(True)
             ops.embed_bwd(args=bwd_args(h, s, X, D, adam=adam))
             bs = prof_sites()
@@ -540,7 +559,10 @@ def test_fused_first_layer_adam(J, rows, dims, storage, mode):
     (g1, _, _, _, _), (g2, p2, m2, v2, wq) = results
     assert torch.equal(g1, g2), 'the fused call stores another gradient'
     pr, mr, vr = p0.clone(), m0.clone(), v0.clone()
-    ops.adam_step(pr, g1, mr, vr, hyper['step'], hyper['lr'], hyper['beta1'], hyper['beta2'], hyper['eps'], hyper['weight_decay'])
+    ops.adam_step(pr, g1, mr, vr, hyper['step'], hyper['lr'], hyper['beta1'], hyper['beta2'], hyper['eps'], hyper['weight_decay'],
+                  grad_scale=hyper['grad_scale'], step_dev=hyper['step_dev'])
+    if hyper['step_dev'] is not None:
+        assert int(hyper['step_dev']) == 7
     rng = torch.zeros(n, dtype=torch.bool, device=DEV)
     for i, d in enumerate(dims):
         rng[offs[i]:offs[i] + J * d] = True
@@ -548,6 +570,10 @@ def test_fused_first_layer_adam(J, rows, dims, storage, mode):
     for got, want, what in ((p2, pr, 'parameters'), (m2, mr, 'exp_avg'), (v2, vr, 'exp_avg_sq')):
         assert torch.equal(got[rng], want[rng]), what + ' differ from ops.adam_step on the unfused gradient'
         assert torch.equal(got[~rng], (p0 if what == 'parameters' else (m0 if what == 'exp_avg' else v0))[~rng]), what + ': outside W1 / b1'
+    assert bool((pr[rng] != p0[rng]).any()) and bool((vr[rng] != v0[rng]).any())
+    if not shadow:
+        assert bool((wq == 0x5A).all()), 'no shadow was asked for, and the buffer a shadow would go to was written'
+        return
     for i, d in enumerate(dims):
         neww = pr[offs[i]:offs[i] + J * d].view(J, d).contiguous()
         if mode == 3:
