@@ -573,6 +573,27 @@ int lirec_adam_step(float* p, const float* g, float* m, float* v, int64_t n, int
 int lirec_adam_step_counted(float* p, const float* g, float* m, float* v, int64_t n,
                             float lr, float beta1, float beta2, float eps, float weight_decay,
                             float grad_scale, int64_t* count_dev, int32_t* ticket, int32_t advance, lirec_stream_t stream);
+/* The same update over a scattered set of ranges of the flat buffers, one launch: what a partly frozen model needs (parameters
+ * with requires_grad = False keep their values AND their moments; lirec_amd/optim.py).  `ranges` (HOST memory, copied into the
+ * launch by value): `count` <= LIREC_ADAM_MAX_RANGES entries, ascending and disjoint; element offsets from p / g / m / v that
+ * are multiples of 4 (every parameter of the flat layout starts on one), any length >= 0.  Range r is updated with step
+ * t - lag[r] -- the number of updates ITS parameters have received, torch.optim.Adam's per-parameter `step` -- where t is
+ *   `step` by value (step_dev and count_dev NULL; step - lag >= 1 for every range),
+ *   *step_dev, or
+ *   *count_dev + 1, with ticket / advance exactly as in lirec_adam_step_counted
+ * (a device step below 1 after the lag counts as 1).  Element for element the arithmetic -- and the bits -- of lirec_adam_step
+ * on that range with that step; nothing outside the ranges is read or written.  count == 0, or all lengths 0: no launch (and no
+ * advance).  LIREC_EINVAL before any device call for: count outside 0..64, a negative length, offset or lag, an offset that is not
+ * a multiple of 4, p / g / m / v not 16-byte aligned, ranges overlapping or out of order, a by-value step with step - lag < 1,
+ * step_dev together with count_dev, count_dev without ticket. */
+#define LIREC_ADAM_MAX_RANGES 64
+typedef struct {
+  int64_t offset, length;                /* elements */
+  int32_t lag, reserved_;
+} lirec_adam_range;
+int lirec_adam_step_ranges(float* p, const float* g, float* m, float* v, const lirec_adam_range* ranges, int32_t count,
+                           int32_t step, float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                           const int64_t* step_dev, int64_t* count_dev, int32_t* ticket, int32_t advance, lirec_stream_t stream);
 /* `step_dev` (optional, device): when not NULL the 1-based step is read from it by the kernel instead of `step`
  * (bias corrections computed on the device), so that a captured graph advances through the steps.
  * lirec_counter_add: ctr[i] += inc[i] for i < n (n <= 4), one tiny kernel -- the "next step" node of such a graph. */

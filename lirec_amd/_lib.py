@@ -99,6 +99,14 @@ class EmbedDxIndexedArgs(C.Structure):
                 ('dClip', _vp), ('ld_clip', _i64), ('dTrack', _vp), ('ld_track', _i64)]
 
 
+class AdamRange(C.Structure):
+    """lirec_adam_range: one range of the flat buffers and the steps its parameters sat out (lirec_adam_step_ranges)"""
+    _fields_ = [('offset', _i64), ('length', _i64), ('lag', _i32), ('reserved_', _i32)]
+
+
+ADAM_MAX_RANGES = 64
+
+
 class LinearFwdArgs(C.Structure):
     _fields_ = [('A', _vp), ('lda', _i64), ('W', _vp), ('b', _vp), ('Y', _vp), ('ldy', _i64),
                 ('n', _i32), ('K', _i32), ('N', _i32), ('reserved_', _i32)]
@@ -188,6 +196,8 @@ _PROTOS = {
     'lirec_ce_loss': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _f32, _f32, _vp, _vp]),
     'lirec_adam_step': (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _vp]),
     'lirec_adam_step_counted': (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _i32, _vp]),
+    'lirec_adam_step_ranges': (_i32, [_vp, _vp, _vp, _vp, C.POINTER(AdamRange), _i32, _i32, _f32, _f32, _f32, _f32, _f32, _f32,
+                                      _vp, _vp, _vp, _i32, _vp]),
     'lirec_counter_add': (_i32, [_vp, C.POINTER(C.c_int64), _i32, _vp]),
     'lirec_eval_max_tracks': (_i32, [C.POINTER(EvalArgs), _vp]),
     'lirec_cast_f64_f32': (_i32, [_vp, _vp, _i64, _vp]),
@@ -236,7 +246,8 @@ def lib():
         fn = getattr(L, name)          # AttributeError if the symbol is missing
         fn.restype, fn.argtypes = res, args
     for which, st in list(enumerate((EmbedFwdArgs, EmbedBwdArgs, MarginLossArgs, Dropout, RowSel))) + [(8, EmbedDxArgs),
-                                                                                                      (9, EmbedDxIndexedArgs)]:
+                                                                                                      (9, EmbedDxIndexedArgs),
+                                                                                                      (10, AdamRange)]:
         if L.lirec_abi_sizeof(which) != C.sizeof(st):
             raise LirecError('ABI mismatch for %s: library %d bytes, binding %d bytes'
                              % (st.__name__, L.lirec_abi_sizeof(which), C.sizeof(st)))

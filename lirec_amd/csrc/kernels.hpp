@@ -1638,6 +1638,76 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   }
 }
 
+// The same update over a scattered set of ranges of the flat buffers in ONE launch (lirec_adam_step_ranges: the trainable
+// parameters of a partly frozen model).  Range r = [off[r], off[r] + len[r]) with off a multiple of 4, updated with step t - lag[r]:
+// a parameter that sat out `lag` steps frozen has received that many updates fewer (torch.optim.Adam keeps one step per
+// parameter).  The work is dealt in blocks of ADAM_RANGE_BLOCK elements numbered across the ranges (one f32x4 per thread and
+// block), a workgroup taking every gridDim.x-th; the block -> range lookup is a loop over the by-value table with nothing but
+// workgroup-uniform values in it.  Each element goes through adam4 / adam1 -- a range gives the bits adam_kernel gives on it
+// with that step.  t: by value (the host then fills step_size / bc2_sqrt per range, as lirec_adam_step does), or from step_dev
+// or the count_dev / ticket / advance triple of adam_kernel (the two factors then computed here, in double, per range).
+#define ADAM_MAX_RANGES 64
+#define ADAM_RANGE_BLOCK 1024
+struct AdamRanges {
+  long off[ADAM_MAX_RANGES], len[ADAM_MAX_RANGES];
+  int lag[ADAM_MAX_RANGES];
+  float step_size[ADAM_MAX_RANGES], bc2_sqrt[ADAM_MAX_RANGES];       // by-value step only
+  int count;
+};
+__global__ __launch_bounds__(256) void adam_ranges_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                          float* __restrict__ m, float* __restrict__ v, const AdamRanges rt,
+                                                          long nblocks, float beta1, float beta2, float eps, float wd,
+                                                          float gscale, float lr, const long long* __restrict__ step_dev,
+                                                          long long* count_dev, int* ticket, int advance) {
+  long long t_counted = 0;
+  if (count_dev) t_counted = __hip_atomic_load(count_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
+  const bool dev_step = step_dev || count_dev;
+  const long long t_dev = count_dev ? t_counted : (step_dev ? *step_dev : 0);
+  const AdamFuse ad{p, g, m, v, 0.f, 0.f, beta1, beta2, eps, wd, gscale, lr, step_dev};
+  int cur = -1;
+  float step_size = 0.f, bc2_sqrt = 1.f;
+  for (long wb = blockIdx.x; wb < nblocks; wb += gridDim.x) {
+    long b = wb;
+    int r = 0;
+    for (; r < rt.count - 1; ++r) {
+      const long nb = (rt.len[r] + ADAM_RANGE_BLOCK - 1) / ADAM_RANGE_BLOCK;
+      if (b < nb) break;
+      b -= nb;
+    }
+    if (r != cur) {               // (uniform: a workgroup's blocks ascend, so once per range it touches)
+      cur = r;
+      if (dev_step) {
+        long long tr = t_dev - rt.lag[r];
+        if (tr < 1) tr = 1;
+        step_size = (float)((double)lr / (1.0 - pow((double)beta1, (double)tr)));
+        bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)tr));
+      } else {
+        step_size = rt.step_size[r]; bc2_sqrt = rt.bc2_sqrt[r];
+      }
+    }
+    const long first = b * ADAM_RANGE_BLOCK;                  // within the range
+    long left = rt.len[r] - first;
+    if (left > ADAM_RANGE_BLOCK) left = ADAM_RANGE_BLOCK;
+    const long e = 4L * threadIdx.x;
+    const long at = rt.off[r] + first + e;
+    if (e + 4 <= left) {
+      (void)adam4(ad, step_size, bc2_sqrt, at, *reinterpret_cast<const f32x4*>(g + at));
+    } else {
+      for (long j = 0; e + j < left; ++j) (void)adam1(ad, step_size, bc2_sqrt, at + j, g[at + j]);
+    }
+  }
+  if (count_dev && advance) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int tk = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (tk == (int)gridDim.x - 1) {
+        __hip_atomic_store(count_dev, t_counted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void cast_f64_f32_kernel(const double* __restrict__ src, float* __restrict__ dst, long n) {
   const long stride = (long)gridDim.x * blockDim.x;
   const long n2 = n >> 1;

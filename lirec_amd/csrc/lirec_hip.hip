@@ -974,6 +974,7 @@ int lirec_abi_sizeof(int which) {
     case 7: return (int)sizeof(lirec_linear_bwd_args);
     case 8: return (int)sizeof(lirec_embed_dx_args);
     case 9: return (int)sizeof(lirec_embed_dx_indexed_args);
+    case 10: return (int)sizeof(lirec_adam_range);
     default: return -1;
   }
 }
@@ -2387,6 +2388,44 @@ int lirec_adam_step_counted(float* p, const float* g, float* m, float* v, int64_
                      0.f, 0.f, beta1, beta2, eps, weight_decay, grad_scale, lr, (const long long*)nullptr,
                      (long long*)count_dev, (int*)ticket, (int)(advance != 0));
   prof_stop(pi, (hipStream_t)stream, 0.0, 28.0 * (double)n);
+  LIREC_CHECK_LAUNCH();
+  return LIREC_OK;
+}
+
+int lirec_adam_step_ranges(float* p, const float* g, float* m, float* v, const lirec_adam_range* ranges, int32_t count,
+                           int32_t step, float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                           const int64_t* step_dev, int64_t* count_dev, int32_t* ticket, int32_t advance, lirec_stream_t stream) {
+  if (!p || !g || !m || !v || count < 0 || count > LIREC_ADAM_MAX_RANGES || (count > 0 && !ranges)) return LIREC_EINVAL;
+  if (!adam_aligned(p, g, m, v)) return LIREC_EINVAL;
+  if (step_dev && count_dev) return LIREC_EINVAL;
+  if (count_dev && !ticket) return LIREC_EINVAL;
+  const bool by_value = !step_dev && !count_dev;
+  static_assert(LIREC_ADAM_MAX_RANGES == ADAM_MAX_RANGES, "the header's table size is the kernel's");
+  AdamRanges rt;
+  memset(&rt, 0, sizeof(rt));
+  long nblocks = 0;
+  int64_t end = 0, total = 0;                                  // ascending, disjoint
+  for (int r = 0; r < count; ++r) {
+    const lirec_adam_range& q = ranges[r];
+    if (q.length < 0 || q.offset < 0 || (q.offset & 3) != 0 || q.lag < 0 || q.offset < end) return LIREC_EINVAL;
+    if (by_value && (int64_t)step - q.lag < 1) return LIREC_EINVAL;
+    end = q.offset + q.length; total += q.length;
+    rt.off[r] = (long)q.offset; rt.len[r] = (long)q.length; rt.lag[r] = q.lag;
+    if (by_value) {
+      const double t = (double)(step - q.lag);
+      rt.step_size[r] = (float)((double)lr / (1.0 - pow((double)beta1, t)));
+      rt.bc2_sqrt[r] = (float)sqrt(1.0 - pow((double)beta2, t));
+    }
+    nblocks += (long)((q.length + ADAM_RANGE_BLOCK - 1) / ADAM_RANGE_BLOCK);
+  }
+  rt.count = count;
+  if (nblocks == 0) return LIREC_OK;
+  const long blocks = nblocks > 2048 ? 2048 : nblocks;
+  const int pi = prof_start(PS_ADAM, (hipStream_t)stream);
+  lirec::launch(adam_ranges_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, rt, nblocks,
+                beta1, beta2, eps, weight_decay, grad_scale, lr, (const long long*)step_dev, (long long*)count_dev,
+                (int*)ticket, (int)(advance != 0));
+  prof_stop(pi, (hipStream_t)stream, 0.0, 28.0 * (double)total);
   LIREC_CHECK_LAUNCH();
   return LIREC_OK;
 }

@@ -95,13 +95,17 @@ def _fill_sentinel(g):
 def _overwrite_coverage(model, g) -> bool:
     """After a backward in overwrite mode on a buffer ``_fill_sentinel`` filled: was every PARAMETER element written?  Elements
     still holding the sentinel (unwritten parameters -- their gradient is 0 -- and the alignment gaps) are zeroed; a genuine NaN
-    gradient (divergence) has another payload and stays, as it would in the eager loop.  One device reduction, one host sync."""
+    gradient (divergence) has another payload and stays, as it would in the eager loop.  One device reduction, one host sync.
+    A FROZEN parameter (requires_grad False) needs no writer -- nothing reads its gradient: its elements count like the gaps."""
     mask = getattr(model, '_param_elem_mask', None)
-    if mask is None or mask.device != g.device or mask.numel() != g.numel():
+    flags = tuple(p.requires_grad for p in model._plist)
+    if mask is None or mask.device != g.device or mask.numel() != g.numel() or getattr(model, '_param_elem_mask_flags', None) != flags:
         mask = torch.zeros(g.numel(), dtype=torch.bool, device=g.device)
-        for off, k in model._offsets.values():
-            mask[off:off + k] = True
-        model._param_elem_mask = mask
+        live = {n for (n, _), f in zip(torch.nn.Module.named_parameters(model), flags) if f}
+        for n, (off, k) in model._offsets.items():
+            if n in live:
+                mask[off:off + k] = True
+        model._param_elem_mask, model._param_elem_mask_flags = mask, flags
     unwritten = g.view(torch.int32) == _SENTINEL
     covered = not bool((unwritten & mask).any())
     g.masked_fill_(unwritten, 0.0)
@@ -231,6 +235,12 @@ class RecordedTrainStep:
         self.fused = bool(self.sync is None and getattr(_opt, 'fuse_dw1_adam', True) and getattr(model, 'last_layer1_planes', False)
                           and getattr(model, '_has_ints', False) and getattr(model, '_has_ctx', False)
                           and hasattr(optimizer, 'arm_first_layer_update') and hasattr(model, 'refresh_w1q'))
+        if self.fused and hasattr(optimizer, 'trainable_ranges') and not optimizer.all_trainable():
+            # (first layers PARTLY trainable, or behind: the optimiser does not arm the fused update -- the ordinary update writes no
+            #  shadow, the forward stages the weights itself.  Frozen altogether: nothing writes them, the shadow stays current.)
+            lo, hi, _ = model.first_layer_range()
+            if optimizer.trainable_ranges(lo, hi) not in ([], [(lo, hi, 0)]):
+                self.fused = False
         if self.fused:
             self.fused = model.refresh_w1q()
         # (does the recorded forward read the q32b shadow of the first-layer weights?  step() rebuilds a stale one before it replays)
@@ -352,14 +362,20 @@ class RecordedTrainStep:
         """Host mirrors of the device counters (checkpoints, switching back to the eager loop)."""
         self.model._fwd_train_calls += 1
         self.optim._step += 1
+        if hasattr(self.optim, '_advance_lags'):
+            self.optim._advance_lags()              # (frozen parameters sat this update out, as in the eager step())
         if hasattr(self.loss, '_sample_key'):
             self.loss._sample_calls += 1
 
     @staticmethod
     def hyper_key(optimizer):
-        """the optimiser hyper-parameters a recorded step carries BY VALUE (lirec_adam_step's arguments)"""
+        """the optimiser hyper-parameters a recorded step carries BY VALUE (lirec_adam_step's arguments) -- and, when any
+        parameter is frozen or behind, the requires_grad flags and the trainable parameters' lags: they decided which launches
+        were recorded and are in the recorded lirec_adam_step_ranges tables (FusedAdam.frozen_key)"""
         g = optimizer.param_groups[0]
-        return (float(g['lr']), tuple(float(b) for b in g['betas']), float(g['eps']), float(g['weight_decay']), float(getattr(optimizer, 'grad_scale', 1.0)))
+        key = (float(g['lr']), tuple(float(b) for b in g['betas']), float(g['eps']), float(g['weight_decay']), float(getattr(optimizer, 'grad_scale', 1.0)))
+        frozen = optimizer.frozen_key() if hasattr(optimizer, 'frozen_key') else ()
+        return key + (frozen,) if frozen else key
 
     def _check_core(self):
         if ops.get_gemm_mode() != self._gemm_mode:

@@ -71,7 +71,7 @@ class _HotPathFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, X, mask, n, R, clamp, clip, track, *params):
         st = model._run_forward(X, mask, n, R, clamp)
-        ctx.model, ctx.st = model, st
+        ctx.model, ctx.st, ctx.n_params = model, st, len(params)
         if model.debug_keep_state:
             model.last_state = st             # tests read the saved activations (relu decisions) back
         outs = [o for o in (st['inters'], st['rels']) if o is not None]
@@ -92,7 +92,7 @@ class _HotPathFn(torch.autograd.Function):
         dX, dClip, dTrack = ctx.model._run_backward(ctx.st, gi, gr, want_dx=bool(ctx.needs_input_grad[1]), want_dp=want_dp)
         ctx.st = None
         return ((None, dX) + (None,) * 4 + (dClip if want_dp[0] else None, dTrack if want_dp[1] else None)
-                + (None,) * len(ctx.model._plist))
+                + (None,) * ctx.n_params)
 
 
 class _StageFn(torch.autograd.Function):
@@ -109,6 +109,65 @@ class _StageFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         return g.to(device=ctx.device).to(ctx.dtype), None
+
+
+class TrainablePlan:
+    """Which launches of the hand-written backward a set of ``requires_grad`` flags still needs.  Parameters are grouped the way
+    the launches are (``_HotPathModule.param_group_of``); a group is LIVE when any parameter in it requires grad, and it then runs as
+    ever -- a partly frozen group is not cheaper, its frozen members' gradient slices are written and never read.  ``need()`` names
+    the launches by reachability from the live groups (and from a wanted input gradient) along the chain
+
+        loss -> out_ctx / out_ints data gradients -> gate data gradient -> dEE -> per head: second-layer weight gradient,
+        hidden-layer gradient + tail (un-pool, first-layer weight gradient, input gradient)
+
+    ``flags``: the tuple it was made from; ``live``: group -> bool, for the groups the model has."""
+
+    LAUNCHES = ('out_ints_dW', 'out_ctx_dW', 'out_ints_dA', 'out_ctx_dA', 'gate_stage', 'gate_dW', 'gate_dEE',
+                'dW2_i', 'dW2_c', 'tail_i', 'tail_c')
+
+    def __init__(self, flags, live, has_gate):
+        self.flags, self.live, self.has_gate = tuple(flags), dict(live), bool(has_gate)
+        self.all_live = all(self.flags)
+        self._need = {}
+
+    def need(self, want_input=False):
+        """frozenset of LAUNCHES.  ``want_input``: the caller wants the features' or the piece tables' gradient.  ('gate_stage':
+        the staging of dZg's rows on the q32b path -- it runs where the path has it and one of the gate's two launches does.)"""
+        want_input = bool(want_input)
+        if want_input in self._need:
+            return self._need[want_input]
+        L, has = self.live, (lambda g: g in self.live)
+        out = set()
+        dee = {}
+        for h in ('i', 'c'):
+            if not has('L1_' + h):
+                dee[h] = False
+                continue
+            tail = L['L1_' + h] or want_input
+            dw2 = L.get('L2_' + h, False)
+            if tail:
+                out.add('tail_' + h)
+            if dw2:
+                out.add('dW2_' + h)
+            dee[h] = tail or dw2               # this head's half of dEE is read
+        gate = self.has_gate and has('gate')
+        if gate:
+            if dee['i'] or dee['c']:
+                out.add('gate_dEE')            # (one launch forms both halves)
+            if L['gate']:
+                out.add('gate_dW')
+            if out & {'gate_dEE', 'gate_dW'}:
+                out.add('gate_stage')
+                out.add('out_ints_dA')         # dZg: read by both of the gate's launches
+        elif has('out_ints') and dee['i']:
+            out.add('out_ints_dA')             # (no gate: it writes the interaction half of dEE itself)
+        if has('out_ctx') and dee['c']:
+            out.add('out_ctx_dA')
+        for g in ('out_ints', 'out_ctx'):
+            if L.get(g, False):
+                out.add(g + '_dW')
+        self._need[want_input] = frozenset(out)
+        return self._need[want_input]
 
 
 class _HotPathModule(nn.Module):
@@ -217,8 +276,10 @@ class _HotPathModule(nn.Module):
         return self._flat
 
     def flat_grads(self, attach=True):
-        """The flat gradient buffer; (re)attaches every ``p.grad`` as a view of it.  Grads that
-        were set to None (optimizer.zero_grad(set_to_none=True)) count as zero."""
+        """The flat gradient buffer; (re)attaches ``p.grad`` of every TRAINABLE parameter as a view of it.  Grads that
+        were set to None (optimizer.zero_grad(set_to_none=True)) count as zero.  A frozen parameter (``requires_grad`` False) has
+        no gradient, as under autograd: a view attached while it was trainable is dropped, its slice of the buffer has
+        unspecified content (a launch that serves a partly frozen group writes it) and nothing reads it."""
         if self._flat_grad is None or self._flat_grad.device != self._flat.device:
             self._flat_grad = torch.zeros_like(self._flat)
             pd = dict(self.named_parameters())
@@ -231,12 +292,20 @@ class _HotPathModule(nn.Module):
             fresh = False
         if attach:
             pairs = self._grad_views
-            if all(p.grad is v for p, v in pairs):
+            if all(p.grad is v for p, v in pairs) and all(p.requires_grad for p, _ in pairs):
                 return self._flat_grad
-            all_none = all(p.grad is None for p, _ in pairs)
+            live = []
+            for p, view in pairs:
+                if p.requires_grad:
+                    live.append((p, view))
+                elif p.grad is view:
+                    p.grad = None
+            if all(p.grad is v for p, v in live):
+                return self._flat_grad
+            all_none = all(p.grad is None for p, _ in live)
             if all_none and not fresh:
                 self._flat_grad.zero_()
-            for p, view in pairs:
+            for p, view in live:
                 if p.grad is None:
                     if not all_none and not fresh:
                         view.zero_()
@@ -246,6 +315,33 @@ class _HotPathModule(nn.Module):
                         view.copy_(p.grad)
                     p.grad = view
         return self._flat_grad
+
+    # ---- frozen parameters: what backward still has to run ---------------------------------------------------------------
+    def param_group_of(self, name):
+        """the launch group of a parameter: out_ints, out_ctx, gate, L2_i, L2_c (second layers of the interaction / context
+        embedding), L1_i, L1_c (their first layers)"""
+        from .parallel import stage_of
+        if name.startswith('out_'):
+            return name.split('.')[0]
+        if name.startswith('gates_'):
+            return 'gate'
+        return ('L2_' if stage_of(name) == 1 else 'L1_') + ('i' if name.split('.')[0].endswith('_ints') else 'c')
+
+    def trainable_plan(self):
+        """``TrainablePlan`` of the parameters' ``requires_grad`` flags as they are now -- a pure function of them (and of which
+        groups the model has), cached on the tuple of flags: users unfreeze between epochs.  Needs no GPU."""
+        flags = tuple(p.requires_grad for p in self._plist)
+        plan = self.__dict__.get('_plan')
+        if plan is None or plan.flags != flags:
+            names = getattr(self, '_pnames', None)
+            if names is None:
+                names = self._pnames = [n for n, _ in nn.Module.named_parameters(self)]
+            live = {}
+            for n, f in zip(names, flags):
+                grp = self.param_group_of(n)
+                live[grp] = live.get(grp, False) or bool(f)
+            plan = self._plan = TrainablePlan(flags, live, has_gate=bool(getattr(self, '_has_gate', False)))
+        return plan
 
     def _g(self, name):
         """gradient view (flat slice) of parameter ``name``"""
@@ -639,6 +735,11 @@ class _HotPathModule(nn.Module):
             raise LirecError('the piece tables\' gradient is formed on the once-per-piece path only (lirec_embed_l1_indexed)')
         self.flat_grads(attach=True)
         pieces = st.get('pieces')
+        # what the parameters' requires_grad flags leave to do (TrainablePlan; everything, with every parameter trainable).  On the
+        # once-per-piece path the two heads' tails share launches throughout: there they are pruned together or not at all.
+        need = self.trainable_plan().need(want_dx or want_dp)
+        if pieces is not None and ('tail_i' in need or 'tail_c' in need):
+            need = need | {'tail_i', 'tail_c'}
         lane = self._wgrad_lane()
         main = ops.current_stream_handle() if lane is not None else None
         side_h = C.c_void_p(lane[0].cuda_stream) if lane is not None else None
@@ -685,7 +786,7 @@ class _HotPathModule(nn.Module):
         def join_side():
             if lane is not None and not defer:
                 ops.stream_wait(main, side_h)
-            if lane2 is not None:
+            if lane2 is not None and forked2:
                 ops.stream_wait(main, side2_h)
         X, n, R, J = st['X'], st['n'], st['R'], opt.joint_dim
         dev = X.device
@@ -706,8 +807,9 @@ class _HotPathModule(nn.Module):
 
         # relationship head: dW, db and the raw d(E_ctx) (tanh/dropout factor applied later
         # when the gate adds its share; directly when there is no gate)
-        heads = []
-        if has_c:
+        heads, head_names = [], []
+        if has_c and ('out_ctx_dW' in need or 'out_ctx_dA' in need):
+            head_names.append('out_ctx')
             Wo, _ = self._W('out_ctx')
             if d_rels is None:
                 d_rels = ops.zero_(ops.new((n, Wo.shape[0]), dtype=torch.float32, device=dev))
@@ -715,7 +817,8 @@ class _HotPathModule(nn.Module):
                           self._g('out_ctx.weight'), self._g('out_ctx.bias'), _ptr(dEE), ldee,
                           0 if has_g else 2, None if has_g else _ptr(Tn), ldee, 0, drop(0, SITE_E_CTX)))
         dZg = None
-        if has_i:
+        if has_i and ('out_ints_dW' in need or 'out_ints_dA' in need):
+            head_names.append('out_ints')
             Wo, _ = self._W('out_ints')
             if d_inters is None:
                 d_inters = ops.zero_(ops.new((n, Wo.shape[0]), dtype=torch.float32, device=dev))
@@ -731,12 +834,22 @@ class _HotPathModule(nn.Module):
                               self._g('out_ints.weight'), self._g('out_ints.bias'), _ptr(dEE, Wc), ldee,
                               2, _ptr(Tn, Wc), ldee, 0, drop(0, SITE_E_INTS)))
         one_fork = bool(heads) and lane is not None and has_i and has_g
+        # (frozen parameters: a head that is not live is left out of the weight-gradient list, one whose data gradient nobody
+        #  reads out of the other; a launch -- or a fork -- with nothing in it is not issued)
+        heads_w = [h for h, nm in zip(heads, head_names) if nm + '_dW' in need]
+        heads_a = [h for h, nm in zip(heads, head_names) if nm + '_dA' in need]
         if heads and lane is not None:
-            if not one_fork:
-                on_side(lambda: ops.linear_bwd_group(heads, parts=1))   # dW / db of the heads beside ...
-            ops.linear_bwd_group(heads, parts=2)                        # ... their data gradients
+            if not one_fork and heads_w:
+                on_side(lambda: ops.linear_bwd_group(heads_w, parts=1))   # dW / db of the heads beside ...
+            if heads_a:
+                ops.linear_bwd_group(heads_a, parts=2)                    # ... their data gradients
+        elif heads and len(heads_w) == len(heads) == len(heads_a):
+            ops.linear_bwd_group(heads)           # the heads: one launch for the dW's, one for the dA's
         elif heads:
-            ops.linear_bwd_group(heads)           # both heads: one launch for the dW's, one for the dA's
+            if heads_w:
+                ops.linear_bwd_group(heads_w, parts=1)
+            if heads_a:
+                ops.linear_bwd_group(heads_a, parts=2)
         if has_i and has_g:
             G = st['G']
             N = G.shape[1]
@@ -748,16 +861,21 @@ class _HotPathModule(nn.Module):
             # (q32b path: the rows of dZg are staged once, here, for the weight gradient on the side stream and the data gradient
             #  on this one)
             staged = False
-            if st.get('gate_ws') is not None and lane is not None:
+            g_dw, g_dee = 'gate_dW' in need, 'gate_dEE' in need
+            if st.get('gate_ws') is not None and lane is not None and (g_dw or g_dee):
                 gate(4)
                 staged = True
             if one_fork:
                 # one hand-over for both: the heads' weight gradients have waited for nothing but the loss, and the side
                 # stream has slack -- each event record costs the main stream a ~6 us bubble
-                on_side(lambda: (ops.linear_bwd_group(heads, parts=1), gate(1)))
-                gate(2)
-            else:
+                if heads_w or g_dw:
+                    on_side(lambda: (ops.linear_bwd_group(heads_w, parts=1) if heads_w else None, gate(1) if g_dw else None))
+                if g_dee:
+                    gate(2)
+            elif g_dw and g_dee:
                 gate(0)
+            elif g_dw or g_dee:
+                gate(1 if g_dw else 2)
         if self.grad_sync is not None:
             # (the collective waits for both streams; the main chain is not held up by the side stream's weight gradients)
             self.grad_sync.bucket_ready(0, also=side_h)
@@ -770,8 +888,12 @@ class _HotPathModule(nn.Module):
         if adam is not None and not (has_i and has_c and pieces is None and st.get('planes_i') is not None
                                      and st.get('planes_c') is not None and self.grad_sync is None):
             adam = None
+        if adam is not None and not ('tail_i' in need and 'tail_c' in need):
+            adam = None          # (a frozen first layer: the optimiser does not arm the fused update then -- belt and braces)
         self._dw1_adam_applied = adam is not None
-        if has_i:
+        work_i = has_i and ('dW2_i' in need or 'tail_i' in need)
+        work_c = has_c and ('dW2_c' in need or 'tail_c' in need)
+        if work_i:
             mods, segs = self._mods_i, self._segs_i
             ws_i = ops.new(ops.workspace_bytes(n, segs.n, J) // 4, dtype=torch.float32, device=dev)
             args_i = ops.embed_bwd_args(X, D, (1, Rp1, 0), n, J, segs, [self._W(b)[0] for _, b in mods], st['H1_i'],
@@ -779,7 +901,7 @@ class _HotPathModule(nn.Module):
                                         [self._g(a + '.weight') for a, _ in mods], [self._g(a + '.bias') for a, _ in mods],
                                         [self._g(b + '.weight') for _, b in mods], [self._g(b + '.bias') for _, b in mods],
                                         ws_i, drop(SITE_H1_INTS), planes=st.get('planes_i'), pieces=st.get('pieces_gather'), adam=adam)
-        if has_c:
+        if work_c:
             # context embed (pooled form): dW2/db2 and d(Hbar) on the n pooled rows, un-pool fused with the
             # relu/dropout backward, then dW1/db1 over the n*R context rows
             mods, segs = self._mods_c, self._segs_c
@@ -795,17 +917,29 @@ class _HotPathModule(nn.Module):
 
         def run(parts, which=None):
             """parts of the embed backward (include/lirec_hip.h: 1 second-layer weight gradients, 2 the rest, 3 hidden-layer
-            gradients only, 4 the tail -- un-pool and dW1 -- only); both heads share launches where a part covers both"""
-            if which is None and args_i is not None and args_c is not None:
-                ops.embed_bwd2(ops.with_parts(args_i, parts), ops.with_parts(args_c, parts))
+            gradients only, 4 the tail -- un-pool and dW1 -- only); both heads share launches where a part covers both.  A head
+            whose parameters of that part are frozen (and whose input gradient nobody wants) is left out: the other one's call is
+            then the single-head lirec_embed_bwd"""
+            key = 'dW2_' if parts == 1 else 'tail_'
+            a_i = args_i if key + 'i' in need else None
+            a_c = args_c if key + 'c' in need else None
+            if which is None and a_i is not None and a_c is not None:
+                ops.embed_bwd2(ops.with_parts(a_i, parts), ops.with_parts(a_c, parts))
             else:
-                for a in ((args_i, args_c) if which is None else (which,)):
+                for a in ((a_i, a_c) if which is None else (which,)):
                     if a is not None:
                         ops.embed_bwd(args=ops.with_parts(a, parts))
         # (the interaction head's dW1 on the side stream as well measured 2.5 % SLOWER: it competes with the context head's
         #  256x256 split-K launch for whole CUs)
-        if lane2 is not None:
+        forked2 = False
+        if not ('dW2_i' in need or 'dW2_c' in need):
+            # (both second layers frozen: their lane is not forked.  The first side stream is still put behind this point of the
+            #  main one -- the wait on_side2 makes for it: the first bucket's update runs there, after the gate's data gradient)
+            if lane2 is not None and (heads_w or 'gate_dW' in need):
+                ops.stream_wait(side_h, main)
+        elif lane2 is not None:
             on_side2(lambda: run(1))         # second-layer weight gradients beside the rest of the chain, on their own stream
+            forked2 = True
         elif lane is not None:
             on_side(lambda: run(1))
         else:
@@ -813,7 +947,9 @@ class _HotPathModule(nn.Module):
         if self.grad_sync is not None:
             self.grad_sync.bucket_ready(1, also=side2_h if lane2 is not None else side_h)   # second layers of both embeddings: final here
         dClip = dTrack = None
-        if pieces is not None:
+        if not ('tail_i' in need or 'tail_c' in need):
+            pass                 # (both first layers frozen and no input gradient wanted: no hidden-layer gradient, no un-pool, no dW1)
+        elif pieces is not None:
             # batch given as unique pieces + index: hidden-layer gradients as usual, the context head's un-pool pass, then
             # the first-layer weight gradients from the pieces (incidence matrix of the index, two small GEMM stages)
             run(3)
@@ -946,7 +1082,16 @@ class _HotPathModule(nn.Module):
 
     def _call_hot_path(self, X, mask, n, R, clamp, tables=(None, None)):
         self._begin_forward()
-        outs = _HotPathFn.apply(self, X, mask, n, R, clamp, tables[0], tables[1], *self._plist)
+        extra = ()
+        if torch.is_grad_enabled() and not any(p.requires_grad for p in self._plist) \
+                and not any(torch.is_tensor(t) and t.requires_grad for t in (X, tables[0], tables[1])):
+            # every parameter frozen and no input gradient wanted: autograd would hand back logits that require no grad, and
+            # ``loss.backward()`` -- the call every train loop makes -- would raise.  An empty leaf keeps the graph connected; the
+            # backward it reaches finds nothing to do (TrainablePlan) and issues no launch.
+            if getattr(self, '_anchor', None) is None or self._anchor.device != self._flat.device:
+                self._anchor = torch.zeros(0, device=self._flat.device, requires_grad=True)
+            extra = (self._anchor,)
+        outs = _HotPathFn.apply(self, X, mask, n, R, clamp, tables[0], tables[1], *self._plist, *extra)
         outs = list(outs)
         inters = outs.pop(0) if self._has_ints else None
         rels = outs.pop(0) if self._has_ctx else None

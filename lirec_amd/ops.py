@@ -723,6 +723,23 @@ def adam_step(p, g, m, v, step, lr, beta1, beta2, eps, weight_decay, grad_scale=
                                 grad_scale, _p(step_dev), _stream()), 'lirec_adam_step')
 
 
+def adam_step_ranges(p, g, m, v, ranges, step, lr, beta1, beta2, eps, weight_decay, grad_scale=1.0, step_dev=None,
+                     count_dev=None, ticket=None, advance=True):
+    """lirec_adam_step_ranges: one launch over ``ranges`` = [(offset, length, lag), ...] (at most 64, ascending, offsets
+    multiples of 4) of the flat buffers p, g, m, v given WHOLE (or from one common 16-byte-aligned base); range r is updated
+    with step t - lag, t = ``step``, ``step_dev`` or ``count_dev`` + 1 (then ``ticket`` / ``advance`` as in adam_step_counted)."""
+    from ._lib import AdamRange
+    n = p.numel()
+    assert g.numel() == n and m.numel() == n and v.numel() == n
+    assert all(0 <= o and 0 <= k and o + k <= n for o, k, _ in ranges), 'a range outside the buffers'
+    arr = (AdamRange * max(len(ranges), 1))()
+    for a, (o, k, lag) in zip(arr, ranges):
+        a.offset, a.length, a.lag = int(o), int(k), int(lag)
+    check(lib().lirec_adam_step_ranges(_p(p), _p(g), _p(m), _p(v), arr, len(ranges), int(step), lr, beta1, beta2, eps, weight_decay,
+                                       grad_scale, _p(step_dev), _p(count_dev), _p(ticket), int(bool(advance)), _stream()),
+          'lirec_adam_step_ranges')
+
+
 def counter_add(ctr, incs):
     """ctr[i] += incs[i] on the device (ctr: int64 device tensor, len(incs) <= 4)."""
     assert ctr.dtype == torch.int64 and ctr.is_cuda and 1 <= len(incs) <= 4 and ctr.numel() >= len(incs)

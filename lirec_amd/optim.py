@@ -8,6 +8,14 @@ decay, bias correction, eps outside the sqrt) and the same ``state_dict`` layout
 (``step`` / ``exp_avg`` / ``exp_avg_sq`` per parameter, in ``model.parameters()``
 order), so optimizer states of reference checkpoints load unchanged
 (utils/util_functions.py:283-291).
+
+Frozen parameters (``p.requires_grad_(False)``) are honoured as torch.optim.Adam honours a ``grad is None``: ``step()`` updates
+exactly the parameters that require grad when it is called; a frozen one keeps its value and its moments bit for bit, and its
+``state[p]['step']`` -- the number of updates IT has received -- stops.  That count is kept as a lag behind the global step
+(``_lag``); the trainable parameters become ranges ``(offset, length, lag)`` of the flat buffers, and a stretch of an update
+that is not simply one zero-lag range is one ``lirec_adam_step_ranges`` launch.  One difference from torch 1.1 (the
+reference's pin), none from current torch: there ``zero_grad()`` zeroes a gradient instead of dropping it, so a parameter frozen
+AFTER it has trained keeps being updated on a zero gradient (weight decay and its old momentum); here it stops.
 """
 from __future__ import annotations
 
@@ -23,6 +31,7 @@ class FusedAdam(torch.optim.Optimizer):
     def __init__(self, model, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5):
         self.model = model
         params = list(model.parameters())
+        self._names = [n for n, _ in model.named_parameters()]        # (in the order of model._plist)
         # (amsgrad: part of torch.optim.Adam's param_groups since torch 1.1 -- the reference's pin -- so that an
         #  optimizer state_dict saved here has the keys a stock Adam expects, and the other way round)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False))
@@ -31,6 +40,8 @@ class FusedAdam(torch.optim.Optimizer):
         self.grad_scale = 1.0          # 1/world_size after a summing all-reduce
         self._step_dev = None          # device int64[1]: the step kept on the GPU (lirec_amd.graph)
         self._step_side_dev = None     # device int64[1]: the same as the weight-gradient side stream counts it (step(): side update)
+        self._lag = {}                 # parameter name -> updates it sat out frozen (missing = 0): state[p]['step'] = _step - lag
+        self._ranges_key = self._ranges = None
 
     # -- flat state -----------------------------------------------------------
     def _ensure_state(self):
@@ -48,7 +59,7 @@ class FusedAdam(torch.optim.Optimizer):
                 st = old.get(id(p))
                 if st:
                     m.copy_(st['exp_avg']); v.copy_(st['exp_avg_sq'])
-                self.state[p] = {'step': torch.tensor(float(self._step)), 'exp_avg': m, 'exp_avg_sq': v}
+                self.state[p] = {'step': torch.tensor(float(self._step - self._lag.get(n, 0))), 'exp_avg': m, 'exp_avg_sq': v}
             if flat.is_cuda:
                 # (the fills above are on the current stream; the first bucket's update runs on ANOTHER stream -- the weight-gradient
                 #  side stream, or the collectives' launch stream -- that was ordered behind this one during backward, i.e. before
@@ -91,6 +102,12 @@ class FusedAdam(torch.optim.Optimizer):
         m = self.model
         if getattr(m, 'grad_sync', None) is not None or not hasattr(m, 'first_layer_range'):
             return False
+        if not self.all_trainable():
+            # (the fused launch updates EVERY first-layer parameter of the call with the one global step: only when each of them
+            #  is trainable and has received every update so far)
+            lo, hi, _ = m.first_layer_range()
+            if self.trainable_ranges(lo, hi) != [(lo, hi, 0)]:
+                return False
         grp = self.param_groups[0]
         flat, g = m.flat_params(), m.flat_grads(attach=True)
         hyper = (max(self._step + (1 if self._step_dev is None else 0), 1), grp['lr'], grp['betas'][0], grp['betas'][1], grp['eps'],
@@ -100,6 +117,92 @@ class FusedAdam(torch.optim.Optimizer):
         m._dw1_adam = ops.fused_adam_args(flat, g, self._m, self._v, n_params, *hyper,
                                           wq=m._w1q_buf if valid else None, wq_first=m._w1q_first if valid else 0)
         return True
+
+    # -- frozen parameters ------------------------------------------------------
+    def _flags(self):
+        return tuple(p.requires_grad for p in self.model._plist)
+
+    def all_trainable(self):
+        """every parameter requires grad and has received every update (the state this optimiser was written for)"""
+        return not self._lag and all(self._flags())
+
+    def frozen_key(self):
+        """what a recorded step has baked in of the frozen set: the requires_grad flags and the trainable parameters' lags
+        (lirec_amd.graph.RecordedTrainStep.hyper_key); () with nothing frozen and no lag"""
+        if self.all_trainable():
+            return ()
+        flags = self._flags()
+        return (flags, tuple(self._lag.get(n, 0) for n, f in zip(self._names, flags) if f))
+
+    @staticmethod
+    def merged_ranges(offsets, trainable, lags, extent):
+        """The trainable ranges [(start, end, lag)] of a flat layout, ascending.  ``offsets``: name -> (offset, numel) in flat
+        order; ``trainable``: name -> bool; ``lags``: name -> int (missing = 0); ``extent``: the buffer's length.  Neighbours in the
+        layout that are both trainable with the same lag are merged ACROSS the alignment gap between them (the gap holds zeros in
+        all four buffers, which the update leaves zeros -- as the whole-buffer launch always has), and a trainable last parameter
+        takes the buffer's tail: with everything trainable the result is the one range (0, extent, 0)."""
+        out, prev_live = [], False
+        names = list(offsets)
+        for i, n in enumerate(names):
+            off, k = offsets[n]
+            live = bool(trainable[n])
+            if live:
+                end = extent if i == len(names) - 1 else off + k
+                lag = int(lags.get(n, 0))
+                if prev_live and out[-1][2] == lag:
+                    out[-1] = (out[-1][0], end, lag)
+                else:
+                    out.append((off, end, lag))
+            prev_live = live
+        return out
+
+    def trainable_ranges(self, lo=None, hi=None):
+        """merged_ranges of the model as it is now (cached on the flags and lags), cut to [lo, hi) when given"""
+        m = self.model
+        flags = self._flags()
+        key = (flags, tuple(sorted(self._lag.items())), id(m._offsets))
+        if key != self._ranges_key:
+            self._ranges = self.merged_ranges(m._offsets, dict(zip(self._names, flags)), self._lag, m._flat.numel())
+            self._ranges_key = key
+        if lo is None:
+            return list(self._ranges)
+        return [(max(a, lo), min(b, hi), lag) for a, b, lag in self._ranges if min(b, hi) > max(a, lo)]
+
+    @staticmethod
+    def _chunks(rs, most=64):
+        """a list of ranges cut into the tables of single lirec_adam_step_ranges calls (64 entries at the most)"""
+        return [rs[i:i + most] for i in range(0, len(rs), most)]
+
+    def _advance_lags(self):
+        """one update has been issued: every parameter that sat it out falls one further behind"""
+        if self._lag or not all(self._flags()):
+            for n, f in zip(self._names, self._flags()):
+                if not f:
+                    self._lag[n] = self._lag.get(n, 0) + 1
+
+    def _update(self, flat, g, a, b, args, g_is_slice=False, counted=None, last=True):
+        """The update of stretch [a, b) of the flat buffers -- ``g``: the flat gradient buffer, or (``g_is_slice``) the b - a
+        gradients of the stretch on their own.  One zero-lag range: the whole-stretch launch, as ever; nothing trainable: no
+        launch; anything else: lirec_adam_step_ranges, 64 ranges a call.  ``counted`` = (count_dev, ticket): the step from the
+        side stream's own counter, ``last``: this stretch is the last of the update (the last launch advances the counter).
+        Returns the number of launches issued."""
+        rs = [(a, b, 0)] if self._all_live else self.trainable_ranges(a, b)
+        gs = g if g_is_slice else g[a:b]
+        if rs == [(a, b, 0)]:
+            if counted is not None:
+                ops.adam_step_counted(flat[a:b], gs, self._m[a:b], self._v[a:b], *args[1:7], counted[0], counted[1], advance=last)
+            else:
+                ops.adam_step(flat[a:b], gs, self._m[a:b], self._v[a:b], *args)
+            return 1
+        chunks = self._chunks(rs)
+        for i, ch in enumerate(chunks):
+            rel = [(x - a, y - x, lag) for x, y, lag in ch]
+            if counted is not None:
+                ops.adam_step_ranges(flat[a:b], gs, self._m[a:b], self._v[a:b], rel, 0, *args[1:7], count_dev=counted[0],
+                                     ticket=counted[1], advance=last and i == len(chunks) - 1)
+            else:
+                ops.adam_step_ranges(flat[a:b], gs, self._m[a:b], self._v[a:b], rel, *args)
+        return len(chunks)
 
     @staticmethod
     def _minus(lo, hi, skip):
@@ -119,6 +222,7 @@ class FusedAdam(torch.optim.Optimizer):
     def step(self, closure=None):
         loss = closure() if closure is not None else None
         self._ensure_state()
+        self._all_live = self.all_trainable()
         grp = self.param_groups[0]
         g = self.model.flat_grads(attach=True)
         if self._step_dev is None:
@@ -128,6 +232,8 @@ class FusedAdam(torch.optim.Optimizer):
         flat = self.model.flat_params()
         sync = self.model.grad_sync
         if sync is not None and sync.world > 1:
+            if getattr(opt, 'strict', False) and hasattr(sync, 'check_frozen_set'):
+                sync.check_frozen_set(self._flags())
             self.model._bucket0_on_side = False
             # data parallel: each bucket is updated as its reduction lands, the later buckets still in flight.  Sharded
             # (the default, lirec_amd.parallel): this rank holds the summed gradients of ITS slice of the bucket only, updates
@@ -140,12 +246,12 @@ class FusedAdam(torch.optim.Optimizer):
                     #  and gathered on the collective's launch stream, beside the tail of backward: GradSync.early_stream)
                     with ops.on_stream(C.c_void_p(early.cuda_stream)), torch.cuda.stream(early):
                         if b > a:
-                            ops.adam_step(flat[a:b], sync.grad_slice(g, lo, hi), self._m[a:b], self._v[a:b], *args)
+                            self._update(flat, sync.grad_slice(g, lo, hi), a, b, args, g_is_slice=True)
                         sync.gather_params(lo, hi)
                     used = early
                 else:
                     if b > a:
-                        ops.adam_step(flat[a:b], sync.grad_slice(g, lo, hi), self._m[a:b], self._v[a:b], *args)
+                        self._update(flat, sync.grad_slice(g, lo, hi), a, b, args, g_is_slice=True)
                     sync.gather_params(lo, hi)
                 done += hi - lo
             assert done == flat.numel(), 'gradient buckets do not cover the parameter buffer'
@@ -161,11 +267,13 @@ class FusedAdam(torch.optim.Optimizer):
             if self.model.__dict__.pop('_dw1_adam_applied', False):
                 skip.append((self.model.first_layer_range()[0], flat.numel()))
             elif getattr(self.model, '_w1q_valid', False):
-                self.model.invalidate_w1q()
+                # (... unless the first layers are frozen altogether: nothing writes those weights, the shadow stays current)
+                if self._all_live or self.trainable_ranges(*self.model.first_layer_range()[:2]):
+                    self.model.invalidate_w1q()
 
             def update(lo, hi):
                 for a, b in self._minus(lo, hi, skip):
-                    ops.adam_step(flat[a:b], g[a:b], self._m[a:b], self._v[a:b], *args)
+                    self._update(flat, g, a, b, args)
             side = self.model._take_side_after_backward() if hasattr(self.model, '_take_side_after_backward') else None
             # (for the next forward: were the heads' / the gate's weights updated on the weight-gradient side stream?)
             self.model._bucket0_on_side = side is not None
@@ -188,12 +296,12 @@ class FusedAdam(torch.optim.Optimizer):
                         # while this update is still running (lirec_amd.graph, `defer`).  The counter holds the steps this stream
                         # has COMPLETED; the update launch reads it (+ 1) and its last workgroup advances it (round 6: the
                         # one-thread counter launch that used to stand in front of it waited 43 us on average for a CU)
-                        rs = self._minus(0, hi0, skip)
+                        # (stretches with nothing trainable issue no launch; the counter is advanced all the same)
+                        rs = [(a, b) for a, b in self._minus(0, hi0, skip) if self._all_live or self.trainable_ranges(a, b)]
                         if not rs:
                             ops.counter_add(self._step_side_dev, [1])
                         for i, (a, b) in enumerate(rs):
-                            ops.adam_step_counted(flat[a:b], g[a:b], self._m[a:b], self._v[a:b], *args[1:7], self._step_side_dev,
-                                                  self._side_ticket, advance=(i == len(rs) - 1))
+                            self._update(flat, g, a, b, args, counted=(self._step_side_dev, self._side_ticket), last=(i == len(rs) - 1))
                     else:
                         update(0, hi0)
                 update(hi0, flat.numel())
@@ -209,12 +317,15 @@ class FusedAdam(torch.optim.Optimizer):
                 if self._step_dev is not None and self._step_side_dev is not None:
                     ops.counter_add(self._step_side_dev, [1])      # (kept in step with the shared counter whichever path a step takes)
                 update(0, flat.numel())
+        if self._step_dev is None:
+            self._advance_lags()          # (a recorded step's caller advances the host mirrors itself, _step included)
         return loss
 
     def _sync_state_steps(self):
         """``state[p]['step']`` tensors are refreshed when somebody looks (state_dict), not 38 times a step."""
-        for st in self.state.values():
-            st['step'] = torch.tensor(float(self._step))
+        lag = {id(p): self._lag.get(n, 0) for n, p in zip(self._names, self.model._plist)} if self._lag else {}
+        for p, st in self.state.items():
+            st['step'] = torch.tensor(float(self._step - lag.get(id(p), 0)))
 
     def consolidate_state(self):
         """COLLECTIVE (every rank must call it, at the same point): under the sharded data-parallel update a rank's moments are
@@ -248,5 +359,14 @@ class FusedAdam(torch.optim.Optimizer):
         super().load_state_dict(state_dict)
         steps = [float(st['step']) for st in self.state.values() if 'step' in st]
         self._step = int(max(steps)) if steps else 0
+        # (one step per parameter, as torch.optim.Adam keeps it: the ones behind the furthest carry the difference as their lag;
+        #  a parameter without state has received no update)
+        self._lag = {}
+        for n, p in zip(self._names, self.model._plist):
+            st = self.state.get(p)
+            lag = self._step - (int(float(st['step'])) if st and 'step' in st else 0)
+            if lag:
+                self._lag[n] = lag
+        self._ranges_key = None
         self._m = None                      # re-flatten the loaded per-parameter moments
         self._ensure_state()

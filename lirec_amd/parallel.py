@@ -95,6 +95,23 @@ class GradSync:
         out = self._slices.get(lo) if (self.sharded and self._tensor_coll) else None
         return out if (out is not None and out.numel() == b - a) else g[a:b]
 
+    def check_frozen_set(self, flags):
+        """COLLECTIVE, under opt.strict, once per frozen set: the parameters' requires_grad flags must be the same on every rank
+        (each rank updates its own slice of a bucket and the slices are gathered: a parameter frozen on one rank only would be
+        stale on the others' copies or updated behind the freezer's back).  One small all-reduce of a hash."""
+        if flags == getattr(self, '_frozen_checked', None):
+            return
+        self._frozen_checked = flags
+        if self.real_world <= 1 or not dist.is_initialized():
+            return
+        import hashlib
+        h = int(hashlib.sha1(bytes(bytearray(int(bool(f)) for f in flags))).hexdigest()[:12], 16)
+        dev = self.get_flat_grad().device if dist.get_backend(self.group) == 'nccl' else 'cpu'
+        t = torch.tensor([h, -h], dtype=torch.int64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
+        if int(t[0]) != -int(t[1]):
+            raise RuntimeError('data parallelism: the set of frozen parameters (requires_grad) differs between the ranks')
+
     def bucket_ready(self, stage: int, also=None):
         """Called by backward once every kernel writing bucket ``stage`` is enqueued -- on the current stream and,
         optionally, on the stream with raw handle ``also`` (the weight-gradient side stream).  The collective is issued
@@ -239,13 +256,20 @@ class GradSync:
         the averaged one), the same number on every rank -- what a global-norm clip needs.  Under the sharded update a rank holds the
         sums of its own slices only (``wait()`` says why): each rank squares its slices, one small all-reduce adds them up."""
         g = self.get_flat_grad()
+        # (frozen parameters have no gradient: their slices of the buffer hold whatever a shared launch left there and are not
+        #  counted -- `trainable_ranges`, FusedAdam's, set by DataParallel; None: everything)
+        live = getattr(self, 'trainable_ranges', None)
+        cut = (lambda a, b: [(x, y) for x, y, _ in live(a, b)]) if live is not None else (lambda a, b: [(a, b)])
         if not (self.sharded and self.real_world > 1 and dist.is_initialized()):
-            return (g.double() ** 2).sum() * scale ** 2
+            if live is None:
+                return (g.double() ** 2).sum() * scale ** 2
+            return sum(((g[x:y].double() ** 2).sum() for x, y in cut(0, g.numel())),
+                       torch.zeros((), dtype=torch.float64, device=g.device)) * scale ** 2
         tot = torch.zeros((), dtype=torch.float64, device=g.device)
         for lo, hi in self.ranges:
             a, b = self.my_slice(lo, hi)
-            if b > a:
-                tot += (g[a:b].double() ** 2).sum()
+            for x, y in (cut(a, b) if b > a else ()):
+                tot += (g[x:y].double() ** 2).sum()
         dist.all_reduce(tot, group=self.group)
         return tot * scale ** 2
 
@@ -290,6 +314,9 @@ class DataParallel:
         model.grad_sync = GradSync(lambda: model.flat_grads(attach=False), model._offsets, group, force_buckets, sharded,
                                    get_flat_param=model.flat_params)
         optimizer.grad_scale = 1.0 / self.world
+        # (frozen parameters -- requires_grad False -- must be the SAME set on every rank: FusedAdam.step checks it under opt.strict)
+        if hasattr(optimizer, 'trainable_ranges'):
+            model.grad_sync.trainable_ranges = optimizer.trainable_ranges
 
     def global_divisors(self, local, device=None):
         """``local``: this rank's denominators of a loss's batch means (numbers or 0-d tensors: clips, labelled rows, ...).

@@ -140,7 +140,9 @@ def checkpoint_to_flat(ck: dict, model) -> dict:
     (``model._offsets``: heads + gate | interaction embed | context embed, every tensor 16-byte aligned):
     ``{'params', 'exp_avg', 'exp_avg_sq': 1-D fp32 tensors of model._n_flat elements, 'step': int, 'epoch': int,
     'offsets': {name: (offset, numel)}}``.  This is what a host that drives the C ABI without torch modules
-     uploads for ``lirec_adam_step`` and the GEMMs.  Optimizer state is optional."""
+     uploads for ``lirec_adam_step`` and the GEMMs.  Optimizer state is optional.  ``'step'`` is the furthest
+    parameter's; parameters that have received fewer updates (frozen for a while: torch.optim.Adam keeps a step per parameter)
+    are listed in ``'lags'``: {name: step - its own} -- what ``lirec_adam_step_ranges`` takes per range; absent when all agree."""
     sd = ck['state_dict']
     names = [n for n, _ in model.named_parameters()]
     if list(sd.keys()) != names:
@@ -158,16 +160,20 @@ def checkpoint_to_flat(ck: dict, model) -> dict:
     if osd and osd.get('state'):
         # torch numbers optimizer state by position in param_groups[*]['params'] = model.parameters() order
         order = [i for g in osd['param_groups'] for i in g['params']]
-        steps = []
+        steps = {}
         for idx, k in zip(order, names):
             st = osd['state'].get(idx)
             if st is None:
+                steps[k] = 0          # (a parameter stock Adam never updated has no state)
                 continue
             off, cnt = model._offsets[k]
             out['exp_avg'][off:off + cnt] = st['exp_avg'].reshape(-1).float()
             out['exp_avg_sq'][off:off + cnt] = st['exp_avg_sq'].reshape(-1).float()
-            steps.append(int(float(st['step'])))
-        out['step'] = max(steps) if steps else 0
+            steps[k] = int(float(st['step']))
+        out['step'] = max(steps.values()) if steps else 0
+        lags = {k: out['step'] - t for k, t in steps.items() if t != out['step']}
+        if lags:
+            out['lags'] = lags
     return out
 
 
@@ -182,7 +188,7 @@ def flat_to_checkpoint(flat: dict, model, lr=None, weight_decay=None) -> dict:
         off, cnt = flat['offsets'][k] if 'offsets' in flat else model._offsets[k]
         shp = pd[k].shape
         sd[k] = flat['params'][off:off + cnt].clone().view(shp)
-        state[i] = {'step': torch.tensor(float(flat['step'])), 'exp_avg': flat['exp_avg'][off:off + cnt].clone().view(shp),
+        state[i] = {'step': torch.tensor(float(flat['step'] - flat.get('lags', {}).get(k, 0))), 'exp_avg': flat['exp_avg'][off:off + cnt].clone().view(shp),
                     'exp_avg_sq': flat['exp_avg_sq'][off:off + cnt].clone().view(shp)}
     group = {'lr': opt.lr if lr is None else lr, 'betas': (0.9, 0.999), 'eps': 1e-8,
              'weight_decay': opt.weight_decay if weight_decay is None else weight_decay, 'amsgrad': False,
