@@ -594,6 +594,43 @@ typedef struct {
 int lirec_adam_step_ranges(float* p, const float* g, float* m, float* v, const lirec_adam_range* ranges, int32_t count,
                            int32_t step, float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                            const int64_t* step_dev, int64_t* count_dev, int32_t* ticket, int32_t advance, lirec_stream_t stream);
+/* ---- gradient clipping by global norm, on the device ------------------------------
+ * torch.nn.utils.clip_grad_norm_(parameters, max_norm) (norm type 2) for callers that cannot visit the host between backward and
+ * update (a recorded step, a sharded data-parallel update): a reduction leaves the clip coefficient in device memory, and the Adam
+ * launches multiply it into the scale they already apply to every gradient -- no pass that scales the gradients, which therefore
+ * stay UNCLIPPED in their buffer (clip_grad_norm_ scales them in place; the update is the same to one fp32 rounding of the scalar:
+ * g * (grad_scale * coef) here, (g * coef) * grad_scale there).  (Added to ABI 124 without a new number: exports only.)
+ *
+ * lirec_grad_sq_partials: partials[w], w < LIREC_CLIP_PARTIALS (device doubles, all of them written), = the sums of squares that
+ * workgroup w of a FIXED grid finds in the ranges of g (`ranges`: host memory, offset / length as in lirec_adam_step_ranges, `lag`
+ * ignored; ranges may come in any order and are not checked against each other).  Accumulated in double in a fixed order: the
+ * partials -- and their sum -- are a pure function of the values, the ranges and LIREC_CLIP_PARTIALS, bit for bit the same on every
+ * device, stream and launch form (eager, recorded).  LIREC_EINVAL before any device call for: a NULL pointer, n_ranges outside
+ * 1..64, a negative length or offset, an offset that is not a multiple of 4, g not 16-byte or partials not 8-byte aligned.
+ *
+ * lirec_clip_finalize (one workgroup): S = the sum of the partials in a fixed tree;
+ *   mode 0  *sq_dev = S          mode 1  *sq_dev += S (a second table of ranges, further buckets)
+ *   mode 2  partials not read (may be NULL), *sq_dev as it stands (after an all-reduce of it)
+ * then, in double, norm = sqrt(*sq_dev) * grad_scale, x = max_norm / (norm + 1e-6) (torch's formula), and
+ *   out[0] = coef = x < 1 ? x : (x is NaN ? x : 1)      out[1] = norm                      (device floats)
+ * A NaN norm gives a NaN coefficient -- and NaN parameters, as clip_grad_norm_ without error_if_nonfinite does --, an infinite
+ * norm the coefficient 0.  LIREC_EINVAL for: sq_dev / out NULL, partials NULL with mode 0 or 1, a mode outside 0..2, max_norm NaN
+ * or <= 0, partials / sq_dev not 8-byte or out not 4-byte aligned.
+ *
+ * lirec_set_adam_clip(coef_dev): while coef_dev is not NULL, every lirec_adam_step, lirec_adam_step_counted and
+ * lirec_adam_step_ranges launch issued BY THE CALLING HOST THREAD uses grad_scale * *coef_dev (one fp32 product) where it used
+ * grad_scale; the kernel reads the word once per launch -- a uniform load of what an earlier launch on the stream wrote.  The
+ * pointer is taken when the launch is issued: a recorded launch keeps it by value, and every replay reads the coefficient anew.
+ * The setting follows the HOST THREAD (like lirec_set_grad_overwrite and the recorder), not the context: launches the thread issues
+ * on a side stream under a context of its own are clipped too.  NULL (the default): the launches are exactly the unclipped ones,
+ * kernels and arguments.  A folded update (lirec_embed_bwd_args::adam) is REFUSED (LIREC_EINVAL) while a coefficient is set: the
+ * norm needs the finished gradient that launch itself produces.  LIREC_EINVAL for a pointer that is not 4-byte aligned. */
+#define LIREC_CLIP_PARTIALS 1024
+int lirec_grad_sq_partials(const float* g, const lirec_adam_range* ranges, int32_t n_ranges, double* partials,
+                           lirec_stream_t stream);
+int lirec_clip_finalize(const double* partials, double* sq_dev, int32_t mode, float grad_scale, float max_norm, float* out,
+                        lirec_stream_t stream);
+int lirec_set_adam_clip(const float* coef_dev);
 /* `step_dev` (optional, device): when not NULL the 1-based step is read from it by the kernel instead of `step`
  * (bias corrections computed on the device), so that a captured graph advances through the steps.
  * lirec_counter_add: ctr[i] += inc[i] for i < n (n <= 4), one tiny kernel -- the "next step" node of such a graph. */

@@ -105,6 +105,7 @@ class AdamRange(C.Structure):
 
 
 ADAM_MAX_RANGES = 64
+CLIP_PARTIALS = 1024          # LIREC_CLIP_PARTIALS: the doubles lirec_grad_sq_partials writes
 
 
 class LinearFwdArgs(C.Structure):
@@ -199,6 +200,9 @@ _PROTOS = {
     'lirec_adam_step_ranges': (_i32, [_vp, _vp, _vp, _vp, C.POINTER(AdamRange), _i32, _i32, _f32, _f32, _f32, _f32, _f32, _f32,
                                       _vp, _vp, _vp, _i32, _vp]),
     'lirec_counter_add': (_i32, [_vp, C.POINTER(C.c_int64), _i32, _vp]),
+    'lirec_grad_sq_partials': (_i32, [_vp, C.POINTER(AdamRange), _i32, _vp, _vp]),
+    'lirec_clip_finalize': (_i32, [_vp, _vp, _i32, _f32, _f32, _vp, _vp]),
+    'lirec_set_adam_clip': (_i32, [_vp]),
     'lirec_eval_max_tracks': (_i32, [C.POINTER(EvalArgs), _vp]),
     'lirec_cast_f64_f32': (_i32, [_vp, _vp, _i64, _vp]),
     'lirec_grid_pool': (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i64, _vp]),

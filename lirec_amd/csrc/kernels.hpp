@@ -1604,12 +1604,12 @@ __global__ __launch_bounds__(256) void ce_loss_kernel(const float* __restrict__ 
 // ---------------------------------------------------------------------------
 // K7: fused Adam over one flat buffer (torch.optim.Adam single-tensor op order)
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                   float* __restrict__ m, float* __restrict__ v, long n,
-                                                   float step_size, float bc2_sqrt, float beta1, float beta2,
-                                                   float eps, float wd, float gscale, float lr,
-                                                   const long long* __restrict__ step_dev,
-                                                   long long* count_dev = nullptr, int* ticket = nullptr, int advance = 0) {
+__device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __restrict__ g,
+                                          float* __restrict__ m, float* __restrict__ v, long n,
+                                          float step_size, float bc2_sqrt, float beta1, float beta2,
+                                          float eps, float wd, float gscale, float lr,
+                                          const long long* __restrict__ step_dev,
+                                          long long* count_dev, int* ticket, int advance) {
   // count_dev (lirec_adam_step_counted): a counter of COMPLETED steps owned by this launch's stream -- the step is *count_dev + 1,
   // and, `advance`, the workgroup that finishes last stores it back (every workgroup has read the counter by then: a workgroup
   // takes its ticket behind its last element) -- the one-thread counter launch in front of the side stream's update is gone
@@ -1637,6 +1637,25 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     }
   }
 }
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                   float* __restrict__ m, float* __restrict__ v, long n,
+                                                   float step_size, float bc2_sqrt, float beta1, float beta2,
+                                                   float eps, float wd, float gscale, float lr,
+                                                   const long long* __restrict__ step_dev,
+                                                   long long* count_dev = nullptr, int* ticket = nullptr, int advance = 0) {
+  adam_body(p, g, m, v, n, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, lr, step_dev, count_dev, ticket, advance);
+}
+// The same launch with the gradients clipped (lirec_set_adam_clip): the scale is gscale * *coef, `coef` a device float that an
+// earlier launch wrote (clip_finalize_kernel) -- one uniform load, one fp32 multiply; nothing else differs.
+__global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                        float* __restrict__ m, float* __restrict__ v, long n,
+                                                        float step_size, float bc2_sqrt, float beta1, float beta2,
+                                                        float eps, float wd, float gscale, float lr,
+                                                        const long long* __restrict__ step_dev,
+                                                        long long* count_dev, int* ticket, int advance,
+                                                        const float* __restrict__ coef) {
+  adam_body(p, g, m, v, n, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale * *coef, lr, step_dev, count_dev, ticket, advance);
+}
 
 // The same update over a scattered set of ranges of the flat buffers in ONE launch (lirec_adam_step_ranges: the trainable
 // parameters of a partly frozen model).  Range r = [off[r], off[r] + len[r]) with off a multiple of 4, updated with step t - lag[r]:
@@ -1654,11 +1673,11 @@ struct AdamRanges {
   float step_size[ADAM_MAX_RANGES], bc2_sqrt[ADAM_MAX_RANGES];       // by-value step only
   int count;
 };
-__global__ __launch_bounds__(256) void adam_ranges_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                          float* __restrict__ m, float* __restrict__ v, const AdamRanges rt,
-                                                          long nblocks, float beta1, float beta2, float eps, float wd,
-                                                          float gscale, float lr, const long long* __restrict__ step_dev,
-                                                          long long* count_dev, int* ticket, int advance) {
+__device__ __forceinline__ void adam_ranges_body(float* __restrict__ p, const float* __restrict__ g,
+                                                 float* __restrict__ m, float* __restrict__ v, const AdamRanges& rt,
+                                                 long nblocks, float beta1, float beta2, float eps, float wd,
+                                                 float gscale, float lr, const long long* __restrict__ step_dev,
+                                                 long long* count_dev, int* ticket, int advance) {
   long long t_counted = 0;
   if (count_dev) t_counted = __hip_atomic_load(count_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
   const bool dev_step = step_dev || count_dev;
@@ -1705,6 +1724,101 @@ __global__ __launch_bounds__(256) void adam_ranges_kernel(float* __restrict__ p,
         __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
+  }
+}
+__global__ __launch_bounds__(256) void adam_ranges_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                          float* __restrict__ m, float* __restrict__ v, const AdamRanges rt,
+                                                          long nblocks, float beta1, float beta2, float eps, float wd,
+                                                          float gscale, float lr, const long long* __restrict__ step_dev,
+                                                          long long* count_dev, int* ticket, int advance) {
+  adam_ranges_body(p, g, m, v, rt, nblocks, beta1, beta2, eps, wd, gscale, lr, step_dev, count_dev, ticket, advance);
+}
+// ... clipped: as adam_clip_kernel
+__global__ __launch_bounds__(256) void adam_ranges_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                               float* __restrict__ m, float* __restrict__ v, const AdamRanges rt,
+                                                               long nblocks, float beta1, float beta2, float eps, float wd,
+                                                               float gscale, float lr, const long long* __restrict__ step_dev,
+                                                               long long* count_dev, int* ticket, int advance,
+                                                               const float* __restrict__ coef) {
+  adam_ranges_body(p, g, m, v, rt, nblocks, beta1, beta2, eps, wd, gscale * *coef, lr, step_dev, count_dev, ticket, advance);
+}
+
+// ---------------------------------------------------------------------------
+// Global-norm gradient clipping (lirec_grad_sq_partials, lirec_clip_finalize): the clip coefficient is produced in device memory
+// and folds into the scale the Adam kernels multiply every gradient by -- no scaling pass over the gradients, no host visit.
+//
+// grad_sq_partials_kernel: the sum of squares of the flat fp32 gradient buffer over a table of ranges (the offset / length part of
+// adam_ranges_kernel's table: offsets multiples of 4).  The grid is ALWAYS CLIP_PARTIALS workgroups -- a constant, never derived
+// from the device -- and the work is dealt as in adam_ranges_kernel: blocks of ADAM_RANGE_BLOCK elements numbered across the
+// ranges, workgroup w taking blocks w, w + CLIP_PARTIALS, ...  Every thread squares and accumulates in double (the square of an
+// fp32 value is exact there, so whether the compiler contracts the multiply-add changes nothing), then a fixed tree: the wave's
+// shuffles, the four waves through LDS.  Workgroup w stores ONE double to partials[w] (0 without work): the result is a pure
+// function of (values, ranges, CLIP_PARTIALS) -- the same bits on every device and in every launch form.
+#define CLIP_PARTIALS 1024
+struct SqRanges {
+  long off[ADAM_MAX_RANGES], len[ADAM_MAX_RANGES];
+  int count;
+};
+__device__ __forceinline__ double clip_block_sum(double acc, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);          // (meaningful in thread 0; every thread may read it)
+}
+__global__ __launch_bounds__(256) void grad_sq_partials_kernel(const float* __restrict__ g, const SqRanges rt, long nblocks,
+                                                               double* __restrict__ partials) {
+  __shared__ double red[4];
+  double acc = 0.0;
+  for (long wb = blockIdx.x; wb < nblocks; wb += CLIP_PARTIALS) {
+    long b = wb;
+    int r = 0;
+    for (; r < rt.count - 1; ++r) {
+      const long nb = (rt.len[r] + ADAM_RANGE_BLOCK - 1) / ADAM_RANGE_BLOCK;
+      if (b < nb) break;
+      b -= nb;
+    }
+    const long first = b * ADAM_RANGE_BLOCK;                  // within the range
+    long left = rt.len[r] - first;
+    if (left > ADAM_RANGE_BLOCK) left = ADAM_RANGE_BLOCK;
+    const long e = 4L * threadIdx.x;
+    const long at = rt.off[r] + first + e;
+    if (e + 4 <= left) {
+      const f32x4 x = *reinterpret_cast<const f32x4*>(g + at);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc += (double)x[j] * (double)x[j];
+    } else {
+      for (long j = 0; e + j < left; ++j) acc += (double)g[at + j] * (double)g[at + j];
+    }
+  }
+  const double s = clip_block_sum(acc, red);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// clip_finalize_kernel, ONE workgroup of 256 threads: thread t sums partials[4t .. 4t + 3] in index order, then the same fixed
+// tree.  mode 0: *sq = sum; 1: *sq += sum (a second table of ranges, later buckets); 2: no partials, *sq as it stands (after an
+// all-reduce).  norm = sqrt(*sq) * grad_scale; x = max_norm / (norm + 1e-6) -- torch.nn.utils.clip_grad_norm_'s formula --
+// out[0] = x < 1 ? x : (x is NaN ? x : 1), out[1] = norm, both fp32.  A NaN norm gives a NaN coefficient (and NaN parameters: what
+// clip_grad_norm_ without error_if_nonfinite does), an infinite one the coefficient 0.
+__global__ __launch_bounds__(256) void clip_finalize_kernel(const double* __restrict__ partials, double* __restrict__ sq, int mode,
+                                                            float grad_scale, float max_norm, float* __restrict__ out) {
+  __shared__ double red[4];
+  static_assert(CLIP_PARTIALS % 256 == 0, "every thread sums the same number of partials");
+  double acc = 0.0;
+  if (mode != 2) {
+    const double* q = partials + (long)threadIdx.x * (CLIP_PARTIALS / 256);
+#pragma unroll
+    for (int j = 0; j < CLIP_PARTIALS / 256; ++j) acc += q[j];
+  }
+  const double s = clip_block_sum(acc, red);
+  if (threadIdx.x == 0) {
+    double total = mode == 0 ? s : (mode == 1 ? *sq + s : *sq);
+    if (mode != 2) *sq = total;
+    const double norm = sqrt(total) * (double)grad_scale;
+    const double x = (double)max_norm / (norm + 1e-6);
+    const double coef = x < 1.0 ? x : (x != x ? x : 1.0);
+    out[0] = (float)coef;
+    out[1] = (float)norm;
   }
 }
 

@@ -139,6 +139,10 @@ static inline unsigned row_magic(int gs, long max_rows) {
 static thread_local int g_grad_overwrite = 0;       // (per host thread, like the recorder and the contexts: a backward on another
                                                     //  thread -- an evaluation loop's, another model's -- never picks it up)
 static inline float grad_beta() { return g_grad_overwrite ? 0.f : 1.f; }
+// The clip coefficient of this host thread's Adam launches (lirec_set_adam_clip): a device float the launches read, NULL = off.
+// Per host thread, like g_grad_overwrite and the recorder -- NOT per context: the side streams' launches of a step are issued by
+// the thread that set it, under contexts of their own.
+static thread_local const float* t_adam_clip = nullptr;
 // While the mode is on, every weight / bias gradient target that is handed to a launch is noted: a parameter written by TWO
 // launches of one step (a tied module, a gradient cut over several launches) would silently lose the first contribution -- the
 // caller that switches the mode on asks for the count of such targets afterwards (lirec_grad_overwrite_conflicts) and keeps
@@ -662,6 +666,9 @@ static int gather_planes(const Args* const* hs, int nh) {
 // call inside the flat buffer, and together exactly the parameters the caller counts on; sets each problem's aux_out to where
 // the q32b form of its new weights goes (or NULL)
 static int fused_adam_fill(const lirec_fused_adam* adam, GemmGroup& g, AdamFuse& af) {
+  // (a clip coefficient needs the norm of the FINISHED gradient, which this very launch produces: the folded update cannot be
+  //  clipped, and an unclipped one beside clipped launches would be a silent error)
+  if (t_adam_clip) return LIREC_EINVAL;
   if (!adam->p || !adam->g || !adam->m || !adam->v || adam->n < 1 || (adam->step < 1 && !adam->step_dev)) return LIREC_EINVAL;
   if (((reinterpret_cast<uintptr_t>(adam->p) | reinterpret_cast<uintptr_t>(adam->g) | reinterpret_cast<uintptr_t>(adam->m) |
         reinterpret_cast<uintptr_t>(adam->v)) & 15) != 0 || (reinterpret_cast<uintptr_t>(adam->wq) & 255) != 0) return LIREC_EINVAL;
@@ -2367,7 +2374,12 @@ int lirec_adam_step(float* p, const float* g, float* m, float* v, int64_t n, int
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
   const int pi = prof_start(PS_ADAM, (hipStream_t)stream);
-  lirec::launch(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n,
+  if (t_adam_clip)
+    lirec::launch(adam_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n,
+                  step_size, bc2_sqrt, beta1, beta2, eps, weight_decay, grad_scale, lr, (const long long*)step_dev,
+                  (long long*)nullptr, (int*)nullptr, 0, t_adam_clip);
+  else
+    lirec::launch(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n,
                      step_size, bc2_sqrt, beta1, beta2, eps, weight_decay, grad_scale, lr, (const long long*)step_dev,
                      (long long*)nullptr, (int*)nullptr, 0);
   prof_stop(pi, (hipStream_t)stream, 0.0, 28.0 * (double)n);     // read p,g,m,v; write p,m,v
@@ -2384,7 +2396,12 @@ int lirec_adam_step_counted(float* p, const float* g, float* m, float* v, int64_
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
   const int pi = prof_start(PS_ADAM, (hipStream_t)stream);
-  lirec::launch(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n,
+  if (t_adam_clip)
+    lirec::launch(adam_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n,
+                  0.f, 0.f, beta1, beta2, eps, weight_decay, grad_scale, lr, (const long long*)nullptr,
+                  (long long*)count_dev, (int*)ticket, (int)(advance != 0), t_adam_clip);
+  else
+    lirec::launch(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n,
                      0.f, 0.f, beta1, beta2, eps, weight_decay, grad_scale, lr, (const long long*)nullptr,
                      (long long*)count_dev, (int*)ticket, (int)(advance != 0));
   prof_stop(pi, (hipStream_t)stream, 0.0, 28.0 * (double)n);
@@ -2422,10 +2439,55 @@ int lirec_adam_step_ranges(float* p, const float* g, float* m, float* v, const l
   if (nblocks == 0) return LIREC_OK;
   const long blocks = nblocks > 2048 ? 2048 : nblocks;
   const int pi = prof_start(PS_ADAM, (hipStream_t)stream);
-  lirec::launch(adam_ranges_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, rt, nblocks,
+  if (t_adam_clip)
+    lirec::launch(adam_ranges_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, rt, nblocks,
+                  beta1, beta2, eps, weight_decay, grad_scale, lr, (const long long*)step_dev, (long long*)count_dev,
+                  (int*)ticket, (int)(advance != 0), t_adam_clip);
+  else
+    lirec::launch(adam_ranges_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, rt, nblocks,
                 beta1, beta2, eps, weight_decay, grad_scale, lr, (const long long*)step_dev, (long long*)count_dev,
                 (int*)ticket, (int)(advance != 0));
   prof_stop(pi, (hipStream_t)stream, 0.0, 28.0 * (double)total);
+  LIREC_CHECK_LAUNCH();
+  return LIREC_OK;
+}
+
+int lirec_set_adam_clip(const float* coef_dev) {
+  if (reinterpret_cast<uintptr_t>(coef_dev) & 3) return LIREC_EINVAL;
+  t_adam_clip = coef_dev;
+  return LIREC_OK;
+}
+
+int lirec_grad_sq_partials(const float* g, const lirec_adam_range* ranges, int32_t n_ranges, double* partials,
+                           lirec_stream_t stream) {
+  if (!g || !ranges || !partials || n_ranges < 1 || n_ranges > LIREC_ADAM_MAX_RANGES) return LIREC_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(g) & 15) != 0 || (reinterpret_cast<uintptr_t>(partials) & 7) != 0) return LIREC_EINVAL;
+  static_assert(LIREC_CLIP_PARTIALS == CLIP_PARTIALS, "the header's number of partials is the kernel's");
+  SqRanges rt;
+  memset(&rt, 0, sizeof(rt));
+  long nblocks = 0;
+  for (int r = 0; r < n_ranges; ++r) {
+    const lirec_adam_range& q = ranges[r];
+    if (q.length < 0 || q.offset < 0 || (q.offset & 3) != 0) return LIREC_EINVAL;
+    rt.off[r] = (long)q.offset; rt.len[r] = (long)q.length;
+    nblocks += (long)((q.length + ADAM_RANGE_BLOCK - 1) / ADAM_RANGE_BLOCK);
+  }
+  rt.count = n_ranges;
+  // (always launched, also with nothing to sum: every one of the partials is written)
+  // (no profiling bracket: the norm pass is not part of the "adam" site, whose bytes are the update's)
+  lirec::launch(grad_sq_partials_kernel, dim3(CLIP_PARTIALS), dim3(256), 0, (hipStream_t)stream, g, rt, nblocks, partials);
+  LIREC_CHECK_LAUNCH();
+  return LIREC_OK;
+}
+
+int lirec_clip_finalize(const double* partials, double* sq_dev, int32_t mode, float grad_scale, float max_norm, float* out,
+                        lirec_stream_t stream) {
+  if (!sq_dev || !out || mode < 0 || mode > 2 || (mode != 2 && !partials)) return LIREC_EINVAL;
+  if (!(max_norm > 0.f)) return LIREC_EINVAL;                    // (NaN included)
+  if (((reinterpret_cast<uintptr_t>(partials) | reinterpret_cast<uintptr_t>(sq_dev)) & 7) != 0 ||
+      (reinterpret_cast<uintptr_t>(out) & 3) != 0) return LIREC_EINVAL;
+  lirec::launch(clip_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, sq_dev, (int)mode, grad_scale, max_norm,
+                out);
   LIREC_CHECK_LAUNCH();
   return LIREC_OK;
 }

@@ -219,6 +219,12 @@ class RecordedTrainStep:
         # (``overwrite``: the caller has run the check itself -- checked_overwrite_step on an earlier batch of this layout -- and
         #  passes its verdict: lirec_amd.train records with no warm-up step of its own)
         self.overwrite = bool(overwrite) if (overwrite is not None and getattr(model, 'grad_sync', None) is None) else False
+        # Gradient clipping (FusedAdam.max_grad_norm): the norm needs every gradient of the step finished, so the clipped update is
+        # issued whole on this stream behind backward -- no fused first-layer update, no un-joined side stream (`defer`)
+        clipping = bool(getattr(optimizer, 'max_grad_norm', None))
+        if clipping and self.sync is not None and self.sync.world > 1:
+            raise LirecError('RecordedTrainStep: gradient clipping under data parallelism is not recorded (the all-reduce of the squared '
+                             'norm sits between the recorded launches) -- run the eager step')
         self.mid, self.parity, self.pre = None, 0, [None, None]
         # (warmup = 0: the caller has already run eager steps of this model -- lirec_amd.train records in the middle of an epoch,
         #  every batch being stepped on exactly once -- so the recording step is the only step taken here; the gradient-overwrite
@@ -234,7 +240,7 @@ class RecordedTrainStep:
         from .config import opt as _opt
         self.fused = bool(self.sync is None and getattr(_opt, 'fuse_dw1_adam', True) and getattr(model, 'last_layer1_planes', False)
                           and getattr(model, '_has_ints', False) and getattr(model, '_has_ctx', False)
-                          and hasattr(optimizer, 'arm_first_layer_update') and hasattr(model, 'refresh_w1q'))
+                          and hasattr(optimizer, 'arm_first_layer_update') and hasattr(model, 'refresh_w1q') and not clipping)
         if self.fused and hasattr(optimizer, 'trainable_ranges') and not optimizer.all_trainable():
             # (first layers PARTLY trainable, or behind: the optimiser does not arm the fused update -- the ordinary update writes no
             #  shadow, the forward stages the weights itself.  Frozen altogether: nothing writes them, the shadow stays current.)
@@ -255,7 +261,7 @@ class RecordedTrainStep:
         # weight gradients, their Adam launch and the next step's staging of the gate's weights overlap the next step's head.  Needs the
         # overwrite mode (no zeroing pass over gradients the deferred update still reads) and one GPU.
         from .config import opt as _o
-        self.defer = bool(self.overwrite and self.sync is None and getattr(_o, 'defer_side_join', True))
+        self.defer = bool(self.overwrite and self.sync is None and getattr(_o, 'defer_side_join', True) and not clipping)
         model._defer_side_join = self.defer
         if self.sync is not None:
             model.grad_sync = _MarkingSync(self.sync, self.marks)
@@ -375,7 +381,11 @@ class RecordedTrainStep:
         g = optimizer.param_groups[0]
         key = (float(g['lr']), tuple(float(b) for b in g['betas']), float(g['eps']), float(g['weight_decay']), float(getattr(optimizer, 'grad_scale', 1.0)))
         frozen = optimizer.frozen_key() if hasattr(optimizer, 'frozen_key') else ()
-        return key + (frozen,) if frozen else key
+        key = key + (frozen,) if frozen else key
+        # (gradient clipping: whether the norm launches and the clipped Adam kernels were recorded, and the bound the recorded
+        #  lirec_clip_finalize carries by value -- the coefficient itself is computed anew by every replay.  Off: today's key.)
+        clip = getattr(optimizer, 'max_grad_norm', None)
+        return key + (('max_grad_norm', float(clip)),) if clip else key
 
     def _check_core(self):
         if ops.get_gemm_mode() != self._gemm_mode:

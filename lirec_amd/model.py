@@ -1629,7 +1629,7 @@ def create_model(n_classes, n_rels=0, verbose=False):
     else:
         loss = MultiTaskMaxMargin(n_rels=n_rels) if opt.rels_multitask else MaxMarginCrossEntropyLoss()
 
-    optimizer = FusedAdam(model, lr=opt.lr, weight_decay=opt.weight_decay)
+    optimizer = FusedAdam(model, lr=opt.lr, weight_decay=opt.weight_decay, max_grad_norm=getattr(opt, 'clip_grad_norm', 0.0) or None)
     if verbose:
         print(str(model))
         for name, param in model.named_parameters():

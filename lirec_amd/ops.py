@@ -740,6 +740,46 @@ def adam_step_ranges(p, g, m, v, ranges, step, lr, beta1, beta2, eps, weight_dec
           'lirec_adam_step_ranges')
 
 
+def grad_sq_partials(g, ranges, partials):
+    """lirec_grad_sq_partials: ``partials`` (device float64[CLIP_PARTIALS]) = the fixed grid's sums of squares of ``g`` over
+    ``ranges`` = [(offset, length), ...] (1..64, offsets multiples of 4; a third entry -- a lag -- is ignored)"""
+    from ._lib import AdamRange, CLIP_PARTIALS
+    assert partials.dtype == torch.float64 and partials.numel() >= CLIP_PARTIALS and partials.is_contiguous()
+    assert all(0 <= r[0] and 0 <= r[1] and r[0] + r[1] <= g.numel() for r in ranges), 'a range outside the buffer'
+    arr = (AdamRange * max(len(ranges), 1))()
+    for a, r in zip(arr, ranges):
+        a.offset, a.length = int(r[0]), int(r[1])
+    check(lib().lirec_grad_sq_partials(_p(_f32c(g)), arr, len(ranges), _p(partials), _stream()), 'lirec_grad_sq_partials')
+
+
+def clip_finalize(partials, sq, mode, grad_scale, max_norm, out):
+    """lirec_clip_finalize: ``sq`` (device float64[1]) = / += the sum of ``partials`` (mode 0 / 1; 2: as it stands), then
+    ``out`` (device float32[2]) = (clip coefficient, norm = sqrt(sq) * grad_scale)"""
+    assert sq.dtype == torch.float64 and out.dtype == torch.float32 and out.numel() >= 2 and out.is_contiguous()
+    assert partials is None or partials.dtype == torch.float64
+    check(lib().lirec_clip_finalize(_p(partials), _p(sq), int(mode), float(grad_scale), float(max_norm), _p(out), _stream()),
+          'lirec_clip_finalize')
+
+
+class adam_clip:
+    """``with ops.adam_clip(coef):`` -- the Adam launches this host thread issues inside multiply their gradients by the device
+    float ``coef`` (lirec_set_adam_clip); cleared on the way out, also when a launch raises.  ``None``: nothing is set."""
+
+    def __init__(self, coef):
+        self.coef = coef
+
+    def __enter__(self):
+        if self.coef is not None:
+            assert self.coef.dtype == torch.float32
+            check(lib().lirec_set_adam_clip(_p(self.coef)), 'lirec_set_adam_clip')
+        return self
+
+    def __exit__(self, *exc):
+        if self.coef is not None:
+            check(lib().lirec_set_adam_clip(None), 'lirec_set_adam_clip')
+        return False
+
+
 def counter_add(ctr, incs):
     """ctr[i] += incs[i] on the device (ctr: int64 device tensor, len(incs) <= 4)."""
     assert ctr.dtype == torch.int64 and ctr.is_cuda and 1 <= len(incs) <= 4 and ctr.numel() >= len(incs)

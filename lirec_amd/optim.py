@@ -16,6 +16,15 @@ exactly the parameters that require grad when it is called; a frozen one keeps i
 that is not simply one zero-lag range is one ``lirec_adam_step_ranges`` launch.  One difference from torch 1.1 (the
 reference's pin), none from current torch: there ``zero_grad()`` zeroes a gradient instead of dropping it, so a parameter frozen
 AFTER it has trained keeps being updated on a zero gradient (weight decay and its old momentum); here it stops.
+
+Gradient clipping by global norm (``max_grad_norm``; ``torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm)`` in front
+of the step, norm type 2) happens on the device, inside the update: a reduction over the trainable ranges of the flat gradient
+buffer (``lirec_grad_sq_partials`` / ``lirec_clip_finalize``) leaves the coefficient min(1, max_norm / (norm + 1e-6)) in device
+memory and the Adam launches multiply it into the scale they apply to every gradient anyway (``lirec_set_adam_clip``) -- no pass
+over the gradients, no host visit, so the recorded step and the sharded data-parallel update can clip too.  ONE DIFFERENCE FROM
+TORCH: the gradients in the flat buffer -- every ``p.grad`` -- stay UNCLIPPED after the step (``clip_grad_norm_`` scales them in
+place); whoever wants the clipped values multiplies by ``optimizer.clip_coef``.  The update itself is the same to one fp32 rounding
+of the scalar: g (grad_scale coef) here, (g coef) grad_scale there.
 """
 from __future__ import annotations
 
@@ -28,7 +37,7 @@ from .config import opt
 
 
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, model, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5):
+    def __init__(self, model, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5, max_grad_norm=None):
         self.model = model
         params = list(model.parameters())
         self._names = [n for n, _ in model.named_parameters()]        # (in the order of model._plist)
@@ -42,6 +51,8 @@ class FusedAdam(torch.optim.Optimizer):
         self._step_side_dev = None     # device int64[1]: the same as the weight-gradient side stream counts it (step(): side update)
         self._lag = {}                 # parameter name -> updates it sat out frozen (missing = 0): state[p]['step'] = _step - lag
         self._ranges_key = self._ranges = None
+        self.max_grad_norm = max_grad_norm      # None / 0: no clipping; settable between steps (a recorded step is recorded again)
+        self._clip_out = None          # device float32[2]: (clip coefficient, gradient norm) of the last clipped step
 
     # -- flat state -----------------------------------------------------------
     def _ensure_state(self):
@@ -51,6 +62,7 @@ class FusedAdam(torch.optim.Optimizer):
             self._m = torch.zeros_like(flat)
             self._v = torch.zeros_like(flat)
             self._side_ticket = torch.zeros(1, dtype=torch.int32, device=flat.device)      # (lirec_adam_step_counted's arrival counter)
+            self._clip_out = None
             pd = dict(self.model.named_parameters())
             for n, (off, k) in self.model._offsets.items():
                 p = pd[n]
@@ -91,6 +103,47 @@ class FusedAdam(torch.optim.Optimizer):
             for p in self.model.parameters():
                 p.grad = None
 
+    # -- gradient clipping ------------------------------------------------------
+    def _clip_max(self):
+        """the bound of the global-norm clip as the kernels get it, or None when clipping is off (``max_grad_norm`` None or 0)"""
+        c = self.max_grad_norm
+        if c is None or c == 0:
+            return None
+        c = float(c)
+        if not c > 0.0:
+            raise ValueError('FusedAdam.max_grad_norm must be positive (or None / 0 for no clipping), not %r' % (self.max_grad_norm,))
+        return c
+
+    def _clip_buffers(self):
+        if self._clip_out is None or self._clip_out.device != self.model.flat_params().device:
+            from ._lib import CLIP_PARTIALS
+            dev = self.model.flat_params().device
+            self._clip_out = torch.tensor([1.0, 0.0], dtype=torch.float32, device=dev)
+            self._clip_sq = torch.zeros(1, dtype=torch.float64, device=dev)
+            self._clip_partials = torch.zeros(CLIP_PARTIALS, dtype=torch.float64, device=dev)
+        return self._clip_out
+
+    @property
+    def clip_coef(self):
+        """0-d device tensor (a view: no synchronisation): the coefficient the last step multiplied its gradients by --
+        min(1, max_grad_norm / (grad_norm + 1e-6)); 1 before the first clipped step"""
+        return self._clip_buffers()[0]
+
+    @property
+    def grad_norm(self):
+        """0-d device tensor (a view: no synchronisation): the L2 norm of the last clipped step's gradient over the trainable
+        parameters AS THE UPDATE SAW IT (times ``grad_scale``), before clipping -- what ``clip_grad_norm_`` returns"""
+        return self._clip_buffers()[1]
+
+    def _clip_accumulate(self, gbuf, ranges, first):
+        """sum of squares of ``gbuf`` over ``ranges`` = [(offset, length)] into the device double (the first table of a step sets
+        it, the others add) and the coefficient of the sum so far; returns ``first`` for the next call"""
+        for ch in self._chunks([r for r in ranges if r[1] > 0]):
+            ops.grad_sq_partials(gbuf, ch, self._clip_partials)
+            ops.clip_finalize(self._clip_partials, self._clip_sq, 0 if first else 1, self.grad_scale, self._clip_now, self._clip_out)
+            first = False
+        return first
+
     def arm_first_layer_update(self):
         """For a caller that issues backward and step as a unit (lirec_amd.graph.RecordedTrainStep; single GPU): the NEXT backward
         folds the update of the first layers of both embeddings (the last gradient bucket, 10 M parameters at the bench shape)
@@ -102,6 +155,8 @@ class FusedAdam(torch.optim.Optimizer):
         m = self.model
         if getattr(m, 'grad_sync', None) is not None or not hasattr(m, 'first_layer_range'):
             return False
+        if self._clip_max() is not None:
+            return False          # (the norm needs the finished first-layer gradients: they are updated with the rest, clipped)
         if not self.all_trainable():
             # (the fused launch updates EVERY first-layer parameter of the call with the one global step: only when each of them
             #  is trainable and has received every update so far)
@@ -231,10 +286,19 @@ class FusedAdam(torch.optim.Optimizer):
                 self.grad_scale, self._step_dev)
         flat = self.model.flat_params()
         sync = self.model.grad_sync
+        self._clip_now = self._clip_max()
+        clip = self._clip_now is not None
+        if clip:
+            self._clip_buffers()
         if sync is not None and sync.world > 1:
             if getattr(opt, 'strict', False) and hasattr(sync, 'check_frozen_set'):
                 sync.check_frozen_set(self._flags())
             self.model._bucket0_on_side = False
+            if clip:
+                self._step_parallel_clipped(sync, flat, g, args)
+                if self._step_dev is None:
+                    self._advance_lags()
+                return loss
             # data parallel: each bucket is updated as its reduction lands, the later buckets still in flight.  Sharded
             # (the default, lirec_amd.parallel): this rank holds the summed gradients of ITS slice of the bucket only, updates
             # that slice (parameters and moments), and the slices are all-gathered back into everybody's parameter buffer
@@ -275,6 +339,11 @@ class FusedAdam(torch.optim.Optimizer):
                 for a, b in self._minus(lo, hi, skip):
                     self._update(flat, g, a, b, args)
             side = self.model._take_side_after_backward() if hasattr(self.model, '_take_side_after_backward') else None
+            if clip:
+                # Clipped: the coefficient needs EVERY gradient finished, so nothing is updated beside the tail of backward -- the side
+                # streams are joined (below: the no-side branch), the norm is taken over the trainable ranges (frozen slices of the
+                # buffer hold whatever a shared launch left there) and the whole update follows on this stream, clipped
+                side = None
             # (for the next forward: were the heads' / the gate's weights updated on the weight-gradient side stream?)
             self.model._bucket0_on_side = side is not None
             if side is not None:
@@ -316,10 +385,66 @@ class FusedAdam(torch.optim.Optimizer):
                     self.model.join_side_streams()
                 if self._step_dev is not None and self._step_side_dev is not None:
                     ops.counter_add(self._step_side_dev, [1])      # (kept in step with the shared counter whichever path a step takes)
-                update(0, flat.numel())
+                if clip:
+                    if skip:
+                        # (max_grad_norm was set between arm_first_layer_update() and this step: the backward has already applied
+                        #  the first layers' update, unclipped -- nothing here can take it back)
+                        raise RuntimeError('FusedAdam.step(): max_grad_norm was set after the backward of this step had folded the '
+                                           'first-layer update in (arm_first_layer_update); set it before the step begins')
+                    rs = [(0, flat.numel())] if self._all_live else [(a, b - a) for a, b, _ in self.trainable_ranges()]
+                    if self._clip_accumulate(g, rs, True):
+                        self._clip_nothing()              # (nothing trainable: no update; norm 0, coefficient 1)
+                    else:
+                        with ops.adam_clip(self._clip_out[0:1]):
+                            update(0, flat.numel())
+                else:
+                    update(0, flat.numel())
         if self._step_dev is None:
             self._advance_lags()          # (a recorded step's caller advances the host mirrors itself, _step included)
         return loss
+
+    def _clip_nothing(self):
+        """a clipped step with nothing to clip: (coefficient, norm) = (1, 0), written by the finalize from a zeroed sum -- two
+        tiny library launches that a command list records like the rest (the values of an earlier step must not stay)"""
+        ops.zero_(self._clip_sq)
+        ops.clip_finalize(None, self._clip_sq, 2, self.grad_scale, self._clip_now, self._clip_out)
+
+    def _step_parallel_clipped(self, sync, flat, g, args):
+        """The data-parallel update with gradient clipping: EVERY bucket's reduction lands first (no update beside the tail of
+        backward, none while later buckets are on the wire -- the coefficient needs them all); each rank squares ITS slices of the
+        trainable ranges -- under the sharded update nobody holds the whole reduced gradient -- one all-reduce of the single double
+        adds them up (the same bits on every rank), and the slices are updated and gathered as ever, clipped.  ``grad_scale`` =
+        1 / world enters the norm: every rank gets the coefficient of the AVERAGED gradient."""
+        import torch.distributed as dist
+        cur = ops.current_stream_handle()
+        buckets = []
+        for lo, hi, early in sync.wait_each():
+            if early is not None:            # (the reduction was waited for on the collectives' launch stream)
+                ops.stream_wait(cur, C.c_void_p(early.cuda_stream))
+            buckets.append((lo, hi))
+        assert sum(hi - lo for lo, hi in buckets) == flat.numel(), 'gradient buckets do not cover the parameter buffer'
+        first = True
+        for lo, hi in buckets:
+            a, b = sync.my_slice(lo, hi)
+            if b > a:
+                rs = [(a, b, 0)] if self._all_live else self.trainable_ranges(a, b)
+                first = self._clip_accumulate(sync.grad_slice(g, lo, hi), [(x - a, y - x) for x, y, _ in rs], first)
+        everywhere = not (sync.sharded and sync.real_world > 1 and dist.is_initialized())
+        if first:
+            if everywhere:                   # (nothing trainable at all)
+                self._clip_nothing()
+                return
+            ops.zero_(self._clip_sq)         # (nothing trainable in this rank's slices)
+        if not everywhere:
+            dist.all_reduce(self._clip_sq, op=dist.ReduceOp.SUM, group=sync.group)
+            ops.clip_finalize(None, self._clip_sq, 2, self.grad_scale, self._clip_now, self._clip_out)
+        with ops.adam_clip(self._clip_out[0:1]):
+            for lo, hi in buckets:
+                a, b = sync.my_slice(lo, hi)
+                if b > a:
+                    self._update(flat, sync.grad_slice(g, lo, hi), a, b, args, g_is_slice=True)
+                sync.gather_params(lo, hi)
+        sync.finish_gathers()
 
     def _sync_state_steps(self):
         """``state[p]['step']`` tensors are refreshed when somebody looks (state_dict), not 38 times a step."""
