@@ -631,6 +631,46 @@ int lirec_grad_sq_partials(const float* g, const lirec_adam_range* ranges, int32
 int lirec_clip_finalize(const double* partials, double* sq_dev, int32_t mode, float grad_scale, float max_norm, float* out,
                         lirec_stream_t stream);
 int lirec_set_adam_clip(const float* coef_dev);
+/* ---- parameter groups: hyper-parameters in device memory ---------------------------
+ * torch.optim.Adam's param_groups, and hyper-parameters that change between the replays of a recorded step (a learning-rate
+ * schedule): lr, betas, eps and weight_decay live in a small TABLE in device memory, one 32-byte row per group, that the Adam
+ * launches read instead of taking the five values as arguments.  A recorded launch then holds the table's address, and a changed
+ * value is one tiny launch in front of the replay.  (Added to ABI 124 without a new number: exports only.)
+ *
+ * A table: n_groups <= LIREC_ADAM_MAX_GROUPS rows of lirec_adam_hyper in device memory, 16-byte aligned.
+ *
+ * lirec_adam_hyper_write: one tiny launch that stores `rows_host` (HOST memory, n_groups rows, copied into the launch by value;
+ * the padding is written as zeros) into the table -- an ordinary kernel on `stream`: stream order is all that protects the
+ * launches that read the table, so a table belongs to ONE stream and is written on the stream that reads it.  LIREC_EINVAL before
+ * any device call for: a NULL or not 16-byte aligned table, rows_host NULL, n_groups outside 1..8.  The VALUES are not checked.
+ *
+ * lirec_adam_step_groups: lirec_adam_step_ranges with a group per range: lr, beta1, beta2, eps and weight_decay of range r are
+ * those of row ranges[r].group of the table as the launch finds it.  Ranges, lags, step / step_dev / count_dev + ticket + advance
+ * and the clip coefficient of lirec_set_adam_clip exactly as there.  The bias corrections are ALWAYS computed by the kernel, in
+ * double, from the row's values: a by-value `step` t behaves as step_dev holding t, and the bits on a range are those of
+ * lirec_adam_step with step_dev on that range with the row's values.  count == 0, or all lengths 0: no launch (and no advance).
+ * LIREC_EINVAL before any device call for: everything lirec_adam_step_ranges refuses, a group outside 0..n_groups-1, n_groups
+ * outside 1..8, a NULL or not 16-byte aligned table.
+ *
+ * lirec_set_adam_hyper_row(row_dev): while row_dev is not NULL, a folded update (lirec_embed_bwd_args::adam) issued BY THE CALLING
+ * HOST THREAD reads its five values from that device row -- the by-value ones in lirec_fused_adam are ignored -- and computes its
+ * bias corrections itself (the bits of lirec_adam_step with step_dev and the row's values).  The pointer is taken when the launch
+ * is issued: a recorded launch keeps it, every replay reads the values anew.  NULL (the default): exactly the kernel and the
+ * arguments as without this call.  LIREC_EINVAL for a pointer that is not 16-byte aligned. */
+#define LIREC_ADAM_MAX_GROUPS 8
+typedef struct {
+  float lr, beta1, beta2, eps, weight_decay;
+  float reserved_[3];
+} lirec_adam_hyper;
+typedef struct {
+  int64_t offset, length;                /* elements */
+  int32_t lag, group;
+} lirec_adam_group_range;
+int lirec_adam_hyper_write(lirec_adam_hyper* table_dev, const lirec_adam_hyper* rows_host, int32_t n_groups, lirec_stream_t stream);
+int lirec_adam_step_groups(float* p, const float* g, float* m, float* v, const lirec_adam_group_range* ranges, int32_t count,
+                           const lirec_adam_hyper* table_dev, int32_t n_groups, int32_t step, float grad_scale,
+                           const int64_t* step_dev, int64_t* count_dev, int32_t* ticket, int32_t advance, lirec_stream_t stream);
+int lirec_set_adam_hyper_row(const lirec_adam_hyper* row_dev);
 /* `step_dev` (optional, device): when not NULL the 1-based step is read from it by the kernel instead of `step`
  * (bias corrections computed on the device), so that a captured graph advances through the steps.
  * lirec_counter_add: ctr[i] += inc[i] for i < n (n <= 4), one tiny kernel -- the "next step" node of such a graph. */

@@ -104,6 +104,17 @@ class AdamRange(C.Structure):
     _fields_ = [('offset', _i64), ('length', _i64), ('lag', _i32), ('reserved_', _i32)]
 
 
+class AdamHyper(C.Structure):
+    """lirec_adam_hyper: one row of a table of per-group hyper-parameters in device memory (32 bytes)"""
+    _fields_ = [('lr', _f32), ('beta1', _f32), ('beta2', _f32), ('eps', _f32), ('weight_decay', _f32), ('reserved_', _f32 * 3)]
+
+
+class AdamGroupRange(C.Structure):
+    """lirec_adam_group_range: lirec_adam_range with the group whose row of the table the range is updated with"""
+    _fields_ = [('offset', _i64), ('length', _i64), ('lag', _i32), ('group', _i32)]
+
+
+ADAM_MAX_GROUPS = 8           # LIREC_ADAM_MAX_GROUPS
 ADAM_MAX_RANGES = 64
 CLIP_PARTIALS = 1024          # LIREC_CLIP_PARTIALS: the doubles lirec_grad_sq_partials writes
 
@@ -199,6 +210,10 @@ _PROTOS = {
     'lirec_adam_step_counted': (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _i32, _vp]),
     'lirec_adam_step_ranges': (_i32, [_vp, _vp, _vp, _vp, C.POINTER(AdamRange), _i32, _i32, _f32, _f32, _f32, _f32, _f32, _f32,
                                       _vp, _vp, _vp, _i32, _vp]),
+    'lirec_adam_hyper_write': (_i32, [_vp, C.POINTER(AdamHyper), _i32, _vp]),
+    'lirec_adam_step_groups': (_i32, [_vp, _vp, _vp, _vp, C.POINTER(AdamGroupRange), _i32, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _i32,
+                                      _vp]),
+    'lirec_set_adam_hyper_row': (_i32, [_vp]),
     'lirec_counter_add': (_i32, [_vp, C.POINTER(C.c_int64), _i32, _vp]),
     'lirec_grad_sq_partials': (_i32, [_vp, C.POINTER(AdamRange), _i32, _vp, _vp]),
     'lirec_clip_finalize': (_i32, [_vp, _vp, _i32, _f32, _f32, _vp, _vp]),
@@ -251,7 +266,8 @@ def lib():
         fn.restype, fn.argtypes = res, args
     for which, st in list(enumerate((EmbedFwdArgs, EmbedBwdArgs, MarginLossArgs, Dropout, RowSel))) + [(8, EmbedDxArgs),
                                                                                                       (9, EmbedDxIndexedArgs),
-                                                                                                      (10, AdamRange)]:
+                                                                                                      (10, AdamRange), (11, AdamHyper),
+                                                                                                      (12, AdamGroupRange)]:
         if L.lirec_abi_sizeof(which) != C.sizeof(st):
             raise LirecError('ABI mismatch for %s: library %d bytes, binding %d bytes'
                              % (st.__name__, L.lirec_abi_sizeof(which), C.sizeof(st)))

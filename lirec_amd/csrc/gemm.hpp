@@ -90,6 +90,11 @@ struct AdamFuse {
   const long long* step_dev;
   int wq16c;                                                // the shadow of the new weights (GemmProblem::aux_out) is q16c, not q32b
 };
+// One row of a table of per-group hyper-parameters in device memory (lirec_adam_hyper, include/lirec_hip.h): what the grouped
+// Adam launch and the folded update read where the other launches carry the five values by value.  32 bytes.
+struct AdamHyperRow {
+  float lr, beta1, beta2, eps, wd, pad_[3];
+};
 // (no floating-point contraction inside: whether the compiler forms an fma here would otherwise depend on the kernel the
 //  function is inlined into, and the two kernels must agree to the bit)
 __device__ __forceinline__ float adam1(const AdamFuse& ad, float step_size, float bc2_sqrt, long off, float g) {

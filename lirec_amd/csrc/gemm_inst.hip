@@ -106,9 +106,11 @@ void launch_p2_tn(dim3 grid, hipStream_t s, const GemmGroup& g, int nrep) {
 void launch_p2_tng(dim3 grid, hipStream_t s, const GemmGroup& g, int nrep) {
   lirec::launch(HIP_KERNEL_NAME(gemm_p2_tn_kernel<0, true>), grid, dim3(512), 0, s, g, nrep);
 }
-void launch_p2_tn_reduce(int tiles, int grid, hipStream_t s, const GemmGroup& g, int nrep, const AdamFuse* adam) {
+void launch_p2_tn_reduce(int tiles, int grid, hipStream_t s, const GemmGroup& g, int nrep, const AdamFuse* adam,
+                         const AdamHyperRow* row, int step) {
   const AdamFuse none{};
-  if (adam) lirec::launch(HIP_KERNEL_NAME(gemm_p2_tn_reduce_kernel<true>), dim3((unsigned)tiles * P2_RED_PARTS), dim3(256), 0, s, g, nrep, grid / nrep, *adam);
+  if (adam && row) lirec::launch(gemm_p2_tn_reduce_row_kernel, dim3((unsigned)tiles * P2_RED_PARTS), dim3(256), 0, s, g, nrep, grid / nrep, *adam, row, step);
+  else if (adam) lirec::launch(HIP_KERNEL_NAME(gemm_p2_tn_reduce_kernel<true>), dim3((unsigned)tiles * P2_RED_PARTS), dim3(256), 0, s, g, nrep, grid / nrep, *adam);
   else lirec::launch(HIP_KERNEL_NAME(gemm_p2_tn_reduce_kernel<false>), dim3((unsigned)tiles * P2_RED_PARTS), dim3(256), 0, s, g, nrep, grid / nrep, none);
 }
 #endif

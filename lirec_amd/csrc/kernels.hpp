@@ -1673,6 +1673,9 @@ struct AdamRanges {
   float step_size[ADAM_MAX_RANGES], bc2_sqrt[ADAM_MAX_RANGES];       // by-value step only
   int count;
 };
+// (adam_groups_body below is this body with the hyper-parameters read per range from a device table: the block -> range lookup,
+//  the tails and the ticket are the same text -- a fix to either belongs in both.  Kept apart so that this kernel's code stays
+//  what it was.)
 __device__ __forceinline__ void adam_ranges_body(float* __restrict__ p, const float* __restrict__ g,
                                                  float* __restrict__ m, float* __restrict__ v, const AdamRanges& rt,
                                                  long nblocks, float beta1, float beta2, float eps, float wd,
@@ -1741,6 +1744,97 @@ __global__ __launch_bounds__(256) void adam_ranges_clip_kernel(float* __restrict
                                                                long long* count_dev, int* ticket, int advance,
                                                                const float* __restrict__ coef) {
   adam_ranges_body(p, g, m, v, rt, nblocks, beta1, beta2, eps, wd, gscale * *coef, lr, step_dev, count_dev, ticket, advance);
+}
+
+// Parameter groups (lirec_adam_step_groups): adam_ranges_kernel with a group index per range and the five hyper-parameters of a
+// range taken from row `group` of a table in DEVICE memory (AdamHyperRow, written by adam_hyper_write_kernel in stream order), not
+// from the launch arguments -- a recorded launch holds the table's address and every replay reads the values anew.  The same work
+// distribution; the row is loaded once per range a workgroup touches, by a workgroup-uniform index.  The bias corrections are
+// ALWAYS computed here, in double, from the row's values -- a by-value step t behaves as step_dev holding t -- so a range gets the
+// bits of adam_kernel with step_dev on it with the row's values.
+#define ADAM_MAX_GROUPS 8
+struct AdamGroupRanges {
+  long off[ADAM_MAX_RANGES], len[ADAM_MAX_RANGES];
+  int lag[ADAM_MAX_RANGES];
+  unsigned char group[ADAM_MAX_RANGES];
+  int count;
+};
+// The table's rows by value, as words: thread i of the one wave stores word i (vector stores)
+struct AdamHyperWords {
+  float w[ADAM_MAX_GROUPS * 8];
+};
+__global__ __launch_bounds__(64) void adam_hyper_write_kernel(float* __restrict__ table, const AdamHyperWords rows, int n_words) {
+  static_assert(sizeof(AdamHyperRow) == 32 && ADAM_MAX_GROUPS * 8 == 64, "one word per lane");
+  const int i = threadIdx.x;
+  if (i < n_words) table[i] = rows.w[i];
+}
+// (a copy of adam_ranges_body above -- lookup, tails, ticket -- with the row load in place of the by-value arguments: a fix to
+//  either belongs in both)
+__device__ __forceinline__ void adam_groups_body(float* __restrict__ p, const float* __restrict__ g,
+                                                 float* __restrict__ m, float* __restrict__ v, const AdamGroupRanges& rt,
+                                                 long nblocks, const AdamHyperRow* __restrict__ table, int step, float gscale,
+                                                 const long long* __restrict__ step_dev, long long* count_dev, int* ticket,
+                                                 int advance) {
+  long long t_counted = 0;
+  if (count_dev) t_counted = __hip_atomic_load(count_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
+  const long long t_dev = count_dev ? t_counted : (step_dev ? *step_dev : (long long)step);
+  AdamFuse ad{p, g, m, v, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, gscale, 0.f, step_dev};
+  int cur = -1;
+  float step_size = 0.f, bc2_sqrt = 1.f;
+  for (long wb = blockIdx.x; wb < nblocks; wb += gridDim.x) {
+    long b = wb;
+    int r = 0;
+    for (; r < rt.count - 1; ++r) {
+      const long nb = (rt.len[r] + ADAM_RANGE_BLOCK - 1) / ADAM_RANGE_BLOCK;
+      if (b < nb) break;
+      b -= nb;
+    }
+    if (r != cur) {               // (uniform: a workgroup's blocks ascend, so once per range it touches)
+      cur = r;
+      const AdamHyperRow h = table[rt.group[r]];
+      ad.lr = h.lr; ad.beta1 = h.beta1; ad.beta2 = h.beta2; ad.eps = h.eps; ad.wd = h.wd;
+      long long tr = t_dev - rt.lag[r];
+      if (tr < 1) tr = 1;
+      step_size = (float)((double)h.lr / (1.0 - pow((double)h.beta1, (double)tr)));
+      bc2_sqrt = (float)sqrt(1.0 - pow((double)h.beta2, (double)tr));
+    }
+    const long first = b * ADAM_RANGE_BLOCK;                  // within the range
+    long left = rt.len[r] - first;
+    if (left > ADAM_RANGE_BLOCK) left = ADAM_RANGE_BLOCK;
+    const long e = 4L * threadIdx.x;
+    const long at = rt.off[r] + first + e;
+    if (e + 4 <= left) {
+      (void)adam4(ad, step_size, bc2_sqrt, at, *reinterpret_cast<const f32x4*>(g + at));
+    } else {
+      for (long j = 0; e + j < left; ++j) (void)adam1(ad, step_size, bc2_sqrt, at + j, g[at + j]);
+    }
+  }
+  if (count_dev && advance) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int tk = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (tk == (int)gridDim.x - 1) {
+        __hip_atomic_store(count_dev, t_counted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+}
+__global__ __launch_bounds__(256) void adam_groups_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                          float* __restrict__ m, float* __restrict__ v, const AdamGroupRanges rt,
+                                                          long nblocks, const AdamHyperRow* __restrict__ table, int step,
+                                                          float gscale, const long long* __restrict__ step_dev,
+                                                          long long* count_dev, int* ticket, int advance) {
+  adam_groups_body(p, g, m, v, rt, nblocks, table, step, gscale, step_dev, count_dev, ticket, advance);
+}
+// ... clipped: as adam_clip_kernel
+__global__ __launch_bounds__(256) void adam_groups_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                               float* __restrict__ m, float* __restrict__ v, const AdamGroupRanges rt,
+                                                               long nblocks, const AdamHyperRow* __restrict__ table, int step,
+                                                               float gscale, const long long* __restrict__ step_dev,
+                                                               long long* count_dev, int* ticket, int advance,
+                                                               const float* __restrict__ coef) {
+  adam_groups_body(p, g, m, v, rt, nblocks, table, step, gscale * *coef, step_dev, count_dev, ticket, advance);
 }
 
 // ---------------------------------------------------------------------------

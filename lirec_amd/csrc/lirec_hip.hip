@@ -143,6 +143,9 @@ static inline float grad_beta() { return g_grad_overwrite ? 0.f : 1.f; }
 // Per host thread, like g_grad_overwrite and the recorder -- NOT per context: the side streams' launches of a step are issued by
 // the thread that set it, under contexts of their own.
 static thread_local const float* t_adam_clip = nullptr;
+// The device row a folded first-layer update issued by this host thread reads its five hyper-parameters from
+// (lirec_set_adam_hyper_row), NULL = off: the values of lirec_fused_adam, by value, and today's kernel.  Per host thread, as above.
+static thread_local const lirec_adam_hyper* t_adam_hyper_row = nullptr;
 // While the mode is on, every weight / bias gradient target that is handed to a launch is noted: a parameter written by TWO
 // launches of one step (a tied module, a gradient cut over several launches) would silently lose the first contribution -- the
 // caller that switches the mode on asks for the count of such targets afterwards (lirec_grad_overwrite_conflicts) and keeps
@@ -761,7 +764,11 @@ static int launch_p2(GemmGroup& g0, hipStream_t s, int site, const int* nt_bound
     // (a site of its own: the `embed_dW1` figure is then the GEMM kernel's, the one a kernel trace lists under its name)
     // bytes: at most two partial tiles per workgroup read, every output tile written once
     const int pr = prof_start(PS_EMBED_DW1_RED, s);
-    launch_p2_tn_reduce(tiles, G, s, g, nrep, adam ? &af : nullptr);
+    // (device-resident hyper-parameters: the row kernel, which computes the bias corrections itself from the step it is given)
+    if (adam && t_adam_hyper_row)
+      launch_p2_tn_reduce(tiles, G, s, g, nrep, &af, reinterpret_cast<const AdamHyperRow*>(t_adam_hyper_row), adam->step < 1 ? 1 : adam->step);
+    else
+      launch_p2_tn_reduce(tiles, G, s, g, nrep, adam ? &af : nullptr);
     // (+ the update: p, m, v read and written, the q32b shadow written)
     prof_stop(pr, s, 0.0, 4.0 * 65536.0 * (2.0 * G + tiles) + (adam ? (adam->wq ? 28.0 : 24.0) * (double)adam->n_params : 0.0));
   }
@@ -982,6 +989,8 @@ int lirec_abi_sizeof(int which) {
     case 8: return (int)sizeof(lirec_embed_dx_args);
     case 9: return (int)sizeof(lirec_embed_dx_indexed_args);
     case 10: return (int)sizeof(lirec_adam_range);
+    case 11: return (int)sizeof(lirec_adam_hyper);
+    case 12: return (int)sizeof(lirec_adam_group_range);
     default: return -1;
   }
 }
@@ -2455,6 +2464,73 @@ int lirec_adam_step_ranges(float* p, const float* g, float* m, float* v, const l
 int lirec_set_adam_clip(const float* coef_dev) {
   if (reinterpret_cast<uintptr_t>(coef_dev) & 3) return LIREC_EINVAL;
   t_adam_clip = coef_dev;
+  return LIREC_OK;
+}
+
+// ---- parameter groups: hyper-parameters in device memory ----
+static bool hyper_table_ok(const lirec_adam_hyper* table, int32_t n_groups) {
+  static_assert(sizeof(lirec_adam_hyper) == sizeof(AdamHyperRow) && sizeof(lirec_adam_hyper) == 32, "the header's row is the kernels'");
+  static_assert(LIREC_ADAM_MAX_GROUPS == ADAM_MAX_GROUPS, "the header's number of groups is the kernels'");
+  return table && (reinterpret_cast<uintptr_t>(table) & 15) == 0 && n_groups >= 1 && n_groups <= LIREC_ADAM_MAX_GROUPS;
+}
+
+int lirec_adam_hyper_write(lirec_adam_hyper* table_dev, const lirec_adam_hyper* rows_host, int32_t n_groups, lirec_stream_t stream) {
+  if (!hyper_table_ok(table_dev, n_groups) || !rows_host) return LIREC_EINVAL;
+  AdamHyperWords w;
+  memset(&w, 0, sizeof(w));
+  for (int i = 0; i < n_groups; ++i) {
+    const lirec_adam_hyper& r = rows_host[i];
+    float* q = w.w + 8 * i;
+    q[0] = r.lr; q[1] = r.beta1; q[2] = r.beta2; q[3] = r.eps; q[4] = r.weight_decay;       // (the padding words: zeros)
+  }
+  lirec::launch(adam_hyper_write_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<float*>(table_dev), w,
+                (int)(8 * n_groups));
+  LIREC_CHECK_LAUNCH();
+  return LIREC_OK;
+}
+
+int lirec_adam_step_groups(float* p, const float* g, float* m, float* v, const lirec_adam_group_range* ranges, int32_t count,
+                           const lirec_adam_hyper* table_dev, int32_t n_groups, int32_t step, float grad_scale,
+                           const int64_t* step_dev, int64_t* count_dev, int32_t* ticket, int32_t advance, lirec_stream_t stream) {
+  if (!p || !g || !m || !v || count < 0 || count > LIREC_ADAM_MAX_RANGES || (count > 0 && !ranges)) return LIREC_EINVAL;
+  if (!adam_aligned(p, g, m, v)) return LIREC_EINVAL;
+  if (!hyper_table_ok(table_dev, n_groups)) return LIREC_EINVAL;
+  if (step_dev && count_dev) return LIREC_EINVAL;
+  if (count_dev && !ticket) return LIREC_EINVAL;
+  const bool by_value = !step_dev && !count_dev;
+  AdamGroupRanges rt;
+  memset(&rt, 0, sizeof(rt));
+  long nblocks = 0;
+  int64_t end = 0, total = 0;                                  // ascending, disjoint
+  for (int r = 0; r < count; ++r) {
+    const lirec_adam_group_range& q = ranges[r];
+    if (q.length < 0 || q.offset < 0 || (q.offset & 3) != 0 || q.lag < 0 || q.offset < end) return LIREC_EINVAL;
+    if (q.group < 0 || q.group >= n_groups) return LIREC_EINVAL;
+    if (by_value && (int64_t)step - q.lag < 1) return LIREC_EINVAL;
+    end = q.offset + q.length; total += q.length;
+    rt.off[r] = (long)q.offset; rt.len[r] = (long)q.length; rt.lag[r] = q.lag; rt.group[r] = (unsigned char)q.group;
+    nblocks += (long)((q.length + ADAM_RANGE_BLOCK - 1) / ADAM_RANGE_BLOCK);
+  }
+  rt.count = count;
+  if (nblocks == 0) return LIREC_OK;
+  const long blocks = nblocks > 2048 ? 2048 : nblocks;
+  const AdamHyperRow* table = reinterpret_cast<const AdamHyperRow*>(table_dev);
+  const int pi = prof_start(PS_ADAM, (hipStream_t)stream);
+  if (t_adam_clip)
+    lirec::launch(adam_groups_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, rt, nblocks, table,
+                  (int)step, grad_scale, (const long long*)step_dev, (long long*)count_dev, (int*)ticket, (int)(advance != 0),
+                  t_adam_clip);
+  else
+    lirec::launch(adam_groups_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, rt, nblocks, table,
+                  (int)step, grad_scale, (const long long*)step_dev, (long long*)count_dev, (int*)ticket, (int)(advance != 0));
+  prof_stop(pi, (hipStream_t)stream, 0.0, 28.0 * (double)total);
+  LIREC_CHECK_LAUNCH();
+  return LIREC_OK;
+}
+
+int lirec_set_adam_hyper_row(const lirec_adam_hyper* row_dev) {
+  if (reinterpret_cast<uintptr_t>(row_dev) & 15) return LIREC_EINVAL;
+  t_adam_hyper_row = row_dev;
   return LIREC_OK;
 }
 

@@ -82,6 +82,7 @@ class _MarkingSync:
         self.marks.append((ops.CommandList.mark(), 'finish', None, None))
 
     sharded = property(lambda self: self.real.sharded)
+    _launch_stream = property(lambda self: self.real._launch_stream)      # (FusedAdam: the early stream has a hyper-parameter table)
     real_world = property(lambda self: self.real.real_world)
 
 
@@ -241,7 +242,14 @@ class RecordedTrainStep:
         self.fused = bool(self.sync is None and getattr(_opt, 'fuse_dw1_adam', True) and getattr(model, 'last_layer1_planes', False)
                           and getattr(model, '_has_ints', False) and getattr(model, '_has_ctx', False)
                           and hasattr(optimizer, 'arm_first_layer_update') and hasattr(model, 'refresh_w1q') and not clipping)
-        if self.fused and hasattr(optimizer, 'trainable_ranges') and not optimizer.all_trainable():
+        if self.fused and getattr(optimizer, 'device_hyper', False):
+            # (parameter groups: the folded update reads ONE row of the hyper-parameter table -- the first layers in one group, all
+            #  trainable and up to date, or frozen altogether)
+            lo, hi, _ = model.first_layer_range()
+            rs = optimizer.trainable_ranges(lo, hi)
+            if rs and not (len(rs) == 1 and rs[0][:3] == (lo, hi, 0)):
+                self.fused = False
+        elif self.fused and hasattr(optimizer, 'trainable_ranges') and not optimizer.all_trainable():
             # (first layers PARTLY trainable, or behind: the optimiser does not arm the fused update -- the ordinary update writes no
             #  shadow, the forward stages the weights itself.  Frozen altogether: nothing writes them, the shadow stays current.)
             lo, hi, _ = model.first_layer_range()
@@ -280,6 +288,8 @@ class RecordedTrainStep:
                     self._pre_lane = (_STAGE_LANES[key], None)
                     self.pre[0] = model.prestage(self.batches[0])
                     self.pre[1] = model.prestage(self.batches[1], advance=1)
+                if hasattr(optimizer, 'sync_hyper'):
+                    optimizer.sync_hyper()          # (a command list never contains a write to the hyper-parameter tables)
                 ops.CommandList.begin()
                 try:
                     self._one_step(k=0)
@@ -368,6 +378,7 @@ class RecordedTrainStep:
         """Host mirrors of the device counters (checkpoints, switching back to the eager loop)."""
         self.model._fwd_train_calls += 1
         self.optim._step += 1
+        self.optim._opt_called = True               # (torch's lr_scheduler: an optimiser step HAS been taken -- no order warning)
         if hasattr(self.optim, '_advance_lags'):
             self.optim._advance_lags()              # (frozen parameters sat this update out, as in the eager step())
         if hasattr(self.loss, '_sample_key'):
@@ -379,7 +390,12 @@ class RecordedTrainStep:
         parameter is frozen or behind, the requires_grad flags and the trainable parameters' lags: they decided which launches
         were recorded and are in the recorded lirec_adam_step_ranges tables (FusedAdam.frozen_key)"""
         g = optimizer.param_groups[0]
-        key = (float(g['lr']), tuple(float(b) for b in g['betas']), float(g['eps']), float(g['weight_decay']), float(getattr(optimizer, 'grad_scale', 1.0)))
+        if getattr(optimizer, 'device_hyper', False):
+            # (the hyper-parameters live in device tables the recorded launches hold by ADDRESS -- FusedAdam.sync_hyper writes what
+            #  changed in front of a replay --; what is baked in is which group a range reads: the membership)
+            key = (('device_hyper', optimizer.group_membership()), float(getattr(optimizer, 'grad_scale', 1.0)))
+        else:
+            key = (float(g['lr']), tuple(float(b) for b in g['betas']), float(g['eps']), float(g['weight_decay']), float(getattr(optimizer, 'grad_scale', 1.0)))
         frozen = optimizer.frozen_key() if hasattr(optimizer, 'frozen_key') else ()
         key = key + (frozen,) if frozen else key
         # (gradient clipping: whether the norm launches and the clipped Adam kernels were recorded, and the bound the recorded
@@ -401,6 +417,11 @@ class RecordedTrainStep:
                                'recorded Adam launches carry them by value -- release() this object and record a new one (a learning-'
                                'rate schedule: once per change)' % (self._hyper, self.hyper_key(self.optim)))
         self._check_core()
+        if getattr(self.optim, 'device_hyper', False):
+            # (what param_groups holds now -- a scheduler's step, a changed weight decay -- goes to the tables the recorded Adam
+            #  launches read, each on the stream that reads it; no launch when nothing changed)
+            import ctypes as C
+            self.optim.sync_hyper(main=C.c_void_p(self.stream.cuda_stream))
         # The recorded forward reads the weights' q32b forms the recorded updates keep current.  Anything else that changed the
         # parameters since the last replay -- load_state_dict, an eager optimizer.step() without release() -- has marked them stale
         # (host flags): rebuild them from the parameters as they are now, on this stream, before the replay reads them.

@@ -883,6 +883,8 @@ class _HotPathModule(nn.Module):
         # the first-layer parameters' update folded into the launch that finishes their gradients (armed by the optimiser for a
         # step issued as a unit: FusedAdam.arm_first_layer_update): both heads' tails must be the ONE gemm_p2 launch
         adam = self.__dict__.pop('_dw1_adam', None)
+        # (... reading its hyper-parameters from this device row -- FusedAdam with device_hyper -- or, None, carrying them by value)
+        hyper_row = self.__dict__.pop('_dw1_hyper_row', None)
         if want_dx:
             adam = None          # (the features' gradient reads the first-layer weights after the tail: no update folded into it)
         if adam is not None and not (has_i and has_c and pieces is None and st.get('planes_i') is not None
@@ -970,7 +972,8 @@ class _HotPathModule(nn.Module):
         else:
             # (data parallel or not: both heads' tails share their launches -- the first-layer weight gradients of the two
             #  heads are ONE persistent launch, so their bucket is announced once, at the end)
-            run(2)
+            with ops.adam_hyper_row(hyper_row if adam is not None else None):
+                run(2)
         dX = None
         if want_dx:
             # dX = dZ1 W1 per (head, segment), on this stream right behind the tail that left dZ1 in the workspaces, with the weights

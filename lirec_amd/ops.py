@@ -740,6 +740,54 @@ def adam_step_ranges(p, g, m, v, ranges, step, lr, beta1, beta2, eps, weight_dec
           'lirec_adam_step_ranges')
 
 
+def adam_hyper_write(table, rows):
+    """lirec_adam_hyper_write: ``table`` (device float32, 8 words a row, 16-byte aligned) takes ``rows`` =
+    [(lr, beta1, beta2, eps, weight_decay), ...] (1..8), by one tiny launch on the current stream -- the stream that reads it"""
+    from ._lib import AdamHyper
+    assert table.dtype == torch.float32 and table.is_contiguous() and table.numel() >= 8 * len(rows)
+    arr = (AdamHyper * max(len(rows), 1))()
+    for a, (lr, b1, b2, eps, wd) in zip(arr, rows):
+        a.lr, a.beta1, a.beta2, a.eps, a.weight_decay = float(lr), float(b1), float(b2), float(eps), float(wd)
+    check(lib().lirec_adam_hyper_write(_p(table), arr, len(rows), _stream()), 'lirec_adam_hyper_write')
+
+
+def adam_step_groups(p, g, m, v, ranges, table, n_groups, step, grad_scale=1.0, step_dev=None, count_dev=None, ticket=None,
+                     advance=True):
+    """lirec_adam_step_groups: adam_step_ranges over ``ranges`` = [(offset, length, lag, group), ...] with the hyper-parameters
+    of a range read from row ``group`` of the device ``table`` (adam_hyper_write) of ``n_groups`` rows"""
+    from ._lib import AdamGroupRange
+    n = p.numel()
+    assert g.numel() == n and m.numel() == n and v.numel() == n
+    assert all(0 <= o and 0 <= k and o + k <= n for o, k, _, _ in ranges), 'a range outside the buffers'
+    assert table.dtype == torch.float32 and table.numel() >= 8 * n_groups
+    arr = (AdamGroupRange * max(len(ranges), 1))()
+    for a, (o, k, lag, grp) in zip(arr, ranges):
+        a.offset, a.length, a.lag, a.group = int(o), int(k), int(lag), int(grp)
+    check(lib().lirec_adam_step_groups(_p(p), _p(g), _p(m), _p(v), arr, len(ranges), _p(table), int(n_groups), int(step),
+                                       float(grad_scale), _p(step_dev), _p(count_dev), _p(ticket), int(bool(advance)), _stream()),
+          'lirec_adam_step_groups')
+
+
+class adam_hyper_row:
+    """``with ops.adam_hyper_row(row):`` -- a folded first-layer update this host thread issues inside reads its hyper-parameters
+    from the device row ``row`` (8 float32 words of a table; lirec_set_adam_hyper_row); cleared on the way out.  ``None``: nothing
+    is set."""
+
+    def __init__(self, row):
+        self.row = row
+
+    def __enter__(self):
+        if self.row is not None:
+            assert self.row.dtype == torch.float32
+            check(lib().lirec_set_adam_hyper_row(_p(self.row)), 'lirec_set_adam_hyper_row')
+        return self
+
+    def __exit__(self, *exc):
+        if self.row is not None:
+            check(lib().lirec_set_adam_hyper_row(None), 'lirec_set_adam_hyper_row')
+        return False
+
+
 def grad_sq_partials(g, ranges, partials):
     """lirec_grad_sq_partials: ``partials`` (device float64[CLIP_PARTIALS]) = the fixed grid's sums of squares of ``g`` over
     ``ranges`` = [(offset, length), ...] (1..64, offsets multiples of 4; a third entry -- a lag -- is ignored)"""

@@ -25,6 +25,17 @@ over the gradients, no host visit, so the recorded step and the sharded data-par
 TORCH: the gradients in the flat buffer -- every ``p.grad`` -- stay UNCLIPPED after the step (``clip_grad_norm_`` scales them in
 place); whoever wants the clipped values multiplies by ``optimizer.clip_coef``.  The update itself is the same to one fp32 rounding
 of the scalar: g (grad_scale coef) here, (g coef) grad_scale there.
+
+Parameter groups (``param_groups=[{'params': [names or parameters], 'lr': ..., 'weight_decay': ...}, ...]``, at most 8) and
+device-resident hyper-parameters (``device_hyper``): lr, betas, eps and weight_decay of every group live in a small table in device
+memory that the Adam launches read (``lirec_adam_step_groups``; the folded first-layer update through
+``lirec_set_adam_hyper_row``) instead of taking them by value.  ``self.param_groups`` is torch's list: a scheduler, or a loop that
+assigns ``g['lr']``, changes the values and ``sync_hyper()`` -- called by ``step()`` and in front of every replay of a recorded
+step -- sends what changed, one tiny launch per table.  ONE TABLE PER ISSUING STREAM (the caller's, the weight-gradient side
+stream, the collectives' early stream), each written only on the stream that reads it: a replayed step leaves the side stream's
+Adam launch of step t running into step t + 1, and a write from the main stream would hand part of that launch the next step's
+values.  ``device_hyper=None`` is on with more than one group and off with one; off with one group is the by-value code path,
+launch for launch.  The groups are fixed at construction (the flat layout is): ``add_param_group`` raises afterwards.
 """
 from __future__ import annotations
 
@@ -37,13 +48,50 @@ from .config import opt
 
 
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, model, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5, max_grad_norm=None):
+    MAX_GROUPS = 8                     # (LIREC_ADAM_MAX_GROUPS: the rows of a hyper-parameter table)
+
+    @staticmethod
+    def _check_values(lr, betas, eps, weight_decay):
+        """the values torch.optim.Adam rejects, with its messages"""
+        if not 0.0 <= lr:
+            raise ValueError('Invalid learning rate: {}'.format(lr))
+        if not 0.0 <= eps:
+            raise ValueError('Invalid epsilon value: {}'.format(eps))
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError('Invalid beta parameter at index 0: {}'.format(betas[0]))
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError('Invalid beta parameter at index 1: {}'.format(betas[1]))
+        if not 0.0 <= weight_decay:
+            raise ValueError('Invalid weight_decay value: {}'.format(weight_decay))
+
+    def __init__(self, model, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5, max_grad_norm=None, param_groups=None,
+                 device_hyper=None, amsgrad=False):
         self.model = model
         params = list(model.parameters())
         self._names = [n for n, _ in model.named_parameters()]        # (in the order of model._plist)
+        if amsgrad:
+            raise ValueError('FusedAdam: amsgrad is not supported (the reference never sets it, mlp/model.py:599-601)')
+        self._check_values(lr, betas, eps, weight_decay)
         # (amsgrad: part of torch.optim.Adam's param_groups since torch 1.1 -- the reference's pin -- so that an
         #  optimizer state_dict saved here has the keys a stock Adam expects, and the other way round)
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False))
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False)
+        if param_groups is None:
+            super().__init__(params, defaults)
+        else:
+            super().__init__(self._resolve_groups(param_groups, params), defaults)
+        for grp in self.param_groups:
+            if grp.get('amsgrad'):
+                raise ValueError('FusedAdam: amsgrad is not supported (the reference never sets it, mlp/model.py:599-601)')
+            self._check_values(grp['lr'], grp['betas'], grp['eps'], grp['weight_decay'])
+        self._layout_fixed = True      # (add_param_group from here on raises)
+        gi = {id(p): i for i, grp in enumerate(self.param_groups) for p in grp['params']}
+        self._group_of = {n: gi[id(p)] for n, p in zip(self._names, params)}          # parameter name -> index of its group
+        many = len(self.param_groups) > 1
+        if many and device_hyper is not None and not device_hyper:
+            raise ValueError('FusedAdam: %d parameter groups need device_hyper (by value the launches carry one set of '
+                             'hyper-parameters)' % len(self.param_groups))
+        self.device_hyper = many if device_hyper is None else bool(device_hyper)
+        self._tables = {}              # issuing stream ('main', 'side', 'early') -> [device float32[64], the rows it last received]
         self._m = self._v = None
         self._step = 0
         self.grad_scale = 1.0          # 1/world_size after a summing all-reduce
@@ -53,6 +101,117 @@ class FusedAdam(torch.optim.Optimizer):
         self._ranges_key = self._ranges = None
         self.max_grad_norm = max_grad_norm      # None / 0: no clipping; settable between steps (a recorded step is recorded again)
         self._clip_out = None          # device float32[2]: (clip coefficient, gradient norm) of the last clipped step
+
+    # -- parameter groups -------------------------------------------------------
+    def _resolve_groups(self, param_groups, params):
+        """the constructor's ``param_groups`` with names replaced by the parameter objects; every parameter of the model in
+        exactly one group, at most MAX_GROUPS groups"""
+        if isinstance(param_groups, dict) or not isinstance(param_groups, (list, tuple)) or not param_groups:
+            raise ValueError('FusedAdam: param_groups must be a non-empty list of dicts')
+        if len(param_groups) > self.MAX_GROUPS:
+            raise ValueError('FusedAdam: %d parameter groups, at most %d' % (len(param_groups), self.MAX_GROUPS))
+        by_name = dict(zip(self._names, params))
+        seen, out = {}, []
+        for i, grp in enumerate(param_groups):
+            if not isinstance(grp, dict) or 'params' not in grp:
+                raise ValueError('FusedAdam: parameter group %d is not a dict with \'params\'' % i)
+            members = grp['params']
+            members = [members] if isinstance(members, (str, torch.Tensor)) else list(members)
+            ps = []
+            for x in members:
+                if isinstance(x, str):
+                    if x not in by_name:
+                        raise ValueError('FusedAdam: parameter group %d names %r, which is no parameter of the model' % (i, x))
+                    x = by_name[x]
+                if not any(x is p for p in params):
+                    raise ValueError('FusedAdam: parameter group %d holds a tensor that is no parameter of the model' % i)
+                if id(x) in seen:
+                    raise ValueError('FusedAdam: a parameter is in parameter groups %d and %d' % (seen[id(x)], i))
+                seen[id(x)] = i
+                ps.append(x)
+            out.append(dict(grp, params=ps))
+        missing = [n for n, p in zip(self._names, params) if id(p) not in seen]
+        if missing:
+            raise ValueError('FusedAdam: parameters in no parameter group: %s' % ', '.join(missing))
+        return out
+
+    def add_param_group(self, param_group):
+        if getattr(self, '_layout_fixed', False):
+            raise RuntimeError('FusedAdam.add_param_group: the groups are fixed at construction (the flat parameter layout is); '
+                               'pass param_groups= to the constructor')
+        super().add_param_group(param_group)
+
+    def group_membership(self):
+        """the group index of every parameter, in ``model.named_parameters()`` order"""
+        return tuple(self._group_of[n] for n in self._names)
+
+    def group_names(self):
+        """the parameter names of every group, in the groups' own order (the numbering of ``state_dict()``)"""
+        name_of = {id(p): n for n, p in zip(self._names, self.model._plist)}
+        return [[name_of[id(p)] for p in grp['params']] for grp in self.param_groups]
+
+    def hyper_rows(self):
+        """(lr, beta1, beta2, eps, weight_decay) of every group as ``param_groups`` has them now, checked as at construction"""
+        rows = []
+        for grp in self.param_groups:
+            lr, betas, eps, wd = float(grp['lr']), (float(grp['betas'][0]), float(grp['betas'][1])), float(grp['eps']), float(grp['weight_decay'])
+            self._check_values(lr, betas, eps, wd)
+            rows.append((lr, betas[0], betas[1], eps, wd))
+        return tuple(rows)
+
+    def _issuing_streams(self):
+        """the streams that issue Adam launches, as {role: raw handle or None (= the current one)}"""
+        m = self.model
+        roles = {'main': None}
+        # (the side stream only where step() can put an update on it -- opt.adam_on_side_stream, model._take_side_after_backward --:
+        #  no lane is made, and no table written, for a run that never updates there)
+        lane = None
+        if hasattr(m, '_wgrad_lane') and m.flat_params().is_cuda and getattr(opt, 'adam_on_side_stream', True) \
+                and getattr(getattr(m, 'grad_sync', None), 'world', 1) <= 1:
+            lane = m._wgrad_lane()
+        if lane is not None:
+            roles['side'] = C.c_void_p(lane[0].cuda_stream)
+        early = getattr(getattr(m, 'grad_sync', None), '_launch_stream', None)
+        if early is not None:
+            roles['early'] = C.c_void_p(early.cuda_stream)
+        return roles
+
+    def sync_hyper(self, main=None):
+        """Under ``device_hyper``: compare ``param_groups`` with what the table of each issuing stream last received and send what
+        differs -- one lirec_adam_hyper_write per stale table, ON THE STREAM THAT READS IT (``main``: the raw handle of the stream
+        the caller's Adam launches go to, None = the current one); nothing otherwise.  Returns the number of writes issued.
+        Never inside a recording: a command list holds the tables' addresses, not their values."""
+        if not self.device_hyper:
+            return 0
+        rows = self.hyper_rows()
+        stale = [(role, h) for role, h in self._issuing_streams().items() if self._tables.get(role, (None, None))[1] != rows]
+        if not stale:
+            return 0
+        if ops.CommandList.mark() >= 0:
+            raise RuntimeError('FusedAdam: the hyper-parameter tables are not current while a step is being recorded (a command '
+                               'list never contains a write to them); call sync_hyper() before the recording begins')
+        dev = self.model.flat_params().device
+        for role, h in stale:
+            if role not in self._tables:
+                # (torch.empty: no fill launch on the current stream that could meet the write on another one)
+                self._tables[role] = [torch.empty(8 * self.MAX_GROUPS, dtype=torch.float32, device=dev), None]
+            if role == 'main' and main is not None:
+                h = main
+            if h is None:
+                ops.adam_hyper_write(self._tables[role][0], rows)
+            else:
+                with ops.on_stream(h):
+                    ops.adam_hyper_write(self._tables[role][0], rows)
+            self._tables[role][1] = rows
+        return len(stale)
+
+    def _table(self, role):
+        """the table of issuing stream ``role``, which must be current (sync_hyper)"""
+        t = self._tables.get(role)
+        if t is None or t[1] != self._rows_now:
+            raise RuntimeError('FusedAdam: the hyper-parameter table of the %s stream is not current (sync_hyper() was not called '
+                               'for it, or param_groups changed inside a step)' % role)
+        return t[0]
 
     # -- flat state -----------------------------------------------------------
     def _ensure_state(self):
@@ -157,7 +316,17 @@ class FusedAdam(torch.optim.Optimizer):
             return False
         if self._clip_max() is not None:
             return False          # (the norm needs the finished first-layer gradients: they are updated with the rest, clipped)
-        if not self.all_trainable():
+        row = None
+        if self.device_hyper:
+            # (... and all of them in ONE group: the launch reads one row -- of the table of the stream that runs the backward's tail)
+            lo, hi, _ = m.first_layer_range()
+            rs = self.trainable_ranges(lo, hi)
+            if len(rs) != 1 or rs[0][:3] != (lo, hi, 0):
+                return False
+            self.sync_hyper()
+            self._rows_now = self.hyper_rows()
+            row = self._table('main')[8 * rs[0][3]:8 * rs[0][3] + 8]
+        elif not self.all_trainable():
             # (the fused launch updates EVERY first-layer parameter of the call with the one global step: only when each of them
             #  is trainable and has received every update so far)
             lo, hi, _ = m.first_layer_range()
@@ -171,6 +340,10 @@ class FusedAdam(torch.optim.Optimizer):
         valid = bool(getattr(m, '_w1q_valid', False)) and getattr(m, '_w1q_mode', None) == ops.get_gemm_mode()
         m._dw1_adam = ops.fused_adam_args(flat, g, self._m, self._v, n_params, *hyper,
                                           wq=m._w1q_buf if valid else None, wq_first=m._w1q_first if valid else 0)
+        if row is not None:
+            m._dw1_hyper_row = row          # (the five values above are then ignored: lirec_set_adam_hyper_row)
+        else:
+            m.__dict__.pop('_dw1_hyper_row', None)
         return True
 
     # -- frozen parameters ------------------------------------------------------
@@ -190,8 +363,9 @@ class FusedAdam(torch.optim.Optimizer):
         return (flags, tuple(self._lag.get(n, 0) for n, f in zip(self._names, flags) if f))
 
     @staticmethod
-    def merged_ranges(offsets, trainable, lags, extent):
-        """The trainable ranges [(start, end, lag)] of a flat layout, ascending.  ``offsets``: name -> (offset, numel) in flat
+    def merged_ranges(offsets, trainable, lags, extent, groups=None):
+        """The trainable ranges [(start, end, lag)] of a flat layout, ascending -- with ``groups`` (name -> group index; parameter
+        groups): [(start, end, lag, group)], and neighbours merge only when lag AND group are the same.  ``offsets``: name -> (offset, numel) in flat
         order; ``trainable``: name -> bool; ``lags``: name -> int (missing = 0); ``extent``: the buffer's length.  Neighbours in the
         layout that are both trainable with the same lag are merged ACROSS the alignment gap between them (the gap holds zeros in
         all four buffers, which the update leaves zeros -- as the whole-buffer launch always has), and a trainable last parameter
@@ -204,24 +378,27 @@ class FusedAdam(torch.optim.Optimizer):
             if live:
                 end = extent if i == len(names) - 1 else off + k
                 lag = int(lags.get(n, 0))
-                if prev_live and out[-1][2] == lag:
-                    out[-1] = (out[-1][0], end, lag)
+                tail = (lag,) if groups is None else (lag, int(groups[n]))
+                if prev_live and out[-1][2:] == tail:
+                    out[-1] = (out[-1][0], end) + tail
                 else:
-                    out.append((off, end, lag))
+                    out.append((off, end) + tail)
             prev_live = live
         return out
 
     def trainable_ranges(self, lo=None, hi=None):
-        """merged_ranges of the model as it is now (cached on the flags and lags), cut to [lo, hi) when given"""
+        """merged_ranges of the model as it is now (cached on the flags and lags), cut to [lo, hi) when given; under
+        ``device_hyper`` with each range's group: (start, end, lag, group)"""
         m = self.model
         flags = self._flags()
-        key = (flags, tuple(sorted(self._lag.items())), id(m._offsets))
+        key = (flags, tuple(sorted(self._lag.items())), id(m._offsets), bool(self.device_hyper))
         if key != self._ranges_key:
-            self._ranges = self.merged_ranges(m._offsets, dict(zip(self._names, flags)), self._lag, m._flat.numel())
+            self._ranges = self.merged_ranges(m._offsets, dict(zip(self._names, flags)), self._lag, m._flat.numel(),
+                                              self._group_of if self.device_hyper else None)
             self._ranges_key = key
         if lo is None:
             return list(self._ranges)
-        return [(max(a, lo), min(b, hi), lag) for a, b, lag in self._ranges if min(b, hi) > max(a, lo)]
+        return [(max(r[0], lo), min(r[1], hi)) + r[2:] for r in self._ranges if min(r[1], hi) > max(r[0], lo)]
 
     @staticmethod
     def _chunks(rs, most=64):
@@ -235,14 +412,27 @@ class FusedAdam(torch.optim.Optimizer):
                 if not f:
                     self._lag[n] = self._lag.get(n, 0) + 1
 
-    def _update(self, flat, g, a, b, args, g_is_slice=False, counted=None, last=True):
+    def _update(self, flat, g, a, b, args, g_is_slice=False, counted=None, last=True, role='main'):
         """The update of stretch [a, b) of the flat buffers -- ``g``: the flat gradient buffer, or (``g_is_slice``) the b - a
         gradients of the stretch on their own.  One zero-lag range: the whole-stretch launch, as ever; nothing trainable: no
         launch; anything else: lirec_adam_step_ranges, 64 ranges a call.  ``counted`` = (count_dev, ticket): the step from the
         side stream's own counter, ``last``: this stretch is the last of the update (the last launch advances the counter).
+        Under ``device_hyper`` every stretch is lirec_adam_step_groups launches, reading the table of issuing stream ``role``.
         Returns the number of launches issued."""
-        rs = [(a, b, 0)] if self._all_live else self.trainable_ranges(a, b)
         gs = g if g_is_slice else g[a:b]
+        if self.device_hyper:
+            chunks = self._chunks(self.trainable_ranges(a, b))
+            table, n_groups = self._table(role), len(self.param_groups)
+            for i, ch in enumerate(chunks):
+                rel = [(x - a, y - x, lag, grp) for x, y, lag, grp in ch]
+                if counted is not None:
+                    ops.adam_step_groups(flat[a:b], gs, self._m[a:b], self._v[a:b], rel, table, n_groups, 0, args[6],
+                                         count_dev=counted[0], ticket=counted[1], advance=last and i == len(chunks) - 1)
+                else:
+                    ops.adam_step_groups(flat[a:b], gs, self._m[a:b], self._v[a:b], rel, table, n_groups, args[0], args[6],
+                                         step_dev=args[7])
+            return len(chunks)
+        rs = [(a, b, 0)] if self._all_live else self.trainable_ranges(a, b)
         if rs == [(a, b, 0)]:
             if counted is not None:
                 ops.adam_step_counted(flat[a:b], gs, self._m[a:b], self._v[a:b], *args[1:7], counted[0], counted[1], advance=last)
@@ -279,6 +469,10 @@ class FusedAdam(torch.optim.Optimizer):
         self._ensure_state()
         self._all_live = self.all_trainable()
         grp = self.param_groups[0]
+        if self.device_hyper:
+            # (the tables as param_groups has them now; inside a recording they must be current already -- sync_hyper raises)
+            self.sync_hyper()
+            self._rows_now = self.hyper_rows()
         g = self.model.flat_grads(attach=True)
         if self._step_dev is None:
             self._step += 1
@@ -292,7 +486,7 @@ class FusedAdam(torch.optim.Optimizer):
             self._clip_buffers()
         if sync is not None and sync.world > 1:
             if getattr(opt, 'strict', False) and hasattr(sync, 'check_frozen_set'):
-                sync.check_frozen_set(self._flags())
+                sync.check_frozen_set(self._flags(), self.group_membership() if len(self.param_groups) > 1 else ())
             self.model._bucket0_on_side = False
             if clip:
                 self._step_parallel_clipped(sync, flat, g, args)
@@ -310,7 +504,7 @@ class FusedAdam(torch.optim.Optimizer):
                     #  and gathered on the collective's launch stream, beside the tail of backward: GradSync.early_stream)
                     with ops.on_stream(C.c_void_p(early.cuda_stream)), torch.cuda.stream(early):
                         if b > a:
-                            self._update(flat, sync.grad_slice(g, lo, hi), a, b, args, g_is_slice=True)
+                            self._update(flat, sync.grad_slice(g, lo, hi), a, b, args, g_is_slice=True, role='early')
                         sync.gather_params(lo, hi)
                     used = early
                 else:
@@ -335,9 +529,9 @@ class FusedAdam(torch.optim.Optimizer):
                 if self._all_live or self.trainable_ranges(*self.model.first_layer_range()[:2]):
                     self.model.invalidate_w1q()
 
-            def update(lo, hi):
+            def update(lo, hi, role='main'):
                 for a, b in self._minus(lo, hi, skip):
-                    self._update(flat, g, a, b, args)
+                    self._update(flat, g, a, b, args, role=role)
             side = self.model._take_side_after_backward() if hasattr(self.model, '_take_side_after_backward') else None
             if clip:
                 # Clipped: the coefficient needs EVERY gradient finished, so nothing is updated beside the tail of backward -- the side
@@ -370,9 +564,10 @@ class FusedAdam(torch.optim.Optimizer):
                         if not rs:
                             ops.counter_add(self._step_side_dev, [1])
                         for i, (a, b) in enumerate(rs):
-                            self._update(flat, g, a, b, args, counted=(self._step_side_dev, self._side_ticket), last=(i == len(rs) - 1))
+                            self._update(flat, g, a, b, args, counted=(self._step_side_dev, self._side_ticket), last=(i == len(rs) - 1),
+                                         role='side')
                     else:
-                        update(0, hi0)
+                        update(0, hi0, 'side')
                 update(hi0, flat.numel())
                 # (the step ends when the side stream's share has -- unless the caller replays the step and leaves that stream to run
                 #  on into the next one: model._run_backward, `_side_unjoined`)
@@ -391,7 +586,7 @@ class FusedAdam(torch.optim.Optimizer):
                         #  the first layers' update, unclipped -- nothing here can take it back)
                         raise RuntimeError('FusedAdam.step(): max_grad_norm was set after the backward of this step had folded the '
                                            'first-layer update in (arm_first_layer_update); set it before the step begins')
-                    rs = [(0, flat.numel())] if self._all_live else [(a, b - a) for a, b, _ in self.trainable_ranges()]
+                    rs = [(0, flat.numel())] if self._all_live else [(a, b - a) for a, b, *_ in self.trainable_ranges()]
                     if self._clip_accumulate(g, rs, True):
                         self._clip_nothing()              # (nothing trainable: no update; norm 0, coefficient 1)
                     else:
@@ -428,7 +623,7 @@ class FusedAdam(torch.optim.Optimizer):
             a, b = sync.my_slice(lo, hi)
             if b > a:
                 rs = [(a, b, 0)] if self._all_live else self.trainable_ranges(a, b)
-                first = self._clip_accumulate(sync.grad_slice(g, lo, hi), [(x - a, y - x) for x, y, _ in rs], first)
+                first = self._clip_accumulate(sync.grad_slice(g, lo, hi), [(x - a, y - x) for x, y, *_ in rs], first)
         everywhere = not (sync.sharded and sync.real_world > 1 and dist.is_initialized())
         if first:
             if everywhere:                   # (nothing trainable at all)

@@ -95,22 +95,28 @@ class GradSync:
         out = self._slices.get(lo) if (self.sharded and self._tensor_coll) else None
         return out if (out is not None and out.numel() == b - a) else g[a:b]
 
-    def check_frozen_set(self, flags):
+    def check_frozen_set(self, flags, groups=()):
         """COLLECTIVE, under opt.strict, once per frozen set: the parameters' requires_grad flags must be the same on every rank
         (each rank updates its own slice of a bucket and the slices are gathered: a parameter frozen on one rank only would be
-        stale on the others' copies or updated behind the freezer's back).  One small all-reduce of a hash."""
-        if flags == getattr(self, '_frozen_checked', None):
+        stale on the others' copies or updated behind the freezer's back).  One small all-reduce of a hash.  The same holds for
+        the optimiser's PARAMETER GROUPS (``groups``: the group index of every parameter, FusedAdam.group_membership): a rank
+        updates its slice with ITS groups' hyper-parameters, so the membership must be the same everywhere -- it is folded into
+        the hash.  (The groups' VALUES are the caller's to keep equal, as the one learning rate always was.)"""
+        if (flags, groups) == getattr(self, '_frozen_checked', None):
             return
-        self._frozen_checked = flags
+        self._frozen_checked = (flags, groups)
         if self.real_world <= 1 or not dist.is_initialized():
             return
         import hashlib
-        h = int(hashlib.sha1(bytes(bytearray(int(bool(f)) for f in flags))).hexdigest()[:12], 16)
+        # (no groups given: the flags alone, as ever; otherwise a separator and the membership, whatever it is)
+        what = [int(bool(f)) for f in flags] + ([255] + [int(x) for x in groups] if len(groups) else [])
+        h = int(hashlib.sha1(bytes(bytearray(what))).hexdigest()[:12], 16)
         dev = self.get_flat_grad().device if dist.get_backend(self.group) == 'nccl' else 'cpu'
         t = torch.tensor([h, -h], dtype=torch.int64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
         if int(t[0]) != -int(t[1]):
-            raise RuntimeError('data parallelism: the set of frozen parameters (requires_grad) differs between the ranks')
+            raise RuntimeError('data parallelism: the set of frozen parameters (requires_grad) or the membership of the optimiser\'s '
+                               'parameter groups differs between the ranks')
 
     def bucket_ready(self, stage: int, also=None):
         """Called by backward once every kernel writing bucket ``stage`` is enqueued -- on the current stream and,
@@ -259,7 +265,7 @@ class GradSync:
         # (frozen parameters have no gradient: their slices of the buffer hold whatever a shared launch left there and are not
         #  counted -- `trainable_ranges`, FusedAdam's, set by DataParallel; None: everything)
         live = getattr(self, 'trainable_ranges', None)
-        cut = (lambda a, b: [(x, y) for x, y, _ in live(a, b)]) if live is not None else (lambda a, b: [(a, b)])
+        cut = (lambda a, b: [(x, y) for x, y, *_ in live(a, b)]) if live is not None else (lambda a, b: [(a, b)])
         if not (self.sharded and self.real_world > 1 and dist.is_initialized()):
             if live is None:
                 return (g.double() ** 2).sum() * scale ** 2
@@ -315,6 +321,9 @@ class DataParallel:
                                    get_flat_param=model.flat_params)
         optimizer.grad_scale = 1.0 / self.world
         # (frozen parameters -- requires_grad False -- must be the SAME set on every rank: FusedAdam.step checks it under opt.strict)
+        # (the optimiser's PARAMETER GROUPS -- FusedAdam(param_groups=...) -- must be the same on every rank too, membership and
+        #  values: each rank updates its slice of a bucket with its own groups' hyper-parameters and the slices are gathered.  The
+        #  membership is part of that check's hash; groups that differ between ranks are not supported.)
         if hasattr(optimizer, 'trainable_ranges'):
             model.grad_sync.trainable_ranges = optimizer.trainable_ranges
 

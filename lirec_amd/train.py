@@ -99,6 +99,13 @@ def training(train_dataset, **kwargs):
     val_dataset = kwargs.get('val_dataset', kwargs.get('test_dataset'))
     test_dataset = kwargs.get('test_dataset') if 'val_dataset' in kwargs else None
     sampler = kwargs.get('sampler')
+    # scheduler= any object with .step() (torch.optim.lr_scheduler.*), called after every optimiser step -- eager or replayed --
+    # (scheduler_every='step') or after every epoch ('epoch').  With FusedAdam(device_hyper=True) the recorded step follows it
+    # without being recorded again (FusedAdam.sync_hyper); by value every change of the learning rate records anew.
+    scheduler, scheduler_every = kwargs.get('scheduler'), kwargs.get('scheduler_every', 'step')
+    if scheduler_every not in ('step', 'epoch'):
+        raise ValueError('training(): scheduler_every must be \'step\' or \'epoch\', not %r' % (scheduler_every,))
+    sched_step = scheduler.step if (scheduler is not None and scheduler_every == 'step') else (lambda: None)
     if world > 1 and sampler is None:
         if getattr(model, 'grad_sync', None) is None:
             raise RuntimeError('training() under torch.distributed: wrap model / optimizer with lirec_amd.parallel.DataParallel first')
@@ -156,6 +163,7 @@ def training(train_dataset, **kwargs):
                 PinnedPool.copied(batch.get('_slots'))
                 nlab = len(batch['labels'])
                 lval = rec['step'].step().clone()
+                sched_step()
                 ev = torch.cuda.Event()
                 ev.record()
                 pending.append((lval, nlab, ev))
@@ -203,12 +211,14 @@ def training(train_dataset, **kwargs):
                         rec['step'].release()
                     rec, same_layout, dp_gave_up = None, -10 ** 9, True
                     if g is not None:
+                        sched_step()              # (the step was taken all the same)
                         ev = torch.cuda.Event()
                         ev.record()
                         pending.append((lval, len(labels), ev))
                         seen += len(labels)
                         continue
                 if rec is not None:
+                    sched_step()                  # (the recording took this batch's step)
                     ev = torch.cuda.Event()
                     ev.record()
                     pending.append((lval, len(labels), ev))
@@ -227,6 +237,7 @@ def training(train_dataset, **kwargs):
                 from .graph import checked_overwrite_step
                 ow_ok[(lay, _flag_key(optimizer))], lv = checked_overwrite_step(model, loss, optimizer, batch)
                 lval = lv.detach().reshape(-1)[:1]
+                sched_step()
                 ev = torch.cuda.Event()
                 ev.record()
                 pending.append((lval, len(labels), ev))
@@ -245,6 +256,7 @@ def training(train_dataset, **kwargs):
             optimizer.zero_grad()
             lv.backward()                 # a 0-d or one-element tensor, as mlp/train.py:62
             optimizer.step()
+            sched_step()
             ev = None
             if lval.is_cuda:
                 ev = torch.cuda.Event()
@@ -258,6 +270,8 @@ def training(train_dataset, **kwargs):
                 print('Epoch: [{0}][{1}/{2}]\tTime {bt.val:.3f} ({bt.avg:.3f})\tData {dt.val:.3f} ({dt.avg:.3f})\t'
                       'Loss {ls.val:.4f} ({ls.avg:.4f})\t'.format(epoch, i, len(loader), bt=batch_time, dt=data_time, ls=losses))
         _flush_losses(pending, losses)
+        if scheduler is not None and scheduler_every == 'epoch':
+            scheduler.step()
         print(seen)
         print('loss: %f' % losses.avg)
         print('train clips/s: %.1f' % (seen / max(time.time() - t_epoch, 1e-9)))

@@ -114,7 +114,10 @@ def save_checkpoint(path, epoch, model, optimizer):
         optimizer.consolidate_state()
     if not multi or dist.get_rank() == 0:
         dir_check(os.path.dirname(path))
-        torch.save({'epoch': epoch, 'state_dict': model.state_dict(), 'optimizer': optimizer.state_dict()}, path)
+        ck = {'epoch': epoch, 'state_dict': model.state_dict(), 'optimizer': optimizer.state_dict()}
+        if len(getattr(optimizer, 'param_groups', ())) > 1 and hasattr(optimizer, 'group_names'):
+            ck['param_group_names'] = optimizer.group_names()       # (who is in which group: checkpoint_to_flat needs it)
+        torch.save(ck, path)
     if multi:
         dist.barrier()
 
@@ -142,7 +145,11 @@ def checkpoint_to_flat(ck: dict, model) -> dict:
     'offsets': {name: (offset, numel)}}``.  This is what a host that drives the C ABI without torch modules
      uploads for ``lirec_adam_step`` and the GEMMs.  Optimizer state is optional.  ``'step'`` is the furthest
     parameter's; parameters that have received fewer updates (frozen for a while: torch.optim.Adam keeps a step per parameter)
-    are listed in ``'lags'``: {name: step - its own} -- what ``lirec_adam_step_ranges`` takes per range; absent when all agree."""
+    are listed in ``'lags'``: {name: step - its own} -- what ``lirec_adam_step_ranges`` takes per range; absent when all agree.
+    PARAMETER GROUPS: an optimizer state with more than one group numbers its parameters group by group, so the names of each
+    group's parameters are needed -- ``ck['param_group_names']`` ([[names of group 0], ...]: FusedAdam.group_names(), which
+    ``flat_to_checkpoint`` writes too) -- and the result carries ``'groups'``: [{'lr', 'betas', 'eps', 'weight_decay', 'amsgrad',
+    'names'}, ...], the rows of ``lirec_adam_step_groups``' table and who reads which.  One group: no such key, as ever."""
     sd = ck['state_dict']
     names = [n for n, _ in model.named_parameters()]
     if list(sd.keys()) != names:
@@ -160,8 +167,17 @@ def checkpoint_to_flat(ck: dict, model) -> dict:
     if osd and osd.get('state'):
         # torch numbers optimizer state by position in param_groups[*]['params'] = model.parameters() order
         order = [i for g in osd['param_groups'] for i in g['params']]
+        by_group = names
+        if len(osd['param_groups']) > 1:
+            gn = ck.get('param_group_names')
+            if gn is None or [len(x) for x in gn] != [len(g['params']) for g in osd['param_groups']] or \
+                    sorted(n for x in gn for n in x) != sorted(names):
+                raise ValueError('an optimizer state with %d parameter groups needs ck[\'param_group_names\'] -- the parameter names '
+                                 'of every group, in the groups\' order (FusedAdam.group_names())' % len(osd['param_groups']))
+            by_group = [n for x in gn for n in x]
+            out['groups'] = [dict({k: v for k, v in g.items() if k != 'params'}, names=list(x)) for g, x in zip(osd['param_groups'], gn)]
         steps = {}
-        for idx, k in zip(order, names):
+        for idx, k in zip(order, by_group):
             st = osd['state'].get(idx)
             if st is None:
                 steps[k] = 0          # (a parameter stock Adam never updated has no state)
@@ -179,12 +195,19 @@ def checkpoint_to_flat(ck: dict, model) -> dict:
 
 def flat_to_checkpoint(flat: dict, model, lr=None, weight_decay=None) -> dict:
     """Inverse of ``checkpoint_to_flat``: the reference's ``{'epoch', 'state_dict', 'optimizer'}`` dict, with an
-    optimizer state_dict a stock ``torch.optim.Adam`` over ``model.parameters()`` loads."""
+    optimizer state_dict a stock ``torch.optim.Adam`` over ``model.parameters()`` loads -- with ``flat['groups']``, one built with
+    the same groups (parameters numbered group by group, and ``'param_group_names'`` beside the optimizer state)."""
     from collections import OrderedDict
     names = [n for n, _ in model.named_parameters()]
     pd = dict(model.named_parameters())
     sd, state = OrderedDict(), {}
-    for i, k in enumerate(names):
+    number = {k: i for i, k in enumerate(names)}
+    if flat.get('groups'):
+        number = {k: i for i, k in enumerate(n for g in flat['groups'] for n in g['names'])}
+        if sorted(number) != sorted(names):
+            raise ValueError('flat[\'groups\'] does not name every parameter of the model exactly once')
+    for k in names:
+        i = number[k]
         off, cnt = flat['offsets'][k] if 'offsets' in flat else model._offsets[k]
         shp = pd[k].shape
         sd[k] = flat['params'][off:off + cnt].clone().view(shp)
@@ -193,4 +216,11 @@ def flat_to_checkpoint(flat: dict, model, lr=None, weight_decay=None) -> dict:
     group = {'lr': opt.lr if lr is None else lr, 'betas': (0.9, 0.999), 'eps': 1e-8,
              'weight_decay': opt.weight_decay if weight_decay is None else weight_decay, 'amsgrad': False,
              'params': list(range(len(names)))}
+    if flat.get('groups'):
+        groups, at = [], 0
+        for g in flat['groups']:
+            groups.append(dict({k: v for k, v in g.items() if k != 'names'}, params=list(range(at, at + len(g['names'])))))
+            at += len(g['names'])
+        return {'epoch': int(flat.get('epoch', 0)), 'state_dict': sd, 'optimizer': {'state': state, 'param_groups': groups},
+                'param_group_names': [list(g['names']) for g in flat['groups']]}
     return {'epoch': int(flat.get('epoch', 0)), 'state_dict': sd, 'optimizer': {'state': state, 'param_groups': [group]}}
