@@ -640,7 +640,7 @@ int lirec_set_adam_clip(const float* coef_dev);
  * A table: n_groups <= LIREC_ADAM_MAX_GROUPS rows of lirec_adam_hyper in device memory, 16-byte aligned.
  *
  * lirec_adam_hyper_write: one tiny launch that stores `rows_host` (HOST memory, n_groups rows, copied into the launch by value;
- * the padding is written as zeros) into the table -- an ordinary kernel on `stream`: stream order is all that protects the
+ * `decoupled` as 1.0f / 0, the reserved words as zeros) into the table -- an ordinary kernel on `stream`: stream order is all that protects the
  * launches that read the table, so a table belongs to ONE stream and is written on the stream that reads it.  LIREC_EINVAL before
  * any device call for: a NULL or not 16-byte aligned table, rows_host NULL, n_groups outside 1..8.  The VALUES are not checked.
  *
@@ -656,11 +656,37 @@ int lirec_set_adam_clip(const float* coef_dev);
  * HOST THREAD reads its five values from that device row -- the by-value ones in lirec_fused_adam are ignored -- and computes its
  * bias corrections itself (the bits of lirec_adam_step with step_dev and the row's values).  The pointer is taken when the launch
  * is issued: a recorded launch keeps it, every replay reads the values anew.  NULL (the default): exactly the kernel and the
- * arguments as without this call.  LIREC_EINVAL for a pointer that is not 16-byte aligned. */
+ * arguments as without this call.  LIREC_EINVAL for a pointer that is not 16-byte aligned.
+ *
+ * DECOUPLED WEIGHT DECAY (AdamW; added to ABI 124 without a new number: word 5 of a row was reserved and written as zero, which
+ * reads as "coupled").  A row whose `decoupled` is not 0 is updated, on the ranges of lirec_adam_step_groups that name it and in a
+ * folded update that reads it, by
+ *     d  = (float)(1.0 - (double)lr * (double)weight_decay)          once per range / launch
+ *     g' = g * gscale                                                (no decay term; gscale includes the clip coefficient)
+ *     m' = m + (1 - beta1) * (g' - m);   v' = v * beta2 + ((1 - beta2) * g') * g'
+ *     p' = p * d - step_size * (m' / (sqrtf(v') / bc2_sqrt + eps))
+ * in fp32 in this order, no contraction: torch.optim.AdamW's single-tensor order.  d is exactly 1 when lr weight_decay < 2^-25
+ * (3e-5 x 1e-5, the defaults, is such a case): the decay is then invisible in fp32, as in torch's fp32 mul_.  A launch may mix
+ * coupled and decoupled rows; a row with 0 gives the bits it always gave.  lirec_adam_hyper_write stores the word as 1.0f for any
+ * non-zero host value and as 0 otherwise, the two reserved words as zeros.  THE BY-VALUE LAUNCHES (lirec_adam_step,
+ * lirec_adam_step_counted, lirec_adam_step_ranges, the by-value fields of lirec_fused_adam) KNOW THE COUPLED FORM ONLY: a caller
+ * who wants AdamW uses lirec_adam_step_groups with a table of one row.
+ *
+ * lirec_set_adam_hyper_map(table_dev, ranges, count): ONE ROW PER PARAMETER in a folded update.  While count > 0, a folded update
+ * issued by the calling host thread looks up, per workgroup, the entry of `ranges` that holds its problem's weight and the one
+ * that holds its bias (offsets in elements from lirec_fused_adam::g, i.e. ranges of the flat layout; `group` = the row of
+ * table_dev), and updates each with its own row -- a first layer whose weights and biases are in different groups keeps the
+ * fold.  `ranges` is HOST memory, copied by the call; at most LIREC_ADAM_MAP_MAX entries (two heads x four segments x weight and
+ * bias); every lag must be 0 (the fold updates with the one global step).  It takes precedence over lirec_set_adam_hyper_row;
+ * count == 0 or table_dev NULL switches it off, and the library then launches what it launched before.  LIREC_EINVAL before any
+ * device call for: a table that is not 16-byte aligned, count outside 0..16, count > 0 with ranges or table NULL, ranges that
+ * overlap or do not ascend, a length < 1, offset + length beyond INT64_MAX, a lag != 0, a group outside 0..7; and from the
+ * folded update itself when a weight or a bias of the call lies in no entry. */
 #define LIREC_ADAM_MAX_GROUPS 8
 typedef struct {
   float lr, beta1, beta2, eps, weight_decay;
-  float reserved_[3];
+  float decoupled;                       /* != 0: AdamW, the decay multiplies p by 1 - lr weight_decay; 0: coupled (L2) */
+  float reserved_[2];
 } lirec_adam_hyper;
 typedef struct {
   int64_t offset, length;                /* elements */
@@ -671,6 +697,8 @@ int lirec_adam_step_groups(float* p, const float* g, float* m, float* v, const l
                            const lirec_adam_hyper* table_dev, int32_t n_groups, int32_t step, float grad_scale,
                            const int64_t* step_dev, int64_t* count_dev, int32_t* ticket, int32_t advance, lirec_stream_t stream);
 int lirec_set_adam_hyper_row(const lirec_adam_hyper* row_dev);
+#define LIREC_ADAM_MAP_MAX 16
+int lirec_set_adam_hyper_map(const lirec_adam_hyper* table_dev, const lirec_adam_group_range* ranges, int32_t count);
 /* `step_dev` (optional, device): when not NULL the 1-based step is read from it by the kernel instead of `step`
  * (bias corrections computed on the device), so that a captured graph advances through the steps.
  * lirec_counter_add: ctr[i] += inc[i] for i < n (n <= 4), one tiny kernel -- the "next step" node of such a graph. */

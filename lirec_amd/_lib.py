@@ -106,7 +106,8 @@ class AdamRange(C.Structure):
 
 class AdamHyper(C.Structure):
     """lirec_adam_hyper: one row of a table of per-group hyper-parameters in device memory (32 bytes)"""
-    _fields_ = [('lr', _f32), ('beta1', _f32), ('beta2', _f32), ('eps', _f32), ('weight_decay', _f32), ('reserved_', _f32 * 3)]
+    _fields_ = [('lr', _f32), ('beta1', _f32), ('beta2', _f32), ('eps', _f32), ('weight_decay', _f32), ('decoupled', _f32),
+                ('reserved_', _f32 * 2)]
 
 
 class AdamGroupRange(C.Structure):
@@ -116,6 +117,7 @@ class AdamGroupRange(C.Structure):
 
 ADAM_MAX_GROUPS = 8           # LIREC_ADAM_MAX_GROUPS
 ADAM_MAX_RANGES = 64
+ADAM_MAP_MAX = 16             # LIREC_ADAM_MAP_MAX: the entries of lirec_set_adam_hyper_map
 CLIP_PARTIALS = 1024          # LIREC_CLIP_PARTIALS: the doubles lirec_grad_sq_partials writes
 
 
@@ -214,6 +216,7 @@ _PROTOS = {
     'lirec_adam_step_groups': (_i32, [_vp, _vp, _vp, _vp, C.POINTER(AdamGroupRange), _i32, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _i32,
                                       _vp]),
     'lirec_set_adam_hyper_row': (_i32, [_vp]),
+    'lirec_set_adam_hyper_map': (_i32, [_vp, C.POINTER(AdamGroupRange), _i32]),
     'lirec_counter_add': (_i32, [_vp, C.POINTER(C.c_int64), _i32, _vp]),
     'lirec_grad_sq_partials': (_i32, [_vp, C.POINTER(AdamRange), _i32, _vp, _vp]),
     'lirec_clip_finalize': (_i32, [_vp, _vp, _i32, _f32, _f32, _vp, _vp]),

@@ -92,33 +92,57 @@ struct AdamFuse {
 };
 // One row of a table of per-group hyper-parameters in device memory (lirec_adam_hyper, include/lirec_hip.h): what the grouped
 // Adam launch and the folded update read where the other launches carry the five values by value.  32 bytes.
+// `decoupled` != 0: the group's weight decay is AdamW's -- p is multiplied by 1 - lr wd and the decay stays out of the gradient
+// (adam4 / adam1 <true>); 0 -- what every table written before the word had a meaning holds -- is the coupled form.
 struct AdamHyperRow {
-  float lr, beta1, beta2, eps, wd, pad_[3];
+  float lr, beta1, beta2, eps, wd, decoupled, pad_[2];
 };
+// One row per first-layer parameter in the folded update (lirec_set_adam_hyper_map): entry i = [off[i], end[i]) of the flat
+// layout (offsets from AdamFuse::g) belongs to row group[i] of the table.  By value in the launch.
+#define ADAM_MAP_MAX 16
+struct AdamHyperMap {
+  long off[ADAM_MAP_MAX], end[ADAM_MAP_MAX];
+  unsigned char group[ADAM_MAP_MAX];
+  int count;
+};
+// the factor of a decoupled group's decay, once per range / launch, in double like the bias corrections; exactly 1 when
+// lr wd < 2^-25 (the decay is then invisible in fp32, as in torch's fp32 mul_)
+__device__ __forceinline__ float adam_decay(const AdamHyperRow& h) { return (float)(1.0 - (double)h.lr * (double)h.wd); }
 // (no floating-point contraction inside: whether the compiler forms an fma here would otherwise depend on the kernel the
 //  function is inlined into, and the two kernels must agree to the bit)
-__device__ __forceinline__ float adam1(const AdamFuse& ad, float step_size, float bc2_sqrt, long off, float g) {
+// DECOUPLED (AdamW; the table route only): no decay term in the gradient, p times `decay` = adam_decay() in front of the step --
+// torch's single-tensor order, param.mul_(1 - lr wd), the moments, addcdiv_.  <false> is the text as it was before the parameter.
+template <bool DECOUPLED = false>
+__device__ __forceinline__ float adam1(const AdamFuse& ad, float step_size, float bc2_sqrt, long off, float g, float decay = 1.f) {
 #pragma clang fp contract(off)
   const float pp = ad.p[off];
-  const float gg = g * ad.gscale + ad.wd * pp;
+  float gg;
+  if constexpr (DECOUPLED) gg = g * ad.gscale;
+  else gg = g * ad.gscale + ad.wd * pp;
   const float mm = ad.m[off] + (1.f - ad.beta1) * (gg - ad.m[off]);
   const float vv = ad.v[off] * ad.beta2 + (1.f - ad.beta2) * gg * gg;
   ad.m[off] = mm; ad.v[off] = vv;
-  const float pn = pp - step_size * (mm / (sqrtf(vv) / bc2_sqrt + ad.eps));
+  float pd = pp;
+  if constexpr (DECOUPLED) pd = pp * decay;
+  const float pn = pd - step_size * (mm / (sqrtf(vv) / bc2_sqrt + ad.eps));
   ad.p[off] = pn;
   return pn;
 }
-__device__ __forceinline__ f32x4 adam4(const AdamFuse& ad, float step_size, float bc2_sqrt, long off, const f32x4 gv) {
+template <bool DECOUPLED = false>
+__device__ __forceinline__ f32x4 adam4(const AdamFuse& ad, float step_size, float bc2_sqrt, long off, const f32x4 gv, float decay = 1.f) {
 #pragma clang fp contract(off)
   f32x4 pv = *reinterpret_cast<const f32x4*>(ad.p + off);
   f32x4 mv = *reinterpret_cast<const f32x4*>(ad.m + off);
   f32x4 vv = *reinterpret_cast<const f32x4*>(ad.v + off);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const float gg = gv[j] * ad.gscale + ad.wd * pv[j];
+    float gg;
+    if constexpr (DECOUPLED) gg = gv[j] * ad.gscale;
+    else gg = gv[j] * ad.gscale + ad.wd * pv[j];
     mv[j] = mv[j] + (1.f - ad.beta1) * (gg - mv[j]);
     vv[j] = vv[j] * ad.beta2 + (1.f - ad.beta2) * gg * gg;
     const float denom = sqrtf(vv[j]) / bc2_sqrt + ad.eps;
+    if constexpr (DECOUPLED) pv[j] = pv[j] * decay;
     pv[j] = pv[j] - step_size * (mv[j] / denom);
   }
   *reinterpret_cast<f32x4*>(ad.p + off) = pv;

@@ -107,8 +107,12 @@ void launch_p2_tng(dim3 grid, hipStream_t s, const GemmGroup& g, int nrep) {
   lirec::launch(HIP_KERNEL_NAME(gemm_p2_tn_kernel<0, true>), grid, dim3(512), 0, s, g, nrep);
 }
 void launch_p2_tn_reduce(int tiles, int grid, hipStream_t s, const GemmGroup& g, int nrep, const AdamFuse* adam,
-                         const AdamHyperRow* row, int step) {
+                         const AdamHyperRow* row, int step, const AdamHyperMap* map) {
   const AdamFuse none{};
+  if (adam && row && map) {        // (`row`: the table the map's groups index)
+    lirec::launch(gemm_p2_tn_reduce_map_kernel, dim3((unsigned)tiles * P2_RED_PARTS), dim3(256), 0, s, g, nrep, grid / nrep, *adam, row, *map, step);
+    return;
+  }
   if (adam && row) lirec::launch(gemm_p2_tn_reduce_row_kernel, dim3((unsigned)tiles * P2_RED_PARTS), dim3(256), 0, s, g, nrep, grid / nrep, *adam, row, step);
   else if (adam) lirec::launch(HIP_KERNEL_NAME(gemm_p2_tn_reduce_kernel<true>), dim3((unsigned)tiles * P2_RED_PARTS), dim3(256), 0, s, g, nrep, grid / nrep, *adam);
   else lirec::launch(HIP_KERNEL_NAME(gemm_p2_tn_reduce_kernel<false>), dim3((unsigned)tiles * P2_RED_PARTS), dim3(256), 0, s, g, nrep, grid / nrep, none);

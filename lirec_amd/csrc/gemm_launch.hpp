@@ -42,7 +42,7 @@ void launch_p3_wgrad(dim3 grid, hipStream_t s, const GemmGroup& g);             
 void launch_p2_nn(dim3 grid, hipStream_t s, const GemmGroup& g, int nrep);      // data gradient through k-major weights (gate dEE)
 void launch_p2_tn(dim3 grid, hipStream_t s, const GemmGroup& g, int nrep);
 void launch_p2_tn_reduce(int tiles, int grid, hipStream_t s, const GemmGroup& g, int nrep, const AdamFuse* adam = nullptr,
-                         const AdamHyperRow* row = nullptr, int step = 0);
+                         const AdamHyperRow* row = nullptr, int step = 0, const AdamHyperMap* map = nullptr);
 #undef LIREC_DECL_LAUNCH
 
 }  // namespace lirec

@@ -1208,5 +1208,8 @@ __global__ __launch_bounds__(512, 2) void gemm_p2_tn_kernel(const GemmGroup g, c
 #define P2_RED_ROW 1
 #include "gemm_p2_reduce.inc"
 #undef P2_RED_ROW
+#define P2_RED_ROW 2
+#include "gemm_p2_reduce.inc"
+#undef P2_RED_ROW
 
 }  // namespace lirec

@@ -1,23 +1,39 @@
-// The body of gemm_p2_tn_reduce_kernel, included twice by gemm_p2.hpp (P2_RED_ROW 0, then 1) -- not a header of its own.
+// The body of gemm_p2_tn_reduce_kernel, included three times by gemm_p2.hpp (P2_RED_ROW 0, 1, 2) -- not a header of its own.
 //   P2_RED_ROW 0: template <bool ADAM> gemm_p2_tn_reduce_kernel, text and code as they always were.
 //   P2_RED_ROW 1: gemm_p2_tn_reduce_row_kernel -- the folded update under device-resident hyper-parameters
 //                 (lirec_set_adam_hyper_row): lr, betas, eps and weight decay come from `row` in device memory, one uniform load
 //                 per workgroup, and the bias corrections are computed here from the row's values, also for the by-value `step`
-//                 (the host cannot pre-compute them from values it does not know).
+//                 (the host cannot pre-compute them from values it does not know).  A row whose `decoupled` word is not 0
+//                 gets the AdamW form of adam4 / adam1 (one workgroup-uniform branch).
+//   P2_RED_ROW 2: gemm_p2_tn_reduce_map_kernel -- the same with ONE ROW PER PARAMETER (lirec_set_adam_hyper_map): the workgroup
+//                 looks the group of its problem's C and the group of its bias up in `map` (ranges of the flat layout, by their
+//                 offsets from ad.g: uniform values), loads those rows of `table` and computes the bias corrections per row.
 // Two kernels from one text, not one device function inlined into both: the launches without the feature keep their symbols,
 // their arguments AND their instructions (an inlined body moved the register allocation of the <true> instantiation).
 #if !P2_RED_ROW
 template <bool ADAM>
 static __global__ __launch_bounds__(256) void gemm_p2_tn_reduce_kernel(const GemmGroup g, const int nrep, const int Gr_, const AdamFuse ad) {
-#else
+#elif P2_RED_ROW == 1
 static __global__ __launch_bounds__(256) void gemm_p2_tn_reduce_row_kernel(const GemmGroup g, const int nrep, const int Gr_, const AdamFuse ad_in,
                                                                            const AdamHyperRow* __restrict__ row, const int step) {
   constexpr bool ADAM = true;
   AdamFuse ad = ad_in;
+  bool decoupled;
+  float decay;
   {
     const AdamHyperRow h = *row;
     ad.lr = h.lr; ad.beta1 = h.beta1; ad.beta2 = h.beta2; ad.eps = h.eps; ad.wd = h.wd;
+    decoupled = h.decoupled != 0.f;
+    decay = adam_decay(h);
   }
+#else
+static __global__ __launch_bounds__(256) void gemm_p2_tn_reduce_map_kernel(const GemmGroup g, const int nrep, const int Gr_, const AdamFuse ad_in,
+                                                                           const AdamHyperRow* __restrict__ table, const AdamHyperMap map,
+                                                                           const int step) {
+  constexpr bool ADAM = true;
+  AdamFuse ad = ad_in, adb = ad_in;        // (the weights' values, the bias's)
+  bool decoupled = false, decoupled_b = false;
+  float decay = 1.f, decay_b = 1.f;
 #endif
   const long Gr = Gr_;
   int tile = blockIdx.x / P2_RED_PARTS;
@@ -38,6 +54,34 @@ static __global__ __launch_bounds__(256) void gemm_p2_tn_reduce_row_kernel(const
   const long ks = p2_tn_ks(p), len = p2_tn_len(p), T = p2_tn_total(g);
   const bool do_db = p.dbias != nullptr && nt == 0 && part == 0;
   float step_size = ad.step_size, bc2_sqrt = ad.bc2_sqrt;
+#if P2_RED_ROW == 2
+  float step_size_b = ad.step_size, bc2_sqrt_b = ad.bc2_sqrt;
+  {
+    // the rows of this problem's weight and of its bias: map entries hold whole parameters, so the first element decides; the
+    // host has checked that both lie in an entry (entry 0 otherwise: a row of the table in any case)
+    const long oc = p.C - ad.g, ob = do_db ? p.dbias - ad.g : -1;
+    int gc = map.group[0], gb = map.group[0];
+    for (int i = 0; i < map.count; ++i) {
+      if (oc >= map.off[i] && oc < map.end[i]) gc = map.group[i];
+      if (ob >= map.off[i] && ob < map.end[i]) gb = map.group[i];
+    }
+    const double t = ad.step_dev ? (double)*ad.step_dev : (double)step;
+    const AdamHyperRow h = table[gc];
+    ad.lr = h.lr; ad.beta1 = h.beta1; ad.beta2 = h.beta2; ad.eps = h.eps; ad.wd = h.wd;
+    decoupled = h.decoupled != 0.f;
+    decay = adam_decay(h);
+    step_size = (float)((double)h.lr / (1.0 - pow((double)h.beta1, t)));
+    bc2_sqrt = (float)sqrt(1.0 - pow((double)h.beta2, t));
+    if (do_db) {
+      const AdamHyperRow hb = table[gb];
+      adb.lr = hb.lr; adb.beta1 = hb.beta1; adb.beta2 = hb.beta2; adb.eps = hb.eps; adb.wd = hb.wd;
+      decoupled_b = hb.decoupled != 0.f;
+      decay_b = adam_decay(hb);
+      step_size_b = (float)((double)hb.lr / (1.0 - pow((double)hb.beta1, t)));
+      bc2_sqrt_b = (float)sqrt(1.0 - pow((double)hb.beta2, t));
+    }
+  }
+#else
   if constexpr (ADAM) {
 #if P2_RED_ROW
     {                       // always here, in double, from the row's values: a by-value step t behaves as step_dev holding t
@@ -50,12 +94,17 @@ static __global__ __launch_bounds__(256) void gemm_p2_tn_reduce_row_kernel(const
       bc2_sqrt = (float)sqrt(1.0 - pow((double)ad.beta2, t));
     }
   }
+#endif
   // what happens to the final gradient of this thread's float4 q at C + e: stored (unless C holds it already), and, ADAM, applied
   auto finish = [&](f32x4* cp, const f32x4 o, bool store) {
     if (store) *cp = o;
     if constexpr (ADAM) {
       const long off = reinterpret_cast<const float*>(cp) - ad.g;
+#if P2_RED_ROW
+      const f32x4 pn = decoupled ? adam4<true>(ad, step_size, bc2_sqrt, off, o, decay) : adam4(ad, step_size, bc2_sqrt, off, o);
+#else
       const f32x4 pn = adam4(ad, step_size, bc2_sqrt, off, o);
+#endif
       if (p.aux_out) {      // the new weights as q32b [M][N] (rows of C): 8 bytes of hi halves, 8 of lo
         const long row = (reinterpret_cast<const float*>(cp) - p.C) / p.ldc, col = (reinterpret_cast<const float*>(cp) - p.C) - row * p.ldc;
         if (ad.wq16c) {     // (single-pass mode: bf16 values, 64-column blocks)
@@ -73,7 +122,15 @@ static __global__ __launch_bounds__(256) void gemm_p2_tn_reduce_row_kernel(const
   auto finish_db = [&](float db, bool store) {
     float* bp = p.dbias + 256 * rep + tid;
     if (store) *bp = db;
+#if P2_RED_ROW == 2
+    if (decoupled_b) (void)adam1<true>(adb, step_size_b, bc2_sqrt_b, bp - ad.g, db, decay_b);
+    else (void)adam1(adb, step_size_b, bc2_sqrt_b, bp - ad.g, db);
+#elif P2_RED_ROW
+    if (decoupled) (void)adam1<true>(ad, step_size, bc2_sqrt, bp - ad.g, db, decay);
+    else (void)adam1(ad, step_size, bc2_sqrt, bp - ad.g, db);
+#else
     if constexpr (ADAM) (void)adam1(ad, step_size, bc2_sqrt, bp - ad.g, db);
+#endif
   };
   long e[P2_RED_Q];
 #pragma unroll

@@ -1751,7 +1751,8 @@ __global__ __launch_bounds__(256) void adam_ranges_clip_kernel(float* __restrict
 // from the launch arguments -- a recorded launch holds the table's address and every replay reads the values anew.  The same work
 // distribution; the row is loaded once per range a workgroup touches, by a workgroup-uniform index.  The bias corrections are
 // ALWAYS computed here, in double, from the row's values -- a by-value step t behaves as step_dev holding t -- so a range gets the
-// bits of adam_kernel with step_dev on it with the row's values.
+// bits of adam_kernel with step_dev on it with the row's values.  A row whose `decoupled` word is not 0 takes the AdamW form of
+// adam4 / adam1 on its ranges (one workgroup-uniform branch beside the row load); a launch may mix the two.
 #define ADAM_MAX_GROUPS 8
 struct AdamGroupRanges {
   long off[ADAM_MAX_RANGES], len[ADAM_MAX_RANGES];
@@ -1780,7 +1781,8 @@ __device__ __forceinline__ void adam_groups_body(float* __restrict__ p, const fl
   const long long t_dev = count_dev ? t_counted : (step_dev ? *step_dev : (long long)step);
   AdamFuse ad{p, g, m, v, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, gscale, 0.f, step_dev};
   int cur = -1;
-  float step_size = 0.f, bc2_sqrt = 1.f;
+  float step_size = 0.f, bc2_sqrt = 1.f, decay = 1.f;
+  bool decoupled = false;       // (of the current range's row: workgroup-uniform)
   for (long wb = blockIdx.x; wb < nblocks; wb += gridDim.x) {
     long b = wb;
     int r = 0;
@@ -1793,6 +1795,8 @@ __device__ __forceinline__ void adam_groups_body(float* __restrict__ p, const fl
       cur = r;
       const AdamHyperRow h = table[rt.group[r]];
       ad.lr = h.lr; ad.beta1 = h.beta1; ad.beta2 = h.beta2; ad.eps = h.eps; ad.wd = h.wd;
+      decoupled = h.decoupled != 0.f;
+      decay = adam_decay(h);
       long long tr = t_dev - rt.lag[r];
       if (tr < 1) tr = 1;
       step_size = (float)((double)h.lr / (1.0 - pow((double)h.beta1, (double)tr)));
@@ -1803,7 +1807,13 @@ __device__ __forceinline__ void adam_groups_body(float* __restrict__ p, const fl
     if (left > ADAM_RANGE_BLOCK) left = ADAM_RANGE_BLOCK;
     const long e = 4L * threadIdx.x;
     const long at = rt.off[r] + first + e;
-    if (e + 4 <= left) {
+    if (decoupled) {
+      if (e + 4 <= left) {
+        (void)adam4<true>(ad, step_size, bc2_sqrt, at, *reinterpret_cast<const f32x4*>(g + at), decay);
+      } else {
+        for (long j = 0; e + j < left; ++j) (void)adam1<true>(ad, step_size, bc2_sqrt, at + j, g[at + j], decay);
+      }
+    } else if (e + 4 <= left) {
       (void)adam4(ad, step_size, bc2_sqrt, at, *reinterpret_cast<const f32x4*>(g + at));
     } else {
       for (long j = 0; e + j < left; ++j) (void)adam1(ad, step_size, bc2_sqrt, at + j, g[at + j]);

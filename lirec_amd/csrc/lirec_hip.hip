@@ -146,6 +146,10 @@ static thread_local const float* t_adam_clip = nullptr;
 // The device row a folded first-layer update issued by this host thread reads its five hyper-parameters from
 // (lirec_set_adam_hyper_row), NULL = off: the values of lirec_fused_adam, by value, and today's kernel.  Per host thread, as above.
 static thread_local const lirec_adam_hyper* t_adam_hyper_row = nullptr;
+// ... or one row PER FIRST-LAYER PARAMETER (lirec_set_adam_hyper_map): the table and the ranges of the flat layout with their
+// groups; count 0 = off.  Takes precedence over the single row.  Per host thread.
+static thread_local const lirec_adam_hyper* t_adam_map_table = nullptr;
+static thread_local AdamHyperMap t_adam_map = {};
 // While the mode is on, every weight / bias gradient target that is handed to a launch is noted: a parameter written by TWO
 // launches of one step (a tied module, a gradient cut over several launches) would silently lose the first contribution -- the
 // caller that switches the mode on asks for the count of such targets afterwards (lirec_grad_overwrite_conflicts) and keeps
@@ -727,6 +731,18 @@ static int launch_p2(GemmGroup& g0, hipStream_t s, int site, const int* nt_bound
     if (g.nprob != g0.nprob) return LIREC_EINVAL;                // (a problem was dropped as empty: its parameters would miss the update)
     const int rc = fused_adam_fill(adam, g, af);
     if (rc) return rc;
+    if (t_adam_map.count > 0) {
+      // (one row per parameter: every weight and every bias of the call lies inside an entry of the map -- the kernel takes
+      //  the row of the entry it finds them in)
+      auto inside = [&](const float* q, long n) {
+        const long o = (long)(q - adam->g);
+        for (int i = 0; i < t_adam_map.count; ++i)
+          if (o >= t_adam_map.off[i] && o + n <= t_adam_map.end[i]) return true;
+        return false;
+      };
+      for (int i = 0; i < g.nprob; ++i)
+        if (!inside(g.p[i].C, (long)g.p[i].M * g.p[i].N) || (g.p[i].dbias && !inside(g.p[i].dbias, g.p[i].M))) return LIREC_EINVAL;
+    }
   } else if (LAYOUT == L_TN) {
     for (int i = 0; i < g.nprob; ++i) g.p[i].aux_out = nullptr;
   }
@@ -765,7 +781,10 @@ static int launch_p2(GemmGroup& g0, hipStream_t s, int site, const int* nt_bound
     // bytes: at most two partial tiles per workgroup read, every output tile written once
     const int pr = prof_start(PS_EMBED_DW1_RED, s);
     // (device-resident hyper-parameters: the row kernel, which computes the bias corrections itself from the step it is given)
-    if (adam && t_adam_hyper_row)
+    if (adam && t_adam_map.count > 0)
+      launch_p2_tn_reduce(tiles, G, s, g, nrep, &af, reinterpret_cast<const AdamHyperRow*>(t_adam_map_table), adam->step < 1 ? 1 : adam->step,
+                          &t_adam_map);
+    else if (adam && t_adam_hyper_row)
       launch_p2_tn_reduce(tiles, G, s, g, nrep, &af, reinterpret_cast<const AdamHyperRow*>(t_adam_hyper_row), adam->step < 1 ? 1 : adam->step);
     else
       launch_p2_tn_reduce(tiles, G, s, g, nrep, adam ? &af : nullptr);
@@ -2481,7 +2500,8 @@ int lirec_adam_hyper_write(lirec_adam_hyper* table_dev, const lirec_adam_hyper* 
   for (int i = 0; i < n_groups; ++i) {
     const lirec_adam_hyper& r = rows_host[i];
     float* q = w.w + 8 * i;
-    q[0] = r.lr; q[1] = r.beta1; q[2] = r.beta2; q[3] = r.eps; q[4] = r.weight_decay;       // (the padding words: zeros)
+    q[0] = r.lr; q[1] = r.beta1; q[2] = r.beta2; q[3] = r.eps; q[4] = r.weight_decay;
+    q[5] = r.decoupled != 0.f ? 1.f : 0.f;                                                   // (the two reserved words: zeros)
   }
   lirec::launch(adam_hyper_write_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<float*>(table_dev), w,
                 (int)(8 * n_groups));
@@ -2531,6 +2551,27 @@ int lirec_adam_step_groups(float* p, const float* g, float* m, float* v, const l
 int lirec_set_adam_hyper_row(const lirec_adam_hyper* row_dev) {
   if (reinterpret_cast<uintptr_t>(row_dev) & 15) return LIREC_EINVAL;
   t_adam_hyper_row = row_dev;
+  return LIREC_OK;
+}
+
+int lirec_set_adam_hyper_map(const lirec_adam_hyper* table_dev, const lirec_adam_group_range* ranges, int32_t count) {
+  static_assert(LIREC_ADAM_MAP_MAX == ADAM_MAP_MAX, "the header's number of map entries is the kernels'");
+  if (reinterpret_cast<uintptr_t>(table_dev) & 15) return LIREC_EINVAL;
+  if (count < 0 || count > LIREC_ADAM_MAP_MAX || (count > 0 && (!ranges || !table_dev))) return LIREC_EINVAL;
+  AdamHyperMap mp;
+  memset(&mp, 0, sizeof(mp));
+  int64_t end = 0;                                             // ascending, disjoint
+  for (int r = 0; r < count; ++r) {
+    const lirec_adam_group_range& q = ranges[r];
+    if (q.length < 1 || q.offset < 0 || q.offset < end || q.lag != 0) return LIREC_EINVAL;
+    if (q.length > INT64_MAX - q.offset) return LIREC_EINVAL;                  // (offset + length would wrap)
+    if (q.group < 0 || q.group >= LIREC_ADAM_MAX_GROUPS) return LIREC_EINVAL;
+    end = q.offset + q.length;
+    mp.off[r] = (long)q.offset; mp.end[r] = (long)end; mp.group[r] = (unsigned char)q.group;
+  }
+  mp.count = table_dev ? count : 0;
+  t_adam_map = mp;
+  t_adam_map_table = mp.count ? table_dev : nullptr;
   return LIREC_OK;
 }
 

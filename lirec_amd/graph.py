@@ -243,11 +243,10 @@ class RecordedTrainStep:
                           and getattr(model, '_has_ints', False) and getattr(model, '_has_ctx', False)
                           and hasattr(optimizer, 'arm_first_layer_update') and hasattr(model, 'refresh_w1q') and not clipping)
         if self.fused and getattr(optimizer, 'device_hyper', False):
-            # (parameter groups: the folded update reads ONE row of the hyper-parameter table -- the first layers in one group, all
-            #  trainable and up to date, or frozen altogether)
+            # (parameter groups: the folded update reads one row of the hyper-parameter table per first-layer parameter -- all of
+            #  them trainable and up to date, in one group or several, or frozen altogether)
             lo, hi, _ = model.first_layer_range()
-            rs = optimizer.trainable_ranges(lo, hi)
-            if rs and not (len(rs) == 1 and rs[0][:3] == (lo, hi, 0)):
+            if optimizer.trainable_ranges(lo, hi) and optimizer.first_layer_fold_ranges() is None:
                 self.fused = False
         elif self.fused and hasattr(optimizer, 'trainable_ranges') and not optimizer.all_trainable():
             # (first layers PARTLY trainable, or behind: the optimiser does not arm the fused update -- the ordinary update writes no
@@ -390,6 +389,8 @@ class RecordedTrainStep:
         parameter is frozen or behind, the requires_grad flags and the trainable parameters' lags: they decided which launches
         were recorded and are in the recorded lirec_adam_step_ranges tables (FusedAdam.frozen_key)"""
         g = optimizer.param_groups[0]
+        if hasattr(optimizer, 'resolve_device_hyper'):
+            optimizer.resolve_device_hyper()      # (a group made decoupled since: the table route, i.e. another key -- or a ValueError)
         if getattr(optimizer, 'device_hyper', False):
             # (the hyper-parameters live in device tables the recorded launches hold by ADDRESS -- FusedAdam.sync_hyper writes what
             #  changed in front of a replay --; what is baked in is which group a range reads: the membership)

@@ -885,6 +885,8 @@ class _HotPathModule(nn.Module):
         adam = self.__dict__.pop('_dw1_adam', None)
         # (... reading its hyper-parameters from this device row -- FusedAdam with device_hyper -- or, None, carrying them by value)
         hyper_row = self.__dict__.pop('_dw1_hyper_row', None)
+        # (... or one row per first-layer parameter: (table, [(offset, length, group)]) -- the first layers span several groups)
+        hyper_map = self.__dict__.pop('_dw1_hyper_map', None)
         if want_dx:
             adam = None          # (the features' gradient reads the first-layer weights after the tail: no update folded into it)
         if adam is not None and not (has_i and has_c and pieces is None and st.get('planes_i') is not None
@@ -972,7 +974,8 @@ class _HotPathModule(nn.Module):
         else:
             # (data parallel or not: both heads' tails share their launches -- the first-layer weight gradients of the two
             #  heads are ONE persistent launch, so their bucket is announced once, at the end)
-            with ops.adam_hyper_row(hyper_row if adam is not None else None):
+            with ops.adam_hyper_row(hyper_row if adam is not None else None), \
+                    ops.adam_hyper_map(*(hyper_map if adam is not None and hyper_map is not None else (None,))):
                 run(2)
         dX = None
         if want_dx:
@@ -1632,7 +1635,8 @@ def create_model(n_classes, n_rels=0, verbose=False):
     else:
         loss = MultiTaskMaxMargin(n_rels=n_rels) if opt.rels_multitask else MaxMarginCrossEntropyLoss()
 
-    optimizer = FusedAdam(model, lr=opt.lr, weight_decay=opt.weight_decay, max_grad_norm=getattr(opt, 'clip_grad_norm', 0.0) or None)
+    optimizer = FusedAdam(model, lr=opt.lr, weight_decay=opt.weight_decay, max_grad_norm=getattr(opt, 'clip_grad_norm', 0.0) or None,
+                          decoupled_weight_decay=bool(getattr(opt, 'decoupled_weight_decay', False)))
     if verbose:
         print(str(model))
         for name, param in model.named_parameters():

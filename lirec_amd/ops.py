@@ -742,12 +742,15 @@ def adam_step_ranges(p, g, m, v, ranges, step, lr, beta1, beta2, eps, weight_dec
 
 def adam_hyper_write(table, rows):
     """lirec_adam_hyper_write: ``table`` (device float32, 8 words a row, 16-byte aligned) takes ``rows`` =
-    [(lr, beta1, beta2, eps, weight_decay), ...] (1..8), by one tiny launch on the current stream -- the stream that reads it"""
+    [(lr, beta1, beta2, eps, weight_decay[, decoupled]), ...] (1..8; a row of five is a coupled one), by one tiny launch on the
+    current stream -- the stream that reads it"""
     from ._lib import AdamHyper
     assert table.dtype == torch.float32 and table.is_contiguous() and table.numel() >= 8 * len(rows)
     arr = (AdamHyper * max(len(rows), 1))()
-    for a, (lr, b1, b2, eps, wd) in zip(arr, rows):
+    for a, row in zip(arr, rows):
+        lr, b1, b2, eps, wd = row[:5]
         a.lr, a.beta1, a.beta2, a.eps, a.weight_decay = float(lr), float(b1), float(b2), float(eps), float(wd)
+        a.decoupled = 1.0 if len(row) > 5 and row[5] else 0.0
     check(lib().lirec_adam_hyper_write(_p(table), arr, len(rows), _stream()), 'lirec_adam_hyper_write')
 
 
@@ -785,6 +788,30 @@ class adam_hyper_row:
     def __exit__(self, *exc):
         if self.row is not None:
             check(lib().lirec_set_adam_hyper_row(None), 'lirec_set_adam_hyper_row')
+        return False
+
+
+class adam_hyper_map:
+    """``with ops.adam_hyper_map(table, ranges):`` -- a folded first-layer update this host thread issues inside takes ONE ROW PER
+    PARAMETER: ``ranges`` = [(offset, length, group), ...] of the flat layout (at most 16), ``table`` the device table the groups
+    index (lirec_set_adam_hyper_map); cleared on the way out.  ``table`` None: nothing is set."""
+
+    def __init__(self, table, ranges=()):
+        self.table, self.ranges = table, list(ranges)
+
+    def __enter__(self):
+        if self.table is not None:
+            from ._lib import AdamGroupRange
+            assert self.table.dtype == torch.float32
+            arr = (AdamGroupRange * max(len(self.ranges), 1))()
+            for a, (o, k, grp) in zip(arr, self.ranges):
+                a.offset, a.length, a.lag, a.group = int(o), int(k), 0, int(grp)
+            check(lib().lirec_set_adam_hyper_map(_p(self.table), arr, len(self.ranges)), 'lirec_set_adam_hyper_map')
+        return self
+
+    def __exit__(self, *exc):
+        if self.table is not None:
+            check(lib().lirec_set_adam_hyper_map(None, None, 0), 'lirec_set_adam_hyper_map')
         return False
 
 

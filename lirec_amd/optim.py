@@ -36,6 +36,17 @@ stream, the collectives' early stream), each written only on the stream that rea
 Adam launch of step t running into step t + 1, and a write from the main stream would hand part of that launch the next step's
 values.  ``device_hyper=None`` is on with more than one group and off with one; off with one group is the by-value code path,
 launch for launch.  The groups are fixed at construction (the flat layout is): ``add_param_group`` raises afterwards.
+
+Decoupled weight decay -- AdamW -- per group (``decoupled_weight_decay``, torch's key: ``torch.optim.AdamW`` is
+``torch.optim.Adam`` with it set): p is multiplied by (float)(1 - lr wd) in front of the step and the decay stays out of the
+gradient, hence out of the moments and of a clipped norm's reach (the clip scales g only); a frozen parameter gets no decay.  The
+flag is a TABLE value like lr (word 5 of a group's row): a decoupled group needs ``device_hyper`` -- ``None`` resolves to on with
+any decoupled group, an explicit ``False`` with one is a ValueError -- ``sync_hyper()`` sends a change, a recorded step follows it.
+The by-value launches know the coupled form only.  1 - lr wd is exactly 1 in fp32 when lr wd < 2^-25: with the reference's
+defaults (3e-5 x 1e-5) decoupled decay does nothing, here as in torch's fp32 ``mul_``.  ``state_dict()`` goes to
+``torch.optim.AdamW`` / ``torch.optim.Adam(decoupled_weight_decay=True)`` with the same groups and back.  Under ``device_hyper``
+the first-layer update stays folded into the backward (``arm_first_layer_update``) when the first layers span SEVERAL groups --
+weights that decay, biases that do not --: each parameter then reads the row of its own group (``lirec_set_adam_hyper_map``).
 """
 from __future__ import annotations
 
@@ -65,7 +76,7 @@ class FusedAdam(torch.optim.Optimizer):
             raise ValueError('Invalid weight_decay value: {}'.format(weight_decay))
 
     def __init__(self, model, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5, max_grad_norm=None, param_groups=None,
-                 device_hyper=None, amsgrad=False):
+                 device_hyper=None, amsgrad=False, decoupled_weight_decay=False):
         self.model = model
         params = list(model.parameters())
         self._names = [n for n, _ in model.named_parameters()]        # (in the order of model._plist)
@@ -74,7 +85,9 @@ class FusedAdam(torch.optim.Optimizer):
         self._check_values(lr, betas, eps, weight_decay)
         # (amsgrad: part of torch.optim.Adam's param_groups since torch 1.1 -- the reference's pin -- so that an
         #  optimizer state_dict saved here has the keys a stock Adam expects, and the other way round)
-        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False)
+        # (decoupled_weight_decay: torch.optim.Adam's key since torch 2.x -- what makes a group AdamW)
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
+                        decoupled_weight_decay=bool(decoupled_weight_decay))
         if param_groups is None:
             super().__init__(params, defaults)
         else:
@@ -90,7 +103,10 @@ class FusedAdam(torch.optim.Optimizer):
         if many and device_hyper is not None and not device_hyper:
             raise ValueError('FusedAdam: %d parameter groups need device_hyper (by value the launches carry one set of '
                              'hyper-parameters)' % len(self.param_groups))
+        self._device_hyper_arg = None if device_hyper is None else bool(device_hyper)     # (None: left to default)
         self.device_hyper = many if device_hyper is None else bool(device_hyper)
+        self._ranges_key = self._ranges = None
+        self.resolve_device_hyper()    # (a decoupled group: on, or a ValueError for an explicit False)
         self._tables = {}              # issuing stream ('main', 'side', 'early') -> [device float32[64], the rows it last received]
         self._m = self._v = None
         self._step = 0
@@ -98,11 +114,23 @@ class FusedAdam(torch.optim.Optimizer):
         self._step_dev = None          # device int64[1]: the step kept on the GPU (lirec_amd.graph)
         self._step_side_dev = None     # device int64[1]: the same as the weight-gradient side stream counts it (step(): side update)
         self._lag = {}                 # parameter name -> updates it sat out frozen (missing = 0): state[p]['step'] = _step - lag
-        self._ranges_key = self._ranges = None
         self.max_grad_norm = max_grad_norm      # None / 0: no clipping; settable between steps (a recorded step is recorded again)
         self._clip_out = None          # device float32[2]: (clip coefficient, gradient norm) of the last clipped step
 
     # -- parameter groups -------------------------------------------------------
+    def resolve_device_hyper(self):
+        """A decoupled group needs the table route (the by-value launches have no such form).  Called by the constructor,
+        ``hyper_rows()``, ``step()``, ``load_state_dict()`` and the recorded step's key: with ``device_hyper`` left to default in the
+        constructor it is switched on from here on (a step recorded by value then refuses to replay: its key changed); with an
+        explicit ``device_hyper=False`` this raises.  Returns ``device_hyper``."""
+        if not self.device_hyper and any(g.get('decoupled_weight_decay') for g in self.param_groups):
+            if self._device_hyper_arg is not None:
+                raise ValueError('FusedAdam: a group with decoupled_weight_decay needs device_hyper (the by-value launches know '
+                                 'coupled weight decay only), and device_hyper=False was asked for')
+            self.device_hyper = True
+            self._ranges_key = None
+        return self.device_hyper
+
     def _resolve_groups(self, param_groups, params):
         """the constructor's ``param_groups`` with names replaced by the parameter objects; every parameter of the model in
         exactly one group, at most MAX_GROUPS groups"""
@@ -151,12 +179,14 @@ class FusedAdam(torch.optim.Optimizer):
         return [[name_of[id(p)] for p in grp['params']] for grp in self.param_groups]
 
     def hyper_rows(self):
-        """(lr, beta1, beta2, eps, weight_decay) of every group as ``param_groups`` has them now, checked as at construction"""
+        """(lr, beta1, beta2, eps, weight_decay, decoupled) of every group as ``param_groups`` has them now, checked as at
+        construction (a decoupled group with ``device_hyper=False``: ValueError)"""
+        self.resolve_device_hyper()
         rows = []
         for grp in self.param_groups:
             lr, betas, eps, wd = float(grp['lr']), (float(grp['betas'][0]), float(grp['betas'][1])), float(grp['eps']), float(grp['weight_decay'])
             self._check_values(lr, betas, eps, wd)
-            rows.append((lr, betas[0], betas[1], eps, wd))
+            rows.append((lr, betas[0], betas[1], eps, wd, bool(grp.get('decoupled_weight_decay', False))))
         return tuple(rows)
 
     def _issuing_streams(self):
@@ -181,7 +211,7 @@ class FusedAdam(torch.optim.Optimizer):
         differs -- one lirec_adam_hyper_write per stale table, ON THE STREAM THAT READS IT (``main``: the raw handle of the stream
         the caller's Adam launches go to, None = the current one); nothing otherwise.  Returns the number of writes issued.
         Never inside a recording: a command list holds the tables' addresses, not their values."""
-        if not self.device_hyper:
+        if not self.resolve_device_hyper():
             return 0
         rows = self.hyper_rows()
         stale = [(role, h) for role, h in self._issuing_streams().items() if self._tables.get(role, (None, None))[1] != rows]
@@ -316,16 +346,19 @@ class FusedAdam(torch.optim.Optimizer):
             return False
         if self._clip_max() is not None:
             return False          # (the norm needs the finished first-layer gradients: they are updated with the rest, clipped)
-        row = None
-        if self.device_hyper:
-            # (... and all of them in ONE group: the launch reads one row -- of the table of the stream that runs the backward's tail)
-            lo, hi, _ = m.first_layer_range()
-            rs = self.trainable_ranges(lo, hi)
-            if len(rs) != 1 or rs[0][:3] != (lo, hi, 0):
+        row = hmap = None
+        if self.resolve_device_hyper():
+            # (every first-layer parameter trainable and up to date.  All of them in ONE group: the launch reads one row -- of the
+            #  table of the stream that runs the backward's tail; in several: that table and the ranges with their groups)
+            rs = self.first_layer_fold_ranges()
+            if rs is None:
                 return False
             self.sync_hyper()
             self._rows_now = self.hyper_rows()
-            row = self._table('main')[8 * rs[0][3]:8 * rs[0][3] + 8]
+            if len(rs) == 1:
+                row = self._table('main')[8 * rs[0][3]:8 * rs[0][3] + 8]
+            else:
+                hmap = (self._table('main'), [(a, b - a, grp) for a, b, _, grp in rs])
         elif not self.all_trainable():
             # (the fused launch updates EVERY first-layer parameter of the call with the one global step: only when each of them
             #  is trainable and has received every update so far)
@@ -344,7 +377,24 @@ class FusedAdam(torch.optim.Optimizer):
             m._dw1_hyper_row = row          # (the five values above are then ignored: lirec_set_adam_hyper_row)
         else:
             m.__dict__.pop('_dw1_hyper_row', None)
+        if hmap is not None:
+            m._dw1_hyper_map = hmap         # (... and each parameter reads the row of its group: lirec_set_adam_hyper_map)
+        else:
+            m.__dict__.pop('_dw1_hyper_map', None)
         return True
+
+    def first_layer_fold_ranges(self):
+        """Under ``device_hyper``: the ranges (start, end, 0, group) of the first-layer bucket when the folded update can take it
+        -- every first-layer parameter trainable with lag 0, in at most 16 ranges (one range: one group) -- or None"""
+        from ._lib import ADAM_MAP_MAX
+        m = self.model
+        lo, hi, _ = m.first_layer_range()
+        rs = self.trainable_ranges(lo, hi)
+        inside = [n for n, (off, k) in m._offsets.items() if lo <= off < hi]
+        flags = dict(zip(self._names, self._flags()))
+        if not rs or len(rs) > ADAM_MAP_MAX or any(r[2] != 0 for r in rs) or not all(flags[n] for n in inside):
+            return None
+        return rs
 
     # -- frozen parameters ------------------------------------------------------
     def _flags(self):
@@ -469,7 +519,7 @@ class FusedAdam(torch.optim.Optimizer):
         self._ensure_state()
         self._all_live = self.all_trainable()
         grp = self.param_groups[0]
-        if self.device_hyper:
+        if self.resolve_device_hyper():
             # (the tables as param_groups has them now; inside a recording they must be current already -- sync_hyper raises)
             self.sync_hyper()
             self._rows_now = self.hyper_rows()
@@ -676,7 +726,14 @@ class FusedAdam(torch.optim.Optimizer):
     def load_state_dict(self, state_dict):
         if any(g.get('amsgrad') for g in state_dict.get('param_groups', ())):
             raise ValueError('FusedAdam: amsgrad checkpoints are not supported (the reference never sets it, mlp/model.py:599-601)')
+        if any(g.get('decoupled_weight_decay') for g in state_dict.get('param_groups', ())) and not self.device_hyper \
+                and self._device_hyper_arg is not None:
+            raise ValueError('FusedAdam.load_state_dict: the state has groups with decoupled_weight_decay (AdamW), which need '
+                             'device_hyper, and device_hyper=False was asked for')
         super().load_state_dict(state_dict)
+        for grp in self.param_groups:        # (a state written before the key existed: coupled)
+            grp.setdefault('decoupled_weight_decay', False)
+        self.resolve_device_hyper()          # (decoupled groups switch the table route on)
         steps = [float(st['step']) for st in self.state.values() if 'step' in st]
         self._step = int(max(steps)) if steps else 0
         # (one step per parameter, as torch.optim.Adam keeps it: the ones behind the furthest carry the difference as their lag;

@@ -149,7 +149,9 @@ def checkpoint_to_flat(ck: dict, model) -> dict:
     PARAMETER GROUPS: an optimizer state with more than one group numbers its parameters group by group, so the names of each
     group's parameters are needed -- ``ck['param_group_names']`` ([[names of group 0], ...]: FusedAdam.group_names(), which
     ``flat_to_checkpoint`` writes too) -- and the result carries ``'groups'``: [{'lr', 'betas', 'eps', 'weight_decay', 'amsgrad',
-    'names'}, ...], the rows of ``lirec_adam_step_groups``' table and who reads which.  One group: no such key, as ever."""
+    'names'}, ...], the rows of ``lirec_adam_step_groups``' table and who reads which (``'decoupled_weight_decay'`` among the
+    keys when the state has it).  One group: no such key, as ever -- and ``'decoupled_weight_decay': True`` ONLY when the one
+    group is decoupled (AdamW): the update rule is then another, and the by-value ``lirec_adam_step`` does not have it."""
     sd = ck['state_dict']
     names = [n for n, _ in model.named_parameters()]
     if list(sd.keys()) != names:
@@ -176,6 +178,8 @@ def checkpoint_to_flat(ck: dict, model) -> dict:
                                  'of every group, in the groups\' order (FusedAdam.group_names())' % len(osd['param_groups']))
             by_group = [n for x in gn for n in x]
             out['groups'] = [dict({k: v for k, v in g.items() if k != 'params'}, names=list(x)) for g, x in zip(osd['param_groups'], gn)]
+        elif osd['param_groups'] and osd['param_groups'][0].get('decoupled_weight_decay'):
+            out['decoupled_weight_decay'] = True
         steps = {}
         for idx, k in zip(order, by_group):
             st = osd['state'].get(idx)
@@ -216,6 +220,8 @@ def flat_to_checkpoint(flat: dict, model, lr=None, weight_decay=None) -> dict:
     group = {'lr': opt.lr if lr is None else lr, 'betas': (0.9, 0.999), 'eps': 1e-8,
              'weight_decay': opt.weight_decay if weight_decay is None else weight_decay, 'amsgrad': False,
              'params': list(range(len(names)))}
+    if flat.get('decoupled_weight_decay'):
+        group['decoupled_weight_decay'] = True          # (AdamW: torch.optim.Adam's key; absent = coupled, as ever)
     if flat.get('groups'):
         groups, at = [], 0
         for g in flat['groups']:

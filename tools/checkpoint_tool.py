@@ -49,6 +49,10 @@ def main():
                 print('  %-28s %s' % (k, tuple(v.shape)))
             st = (ck.get('optimizer') or {}).get('state') or {}
             print('optimizer state entries: %d, step %s' % (len(st), sorted({float(s['step']) for s in st.values()})))
+            for i, g in enumerate((ck.get('optimizer') or {}).get('param_groups') or ()):
+                print('  group %d: %d parameters, lr %g, weight_decay %g, %s' % (
+                    i, len(g['params']), g['lr'], g['weight_decay'],
+                    'decoupled (AdamW)' if g.get('decoupled_weight_decay') else 'coupled (L2)'))
         return
     model, _, optim = build_model(a.recipe, a.n_classes, a.n_rels if a.recipe in ('int_rels', 'int_rel_ch') else 0)
     if a.cmd == 'from-flat':
@@ -61,6 +65,8 @@ def main():
     if ck.get('optimizer'):
         optim.load_state_dict(ck['optimizer'])
     print('ok: %d parameters in %d tensors match recipe %s; Adam step %d' % (model._n_params, len(ck['state_dict']), a.recipe, flat['step']))
+    decoupled = [bool(g.get('decoupled_weight_decay')) for g in flat['groups']] if flat.get('groups') else [bool(flat.get('decoupled_weight_decay'))]
+    print('weight decay: %s' % ', '.join('decoupled (AdamW)' if d else 'coupled' for d in decoupled))
     if a.cmd == 'to-flat':
         torch.save(flat, a.dst)
         print('wrote %s (flat extent %d floats)' % (a.dst, flat['params'].numel()))
