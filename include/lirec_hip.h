@@ -631,6 +631,35 @@ int lirec_grad_sq_partials(const float* g, const lirec_adam_range* ranges, int32
 int lirec_clip_finalize(const double* partials, double* sq_dev, int32_t mode, float grad_scale, float max_norm, float* out,
                         lirec_stream_t stream);
 int lirec_set_adam_clip(const float* coef_dev);
+/* ---- skipping non-finite steps, on the device ---------------------------------------
+ * The device-side "found inf -> no-op" of a fused optimiser (apex's noop_flag, torch's _fused_adam(found_inf=)) for callers that
+ * cannot visit the host between backward and update: a step whose gradients hold a NaN or an Inf leaves p, m and v untouched and
+ * does not count as an update for the bias corrections.  Built on the norm above: the double sum of squares of
+ * lirec_grad_sq_partials is non-finite exactly when an element of its ranges is (squares cannot cancel, and the squares of finite
+ * fp32 values cannot overflow a double).  (Added to ABI 124 without a new number: exports only.)
+ *
+ * lirec_clip_finalize_guard (one workgroup): lirec_clip_finalize -- modes, tree and arithmetic, bit for bit -- with
+ *   max_norm == 0   allowed: no clipping, out[0] = 1
+ *   out[2] = skip   1.0f when *sq_dev (the double itself, not norm * grad_scale) is NaN or infinite, 0 otherwise
+ *   count != 0      *skipped_dev += skip (a device int64: the steps skipped so far)
+ * `out`: three device floats (four reserved).  `count` goes on exactly ONE finalize of a step -- the last, behind the all-reduce
+ * under data parallelism.  LIREC_EINVAL before any device call for: sq_dev / out NULL, partials NULL with mode 0 or 1, a mode
+ * outside 0..2, max_norm NaN or negative, count != 0 with skipped_dev NULL, partials / sq_dev / skipped_dev not 8-byte or out not
+ * 4-byte aligned.
+ *
+ * lirec_set_adam_guard(out_dev, skipped_dev): while set, every lirec_adam_step, lirec_adam_step_counted, lirec_adam_step_ranges and
+ * lirec_adam_step_groups launch issued BY THE CALLING HOST THREAD is the guarded kernel: one uniform load of out_dev[2]; set, no
+ * element of p, g, m, v is read or written (the count_dev / ticket / advance epilogue still runs: a counting stream stays in
+ * step); otherwise the update uses the scale grad_scale * out_dev[0] and the step t - *skipped_dev (then - lag per range), clamped
+ * at 1, with the bias corrections ALWAYS computed by the kernel, in double (a by-value step behaves as step_dev holding it): the
+ * bits of the clipped launch with that coefficient and step_dev holding t - *skipped_dev.  Both pointers are taken when the launch
+ * is issued: a recorded launch keeps them, every replay reads them anew.  Host-thread state like lirec_set_adam_clip, over which
+ * it takes precedence.  NULL, NULL (the default): exactly what is launched without this call.  A folded update
+ * (lirec_embed_bwd_args::adam) is REFUSED (LIREC_EINVAL) while a guard is set.  LIREC_EINVAL for: one pointer without the other,
+ * out_dev not 4-byte or skipped_dev not 8-byte aligned. */
+int lirec_clip_finalize_guard(const double* partials, double* sq_dev, int32_t mode, float grad_scale, float max_norm, float* out,
+                              int64_t* skipped_dev, int32_t count, lirec_stream_t stream);
+int lirec_set_adam_guard(const float* out_dev, const int64_t* skipped_dev);
 /* ---- parameter groups: hyper-parameters in device memory ---------------------------
  * torch.optim.Adam's param_groups, and hyper-parameters that change between the replays of a recorded step (a learning-rate
  * schedule): lr, betas, eps and weight_decay live in a small TABLE in device memory, one 32-byte row per group, that the Adam

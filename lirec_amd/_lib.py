@@ -221,6 +221,8 @@ _PROTOS = {
     'lirec_grad_sq_partials': (_i32, [_vp, C.POINTER(AdamRange), _i32, _vp, _vp]),
     'lirec_clip_finalize': (_i32, [_vp, _vp, _i32, _f32, _f32, _vp, _vp]),
     'lirec_set_adam_clip': (_i32, [_vp]),
+    'lirec_clip_finalize_guard': (_i32, [_vp, _vp, _i32, _f32, _f32, _vp, _vp, _i32, _vp]),
+    'lirec_set_adam_guard': (_i32, [_vp, _vp]),
     'lirec_eval_max_tracks': (_i32, [C.POINTER(EvalArgs), _vp]),
     'lirec_cast_f64_f32': (_i32, [_vp, _vp, _i64, _vp]),
     'lirec_grid_pool': (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i64, _vp]),

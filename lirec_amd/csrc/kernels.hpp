@@ -1609,13 +1609,23 @@ __device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __
                                           float step_size, float bc2_sqrt, float beta1, float beta2,
                                           float eps, float wd, float gscale, float lr,
                                           const long long* __restrict__ step_dev,
-                                          long long* count_dev, int* ticket, int advance) {
+                                          long long* count_dev, int* ticket, int advance,
+                                          const float* __restrict__ guard = nullptr,
+                                          const long long* __restrict__ skipped = nullptr, int step = 0) {
+  // guard / skipped / step (adam_guard_kernel; null in the other two kernels, whose code they leave as it was): see there
   // count_dev (lirec_adam_step_counted): a counter of COMPLETED steps owned by this launch's stream -- the step is *count_dev + 1,
   // and, `advance`, the workgroup that finishes last stores it back (every workgroup has read the counter by then: a workgroup
   // takes its ticket behind its last element) -- the one-thread counter launch in front of the side stream's update is gone
   long long t_counted = 0;
   if (count_dev) t_counted = __hip_atomic_load(count_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
-  if (step_dev || count_dev) {        // step kept on the device (graph replay): same double-precision bias corrections as the host
+  if (guard) {                        // guarded: the step less the skipped ones, always from here; a set flag empties the loops
+    if (guard[2] != 0.f) n = 0;
+    long long tg = (count_dev ? t_counted : (step_dev ? *step_dev : (long long)step)) - *skipped;
+    if (tg < 1) tg = 1;
+    step_size = (float)((double)lr / (1.0 - pow((double)beta1, (double)tg)));
+    bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)tg));
+    gscale *= guard[0];
+  } else if (step_dev || count_dev) {        // step kept on the device (graph replay): same double-precision bias corrections as the host
     const double t = count_dev ? (double)t_counted : (double)*step_dev;
     step_size = (float)((double)lr / (1.0 - pow((double)beta1, t)));
     bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, t));
@@ -1657,6 +1667,21 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, c
   adam_body(p, g, m, v, n, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale * *coef, lr, step_dev, count_dev, ticket, advance);
 }
 
+// Guarded (lirec_set_adam_guard): the clipped launch plus the three-word block `guard` = (coefficient, norm, skip) that
+// clip_finalize_guard_kernel wrote and the device count `skipped` of the steps skipped so far -- uniform loads, once per launch.
+// skip != 0: no element is read or written (p, m, v keep their bits); the count_dev / ticket / advance epilogue runs all the same,
+// so a counting stream stays in step.  Otherwise the step is t - *skipped (t: `step` by value, *step_dev or *count_dev + 1),
+// clamped at 1, with the bias corrections ALWAYS computed here, in double -- a by-value step behaves as step_dev holding it --
+// and the scale is gscale * guard[0]: the bits of adam_clip_kernel with that coefficient and step_dev holding t - *skipped.
+__global__ __launch_bounds__(256) void adam_guard_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                         float* __restrict__ m, float* __restrict__ v, long n,
+                                                         float beta1, float beta2, float eps, float wd, float gscale, float lr,
+                                                         int step, const long long* __restrict__ step_dev,
+                                                         long long* count_dev, int* ticket, int advance,
+                                                         const float* __restrict__ guard, const long long* __restrict__ skipped) {
+  adam_body(p, g, m, v, n, 0.f, 0.f, beta1, beta2, eps, wd, gscale, lr, step_dev, count_dev, ticket, advance, guard, skipped, step);
+}
+
 // The same update over a scattered set of ranges of the flat buffers in ONE launch (lirec_adam_step_ranges: the trainable
 // parameters of a partly frozen model).  Range r = [off[r], off[r] + len[r]) with off a multiple of 4, updated with step t - lag[r]:
 // a parameter that sat out `lag` steps frozen has received that many updates fewer (torch.optim.Adam keeps one step per
@@ -1680,11 +1705,16 @@ __device__ __forceinline__ void adam_ranges_body(float* __restrict__ p, const fl
                                                  float* __restrict__ m, float* __restrict__ v, const AdamRanges& rt,
                                                  long nblocks, float beta1, float beta2, float eps, float wd,
                                                  float gscale, float lr, const long long* __restrict__ step_dev,
-                                                 long long* count_dev, int* ticket, int advance) {
+                                                 long long* count_dev, int* ticket, int advance,
+                                                 const float* __restrict__ guard = nullptr,
+                                                 const long long* __restrict__ skipped = nullptr, int step = 0) {
   long long t_counted = 0;
   if (count_dev) t_counted = __hip_atomic_load(count_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
-  const bool dev_step = step_dev || count_dev;
-  const long long t_dev = count_dev ? t_counted : (step_dev ? *step_dev : 0);
+  // (guarded -- adam_ranges_guard_kernel; as adam_guard_kernel -- : the device-step branch below with t less the skipped steps,
+  //  a by-value step included; a set flag ends the block loop before it begins)
+  const bool dev_step = step_dev || count_dev || guard;
+  long long t_dev = count_dev ? t_counted : (step_dev ? *step_dev : (long long)step);
+  if (guard) { t_dev -= *skipped; gscale *= guard[0]; if (guard[2] != 0.f) nblocks = 0; }
   const AdamFuse ad{p, g, m, v, 0.f, 0.f, beta1, beta2, eps, wd, gscale, lr, step_dev};
   int cur = -1;
   float step_size = 0.f, bc2_sqrt = 1.f;
@@ -1746,6 +1776,18 @@ __global__ __launch_bounds__(256) void adam_ranges_clip_kernel(float* __restrict
   adam_ranges_body(p, g, m, v, rt, nblocks, beta1, beta2, eps, wd, gscale * *coef, lr, step_dev, count_dev, ticket, advance);
 }
 
+// ... guarded: as adam_guard_kernel (rt.step_size / rt.bc2_sqrt are not read)
+__global__ __launch_bounds__(256) void adam_ranges_guard_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                float* __restrict__ m, float* __restrict__ v, const AdamRanges rt,
+                                                                long nblocks, float beta1, float beta2, float eps, float wd,
+                                                                float gscale, float lr, int step,
+                                                                const long long* __restrict__ step_dev, long long* count_dev,
+                                                                int* ticket, int advance, const float* __restrict__ guard,
+                                                                const long long* __restrict__ skipped) {
+  adam_ranges_body(p, g, m, v, rt, nblocks, beta1, beta2, eps, wd, gscale, lr, step_dev, count_dev, ticket, advance, guard, skipped,
+                   step);
+}
+
 // Parameter groups (lirec_adam_step_groups): adam_ranges_kernel with a group index per range and the five hyper-parameters of a
 // range taken from row `group` of a table in DEVICE memory (AdamHyperRow, written by adam_hyper_write_kernel in stream order), not
 // from the launch arguments -- a recorded launch holds the table's address and every replay reads the values anew.  The same work
@@ -1775,10 +1817,12 @@ __device__ __forceinline__ void adam_groups_body(float* __restrict__ p, const fl
                                                  float* __restrict__ m, float* __restrict__ v, const AdamGroupRanges& rt,
                                                  long nblocks, const AdamHyperRow* __restrict__ table, int step, float gscale,
                                                  const long long* __restrict__ step_dev, long long* count_dev, int* ticket,
-                                                 int advance) {
+                                                 int advance, const float* __restrict__ guard = nullptr,
+                                                 const long long* __restrict__ skipped = nullptr) {
   long long t_counted = 0;
   if (count_dev) t_counted = __hip_atomic_load(count_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
-  const long long t_dev = count_dev ? t_counted : (step_dev ? *step_dev : (long long)step);
+  long long t_dev = count_dev ? t_counted : (step_dev ? *step_dev : (long long)step);
+  if (guard) { t_dev -= *skipped; gscale *= guard[0]; if (guard[2] != 0.f) nblocks = 0; }      // (guarded: as adam_guard_kernel)
   AdamFuse ad{p, g, m, v, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, gscale, 0.f, step_dev};
   int cur = -1;
   float step_size = 0.f, bc2_sqrt = 1.f, decay = 1.f;
@@ -1845,6 +1889,17 @@ __global__ __launch_bounds__(256) void adam_groups_clip_kernel(float* __restrict
                                                                long long* count_dev, int* ticket, int advance,
                                                                const float* __restrict__ coef) {
   adam_groups_body(p, g, m, v, rt, nblocks, table, step, gscale * *coef, step_dev, count_dev, ticket, advance);
+}
+
+// ... guarded: as adam_guard_kernel, both branches
+__global__ __launch_bounds__(256) void adam_groups_guard_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                float* __restrict__ m, float* __restrict__ v, const AdamGroupRanges rt,
+                                                                long nblocks, const AdamHyperRow* __restrict__ table, int step,
+                                                                float gscale, const long long* __restrict__ step_dev,
+                                                                long long* count_dev, int* ticket, int advance,
+                                                                const float* __restrict__ guard,
+                                                                const long long* __restrict__ skipped) {
+  adam_groups_body(p, g, m, v, rt, nblocks, table, step, gscale, step_dev, count_dev, ticket, advance, guard, skipped);
 }
 
 // ---------------------------------------------------------------------------
@@ -1923,6 +1978,37 @@ __global__ __launch_bounds__(256) void clip_finalize_kernel(const double* __rest
     const double coef = x < 1.0 ? x : (x != x ? x : 1.0);
     out[0] = (float)coef;
     out[1] = (float)norm;
+  }
+}
+
+// clip_finalize_guard_kernel (lirec_clip_finalize_guard): clip_finalize_kernel -- the same tree, modes and arithmetic for out[0]
+// and out[1]; max_norm == 0: no clipping, the coefficient is 1 -- that also writes out[2] = skip: 1.0f when the DOUBLE sum itself
+// is not finite, 0 otherwise.  The sum is non-finite exactly when an element it covers is: squares cannot cancel, and the squares
+// of finite fp32 values cannot overflow a double (each < 2^256).  `count`: *skipped += skip, the device count of skipped steps
+// that the guarded Adam kernels subtract from their step -- on ONE finalize of a step, the last.
+__global__ __launch_bounds__(256) void clip_finalize_guard_kernel(const double* __restrict__ partials, double* __restrict__ sq,
+                                                                  int mode, float grad_scale, float max_norm,
+                                                                  float* __restrict__ out, long long* __restrict__ skipped,
+                                                                  int count) {
+  __shared__ double red[4];
+  double acc = 0.0;
+  if (mode != 2) {
+    const double* q = partials + (long)threadIdx.x * (CLIP_PARTIALS / 256);
+#pragma unroll
+    for (int j = 0; j < CLIP_PARTIALS / 256; ++j) acc += q[j];
+  }
+  const double s = clip_block_sum(acc, red);
+  if (threadIdx.x == 0) {
+    double total = mode == 0 ? s : (mode == 1 ? *sq + s : *sq);
+    if (mode != 2) *sq = total;
+    const double norm = sqrt(total) * (double)grad_scale;
+    const double x = (double)max_norm / (norm + 1e-6);
+    const double coef = max_norm == 0.f ? 1.0 : (x < 1.0 ? x : (x != x ? x : 1.0));
+    const bool skip = !(fabs(total) <= 1.7976931348623157e308);      // NaN or +-Inf
+    out[0] = (float)coef;
+    out[1] = (float)norm;
+    out[2] = skip ? 1.f : 0.f;
+    if (count && skip) *skipped += 1;
   }
 }
 

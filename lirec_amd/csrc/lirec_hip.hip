@@ -143,6 +143,10 @@ static inline float grad_beta() { return g_grad_overwrite ? 0.f : 1.f; }
 // Per host thread, like g_grad_overwrite and the recorder -- NOT per context: the side streams' launches of a step are issued by
 // the thread that set it, under contexts of their own.
 static thread_local const float* t_adam_clip = nullptr;
+// The guard of this host thread's Adam launches (lirec_set_adam_guard): the (coefficient, norm, skip) block and the count of skipped
+// steps, both in device memory; NULL, NULL = off.  Set, it takes precedence over t_adam_clip.
+static thread_local const float* t_adam_guard = nullptr;
+static thread_local const int64_t* t_adam_guard_skipped = nullptr;
 // The device row a folded first-layer update issued by this host thread reads its five hyper-parameters from
 // (lirec_set_adam_hyper_row), NULL = off: the values of lirec_fused_adam, by value, and today's kernel.  Per host thread, as above.
 static thread_local const lirec_adam_hyper* t_adam_hyper_row = nullptr;
@@ -675,7 +679,7 @@ static int gather_planes(const Args* const* hs, int nh) {
 static int fused_adam_fill(const lirec_fused_adam* adam, GemmGroup& g, AdamFuse& af) {
   // (a clip coefficient needs the norm of the FINISHED gradient, which this very launch produces: the folded update cannot be
   //  clipped, and an unclipped one beside clipped launches would be a silent error)
-  if (t_adam_clip) return LIREC_EINVAL;
+  if (t_adam_clip || t_adam_guard) return LIREC_EINVAL;      // (a guard: the decision needs the finished gradient just the same)
   if (!adam->p || !adam->g || !adam->m || !adam->v || adam->n < 1 || (adam->step < 1 && !adam->step_dev)) return LIREC_EINVAL;
   if (((reinterpret_cast<uintptr_t>(adam->p) | reinterpret_cast<uintptr_t>(adam->g) | reinterpret_cast<uintptr_t>(adam->m) |
         reinterpret_cast<uintptr_t>(adam->v)) & 15) != 0 || (reinterpret_cast<uintptr_t>(adam->wq) & 255) != 0) return LIREC_EINVAL;
@@ -2402,7 +2406,11 @@ int lirec_adam_step(float* p, const float* g, float* m, float* v, int64_t n, int
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
   const int pi = prof_start(PS_ADAM, (hipStream_t)stream);
-  if (t_adam_clip)
+  if (t_adam_guard)
+    lirec::launch(adam_guard_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n,
+                  beta1, beta2, eps, weight_decay, grad_scale, lr, (int)step, (const long long*)step_dev,
+                  (long long*)nullptr, (int*)nullptr, 0, t_adam_guard, (const long long*)t_adam_guard_skipped);
+  else if (t_adam_clip)
     lirec::launch(adam_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n,
                   step_size, bc2_sqrt, beta1, beta2, eps, weight_decay, grad_scale, lr, (const long long*)step_dev,
                   (long long*)nullptr, (int*)nullptr, 0, t_adam_clip);
@@ -2424,7 +2432,11 @@ int lirec_adam_step_counted(float* p, const float* g, float* m, float* v, int64_
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
   const int pi = prof_start(PS_ADAM, (hipStream_t)stream);
-  if (t_adam_clip)
+  if (t_adam_guard)
+    lirec::launch(adam_guard_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n,
+                  beta1, beta2, eps, weight_decay, grad_scale, lr, 0, (const long long*)nullptr,
+                  (long long*)count_dev, (int*)ticket, (int)(advance != 0), t_adam_guard, (const long long*)t_adam_guard_skipped);
+  else if (t_adam_clip)
     lirec::launch(adam_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n,
                   0.f, 0.f, beta1, beta2, eps, weight_decay, grad_scale, lr, (const long long*)nullptr,
                   (long long*)count_dev, (int*)ticket, (int)(advance != 0), t_adam_clip);
@@ -2467,7 +2479,11 @@ int lirec_adam_step_ranges(float* p, const float* g, float* m, float* v, const l
   if (nblocks == 0) return LIREC_OK;
   const long blocks = nblocks > 2048 ? 2048 : nblocks;
   const int pi = prof_start(PS_ADAM, (hipStream_t)stream);
-  if (t_adam_clip)
+  if (t_adam_guard)
+    lirec::launch(adam_ranges_guard_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, rt, nblocks,
+                  beta1, beta2, eps, weight_decay, grad_scale, lr, (int)step, (const long long*)step_dev, (long long*)count_dev,
+                  (int*)ticket, (int)(advance != 0), t_adam_guard, (const long long*)t_adam_guard_skipped);
+  else if (t_adam_clip)
     lirec::launch(adam_ranges_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, rt, nblocks,
                   beta1, beta2, eps, weight_decay, grad_scale, lr, (const long long*)step_dev, (long long*)count_dev,
                   (int*)ticket, (int)(advance != 0), t_adam_clip);
@@ -2536,7 +2552,11 @@ int lirec_adam_step_groups(float* p, const float* g, float* m, float* v, const l
   const long blocks = nblocks > 2048 ? 2048 : nblocks;
   const AdamHyperRow* table = reinterpret_cast<const AdamHyperRow*>(table_dev);
   const int pi = prof_start(PS_ADAM, (hipStream_t)stream);
-  if (t_adam_clip)
+  if (t_adam_guard)
+    lirec::launch(adam_groups_guard_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, rt, nblocks, table,
+                  (int)step, grad_scale, (const long long*)step_dev, (long long*)count_dev, (int*)ticket, (int)(advance != 0),
+                  t_adam_guard, (const long long*)t_adam_guard_skipped);
+  else if (t_adam_clip)
     lirec::launch(adam_groups_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, rt, nblocks, table,
                   (int)step, grad_scale, (const long long*)step_dev, (long long*)count_dev, (int*)ticket, (int)(advance != 0),
                   t_adam_clip);
@@ -2606,6 +2626,27 @@ int lirec_clip_finalize(const double* partials, double* sq_dev, int32_t mode, fl
   lirec::launch(clip_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, sq_dev, (int)mode, grad_scale, max_norm,
                 out);
   LIREC_CHECK_LAUNCH();
+  return LIREC_OK;
+}
+
+int lirec_clip_finalize_guard(const double* partials, double* sq_dev, int32_t mode, float grad_scale, float max_norm, float* out,
+                              int64_t* skipped_dev, int32_t count, lirec_stream_t stream) {
+  if (!sq_dev || !out || mode < 0 || mode > 2 || (mode != 2 && !partials)) return LIREC_EINVAL;
+  if (!(max_norm >= 0.f)) return LIREC_EINVAL;                   // (NaN included; 0: no clipping)
+  if (count != 0 && !skipped_dev) return LIREC_EINVAL;
+  if (((reinterpret_cast<uintptr_t>(partials) | reinterpret_cast<uintptr_t>(sq_dev) | reinterpret_cast<uintptr_t>(skipped_dev)) & 7) != 0 ||
+      (reinterpret_cast<uintptr_t>(out) & 3) != 0) return LIREC_EINVAL;
+  lirec::launch(clip_finalize_guard_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, sq_dev, (int)mode, grad_scale,
+                max_norm, out, (long long*)skipped_dev, (int)(count != 0));
+  LIREC_CHECK_LAUNCH();
+  return LIREC_OK;
+}
+
+int lirec_set_adam_guard(const float* out_dev, const int64_t* skipped_dev) {
+  if ((out_dev == nullptr) != (skipped_dev == nullptr)) return LIREC_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(out_dev) & 3) != 0 || (reinterpret_cast<uintptr_t>(skipped_dev) & 7) != 0) return LIREC_EINVAL;
+  t_adam_guard = out_dev;
+  t_adam_guard_skipped = skipped_dev;
   return LIREC_OK;
 }
 

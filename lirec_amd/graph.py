@@ -187,6 +187,8 @@ class RecordedTrainStep:
             raise ValueError('RecordedTrainStep(next_batch=...): single-GPU form')
         dev = model.flat_params().device
         optimizer._ensure_state()
+        if hasattr(optimizer, 'fold_if_due'):
+            optimizer.fold_if_due()       # (skipped steps of another frozen set, or of a guard since switched off: while the step is by value)
         # [forward calls (the dropout key's offset), Adam step, Adam step AS THE SIDE STREAM COUNTS IT]: the first two are advanced by
         # the step's first launch; the third by the side stream itself in front of its share of the update -- a replayed step leaves
         # that stream un-joined (`defer`), so its Adam launch may still be running when the NEXT step's first launch advances the
@@ -222,10 +224,11 @@ class RecordedTrainStep:
         self.overwrite = bool(overwrite) if (overwrite is not None and getattr(model, 'grad_sync', None) is None) else False
         # Gradient clipping (FusedAdam.max_grad_norm): the norm needs every gradient of the step finished, so the clipped update is
         # issued whole on this stream behind backward -- no fused first-layer update, no un-joined side stream (`defer`)
-        clipping = bool(getattr(optimizer, 'max_grad_norm', None))
+        # (skip_nonfinite -- the guard -- takes the same route for the same reason: the decision needs the finished gradients)
+        clipping = bool(getattr(optimizer, 'max_grad_norm', None)) or bool(getattr(optimizer, 'skip_nonfinite', False))
         if clipping and self.sync is not None and self.sync.world > 1:
-            raise LirecError('RecordedTrainStep: gradient clipping under data parallelism is not recorded (the all-reduce of the squared '
-                             'norm sits between the recorded launches) -- run the eager step')
+            raise LirecError('RecordedTrainStep: gradient clipping / skip_nonfinite under data parallelism is not recorded (the all-reduce '
+                             'of the squared norm sits between the recorded launches) -- run the eager step')
         self.mid, self.parity, self.pre = None, 0, [None, None]
         # (warmup = 0: the caller has already run eager steps of this model -- lirec_amd.train records in the middle of an epoch,
         #  every batch being stepped on exactly once -- so the recording step is the only step taken here; the gradient-overwrite
@@ -402,7 +405,9 @@ class RecordedTrainStep:
         # (gradient clipping: whether the norm launches and the clipped Adam kernels were recorded, and the bound the recorded
         #  lirec_clip_finalize carries by value -- the coefficient itself is computed anew by every replay.  Off: today's key.)
         clip = getattr(optimizer, 'max_grad_norm', None)
-        return key + (('max_grad_norm', float(clip)),) if clip else key
+        key = key + (('max_grad_norm', float(clip)),) if clip else key
+        # (the guard: whether the guard finalize and the guarded Adam kernels were recorded.  Off: today's key.)
+        return key + (('skip_nonfinite', True),) if getattr(optimizer, 'skip_nonfinite', False) else key
 
     def _check_core(self):
         if ops.get_gemm_mode() != self._gemm_mode:
@@ -510,6 +515,8 @@ class RecordedTrainStep:
         copy) and the recorded list is valid again -- how a training loop steps on an odd-shaped batch in between
         (lirec_amd.train: the short last batch of an epoch)."""
         self._check_core()
+        if hasattr(self.optim, 'fold_if_due'):
+            self.optim.fold_if_due()      # (the eager steps in between may have changed the frozen set: before the counters attach)
         self.state.copy_(torch.tensor([self.model._fwd_train_calls, self.optim._step, self.optim._step], dtype=torch.int64), non_blocking=False)
         self.model._seed_dev, self.optim._step_dev = self.state[0:1], self.state[1:2]
         self.optim._step_side_dev = self.state[2:3]

@@ -855,6 +855,36 @@ class adam_clip:
         return False
 
 
+def clip_finalize_guard(partials, sq, mode, grad_scale, max_norm, out, skipped=None, count=False):
+    """lirec_clip_finalize_guard: clip_finalize (``max_norm`` 0: coefficient 1) that also writes ``out[2]`` = 1.0 when ``sq`` is not
+    finite, else 0 (``out``: device float32[>= 3]), and -- ``count`` -- adds that to ``skipped`` (device int64[1])"""
+    assert sq.dtype == torch.float64 and out.dtype == torch.float32 and out.numel() >= 3 and out.is_contiguous()
+    assert partials is None or partials.dtype == torch.float64
+    assert skipped is None or skipped.dtype == torch.int64
+    check(lib().lirec_clip_finalize_guard(_p(partials), _p(sq), int(mode), float(grad_scale), float(max_norm), _p(out), _p(skipped),
+                                          int(bool(count)), _stream()), 'lirec_clip_finalize_guard')
+
+
+class adam_guard:
+    """``with ops.adam_guard(out, skipped):`` -- the Adam launches this host thread issues inside are the guarded ones: no-ops
+    when the device float ``out[2]`` is set, otherwise scaled by ``out[0]`` with the step less the device int64 ``skipped``
+    (lirec_set_adam_guard); cleared on the way out, also when a launch raises.  ``out`` None: nothing is set."""
+
+    def __init__(self, out, skipped=None):
+        self.out, self.skipped = out, skipped
+
+    def __enter__(self):
+        if self.out is not None:
+            assert self.out.dtype == torch.float32 and self.out.numel() >= 3 and self.skipped.dtype == torch.int64
+            check(lib().lirec_set_adam_guard(_p(self.out), _p(self.skipped)), 'lirec_set_adam_guard')
+        return self
+
+    def __exit__(self, *exc):
+        if self.out is not None:
+            check(lib().lirec_set_adam_guard(None, None), 'lirec_set_adam_guard')
+        return False
+
+
 def counter_add(ctr, incs):
     """ctr[i] += incs[i] on the device (ctr: int64 device tensor, len(incs) <= 4)."""
     assert ctr.dtype == torch.int64 and ctr.is_cuda and 1 <= len(incs) <= 4 and ctr.numel() >= len(incs)

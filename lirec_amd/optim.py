@@ -47,6 +47,20 @@ defaults (3e-5 x 1e-5) decoupled decay does nothing, here as in torch's fp32 ``m
 ``torch.optim.AdamW`` / ``torch.optim.Adam(decoupled_weight_decay=True)`` with the same groups and back.  Under ``device_hyper``
 the first-layer update stays folded into the backward (``arm_first_layer_update``) when the first layers span SEVERAL groups --
 weights that decay, biases that do not --: each parameter then reads the row of its own group (``lirec_set_adam_hyper_map``).
+
+Skipping non-finite steps (``skip_nonfinite``, off by default; apex's ``noop_flag``, torch's ``_fused_adam(found_inf=)``): a step
+whose TRAINABLE gradients hold a NaN or an Inf leaves parameters and moments bit for bit untouched and does not count as an update
+for the bias corrections -- what a loop that calls ``step()`` only when the norm is finite gets -- decided on the device, with no
+host visit, so the recorded step and the sharded data-parallel update have it too.  The step takes the clipped route whether or
+not ``max_grad_norm`` is set (the norm's double sum of squares is non-finite exactly when a gradient element is; computed once for
+both features), then one ``lirec_clip_finalize_guard`` that also counts, then the whole update inside ``ops.adam_guard``: no update
+beside the tail of backward, no folded first-layer update.  ``found_nonfinite`` / ``skipped_steps`` are device views.  ACCOUNTING:
+``_step`` (and a recorded step's device counter) count every call; the kernels subtract S = the device count of skipped steps.
+Between two changes of the frozen set a trainable parameter has received ``_step - lag - S`` updates, a frozen one ``_step - lag``
+(its lag advances every call); ``state_dict()`` reports exactly that.  Where the frozen set changes, or the guard is switched off
+with steps skipped, the optimiser FOLDS S into ``_step`` and the frozen parameters' lags (one read of S, a synchronisation at a
+rare event) -- legal only where the step is by value: at the top of an eager ``step()``, before a recording attaches its counters.
+The gradients stay as backward left them, non-finite values included.
 """
 from __future__ import annotations
 
@@ -76,7 +90,7 @@ class FusedAdam(torch.optim.Optimizer):
             raise ValueError('Invalid weight_decay value: {}'.format(weight_decay))
 
     def __init__(self, model, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5, max_grad_norm=None, param_groups=None,
-                 device_hyper=None, amsgrad=False, decoupled_weight_decay=False):
+                 device_hyper=None, amsgrad=False, decoupled_weight_decay=False, skip_nonfinite=False):
         self.model = model
         params = list(model.parameters())
         self._names = [n for n, _ in model.named_parameters()]        # (in the order of model._plist)
@@ -115,7 +129,11 @@ class FusedAdam(torch.optim.Optimizer):
         self._step_side_dev = None     # device int64[1]: the same as the weight-gradient side stream counts it (step(): side update)
         self._lag = {}                 # parameter name -> updates it sat out frozen (missing = 0): state[p]['step'] = _step - lag
         self.max_grad_norm = max_grad_norm      # None / 0: no clipping; settable between steps (a recorded step is recorded again)
-        self._clip_out = None          # device float32[2]: (clip coefficient, gradient norm) of the last clipped step
+        self._clip_out = None          # device float32[4]: (clip coefficient, gradient norm, skipped?, -) of the last clipped / guarded step
+        self.skip_nonfinite = bool(skip_nonfinite)      # settable between steps (a recorded step is recorded again)
+        self._skipped_dev = None       # device int64[1]: S, the steps skipped since the last fold
+        self._skipped_folded = 0       # skipped steps already folded into _step (skipped_total)
+        self._guard_flags = None       # the requires_grad flags of the interval S counts in; None: no guarded step since the fold (S = 0)
 
     # -- parameter groups -------------------------------------------------------
     def resolve_device_hyper(self):
@@ -251,6 +269,8 @@ class FusedAdam(torch.optim.Optimizer):
             self._m = torch.zeros_like(flat)
             self._v = torch.zeros_like(flat)
             self._side_ticket = torch.zeros(1, dtype=torch.int32, device=flat.device)      # (lirec_adam_step_counted's arrival counter)
+            if self._guard_flags is not None:
+                self._fold_skipped()   # (the count of skipped steps does not outlive its buffer)
             self._clip_out = None
             pd = dict(self.model.named_parameters())
             for n, (off, k) in self.model._offsets.items():
@@ -307,7 +327,8 @@ class FusedAdam(torch.optim.Optimizer):
         if self._clip_out is None or self._clip_out.device != self.model.flat_params().device:
             from ._lib import CLIP_PARTIALS
             dev = self.model.flat_params().device
-            self._clip_out = torch.tensor([1.0, 0.0], dtype=torch.float32, device=dev)
+            self._clip_out = torch.tensor([1.0, 0.0, 0.0, 0.0], dtype=torch.float32, device=dev)
+            self._skipped_dev = torch.zeros(1, dtype=torch.int64, device=dev)
             self._clip_sq = torch.zeros(1, dtype=torch.float64, device=dev)
             self._clip_partials = torch.zeros(CLIP_PARTIALS, dtype=torch.float64, device=dev)
         return self._clip_out
@@ -324,12 +345,80 @@ class FusedAdam(torch.optim.Optimizer):
         parameters AS THE UPDATE SAW IT (times ``grad_scale``), before clipping -- what ``clip_grad_norm_`` returns"""
         return self._clip_buffers()[1]
 
+    @property
+    def found_nonfinite(self):
+        """0-d device float (a view: no synchronisation): 1.0 when the last guarded step (``skip_nonfinite``) found a NaN or an Inf
+        in the trainable gradients and was skipped, else 0"""
+        return self._clip_buffers()[2]
+
+    @property
+    def skipped_steps(self):
+        """0-d device int64 (a view: no synchronisation): the guarded steps skipped since the optimiser last folded them into its
+        step (a change of the frozen set, the guard switched off, ``load_state_dict``) -- in a run without those, all of them"""
+        self._clip_buffers()
+        return self._skipped_dev[0]
+
+    # -- skipped steps: the accounting ---------------------------------------------
+    @staticmethod
+    def updates_received(step, lags, flags, skipped):
+        """per-parameter number of updates, torch.optim.Adam's ``state[p]['step']``: ``step`` calls so far, ``lags`` and ``flags``
+        (requires_grad during the interval ``skipped`` was counted in) in parameter order.  A trainable parameter sat the skipped
+        steps out; a frozen one's lag has grown with every call, skipped or not."""
+        return [step - lag - (skipped if f else 0) for lag, f in zip(lags, flags)]
+
+    @staticmethod
+    def folded(step, lags, flags, skipped):
+        """(step, lags) after a fold of ``skipped`` steps: the step loses them, and so does the lag of every parameter frozen
+        throughout -- ``updates_received`` with 0 skipped gives the same counts as before"""
+        return step - skipped, [lag if f else lag - skipped for lag, f in zip(lags, flags)]
+
+    def _read_skipped(self):
+        return int(self._skipped_dev.item()) if self._guard_flags is not None and self._skipped_dev is not None else 0
+
+    def _fold_skipped(self):
+        """S into ``_step`` and the frozen parameters' lags; the device count back to 0.  Only where the step is by value."""
+        if self._step_dev is not None:
+            raise RuntimeError('FusedAdam: the frozen set changed, or skip_nonfinite was switched off, while a recorded step holds the '
+                               'step on the device -- the skipped steps cannot be folded in there; release() the recorded step first')
+        S = self._read_skipped()
+        if S:
+            self._step, lags = self.folded(self._step, [self._lag.get(n, 0) for n in self._names], self._guard_flags, S)
+            self._lag = {n: lag for n, lag in zip(self._names, lags) if lag}
+            self._ranges_key = None
+            self._skipped_dev.zero_()
+            self._skipped_folded += S
+        self._guard_flags = None
+
+    def skipped_total(self):
+        """every step skipped so far, folded ones included, as a host int (one read of the device count: synchronises)"""
+        return self._skipped_folded + self._read_skipped()
+
+    def fold_if_due(self):
+        """at the top of an eager step, and before a recording attaches its counters: fold when the frozen set is no longer the one
+        the skipped steps were counted under, or the guard is off"""
+        if self._guard_flags is not None and (not self.skip_nonfinite or self._flags() != self._guard_flags):
+            self._fold_skipped()
+
+    def _finalize(self, partials, mode, count=False):
+        """the finalize of the route: the guard's (bound 0 = no clipping) with the guard on, the clip's otherwise"""
+        if self._guard_now:
+            ops.clip_finalize_guard(partials, self._clip_sq, mode, self.grad_scale, self._clip_now or 0.0, self._clip_out,
+                                    self._skipped_dev, count)
+        else:
+            ops.clip_finalize(partials, self._clip_sq, mode, self.grad_scale, self._clip_now, self._clip_out)
+
+    def _scaled(self):
+        """the context the route's Adam launches are issued in"""
+        if self._guard_now:
+            return ops.adam_guard(self._clip_out, self._skipped_dev)
+        return ops.adam_clip(self._clip_out[0:1])
+
     def _clip_accumulate(self, gbuf, ranges, first):
         """sum of squares of ``gbuf`` over ``ranges`` = [(offset, length)] into the device double (the first table of a step sets
         it, the others add) and the coefficient of the sum so far; returns ``first`` for the next call"""
         for ch in self._chunks([r for r in ranges if r[1] > 0]):
             ops.grad_sq_partials(gbuf, ch, self._clip_partials)
-            ops.clip_finalize(self._clip_partials, self._clip_sq, 0 if first else 1, self.grad_scale, self._clip_now, self._clip_out)
+            self._finalize(self._clip_partials, 0 if first else 1)
             first = False
         return first
 
@@ -342,9 +431,11 @@ class FusedAdam(torch.optim.Optimizer):
         ignores it and step() updates the range as usual."""
         self._ensure_state()
         m = self.model
+        if self._step_dev is None:
+            self.fold_if_due()
         if getattr(m, 'grad_sync', None) is not None or not hasattr(m, 'first_layer_range'):
             return False
-        if self._clip_max() is not None:
+        if self._clip_max() is not None or self.skip_nonfinite:
             return False          # (the norm needs the finished first-layer gradients: they are updated with the rest, clipped)
         row = hmap = None
         if self.resolve_device_hyper():
@@ -517,6 +608,7 @@ class FusedAdam(torch.optim.Optimizer):
     def step(self, closure=None):
         loss = closure() if closure is not None else None
         self._ensure_state()
+        self.fold_if_due()                # (raises where a recorded step holds the step on the device)
         self._all_live = self.all_trainable()
         grp = self.param_groups[0]
         if self.resolve_device_hyper():
@@ -531,9 +623,13 @@ class FusedAdam(torch.optim.Optimizer):
         flat = self.model.flat_params()
         sync = self.model.grad_sync
         self._clip_now = self._clip_max()
-        clip = self._clip_now is not None
+        # (skip_nonfinite: the clipped route, whether or not a bound is set -- `clip` from here on means "that route")
+        self._guard_now = guard = bool(self.skip_nonfinite)
+        clip = self._clip_now is not None or guard
         if clip:
             self._clip_buffers()
+        if guard:
+            self._guard_flags = self._flags()
         if sync is not None and sync.world > 1:
             if getattr(opt, 'strict', False) and hasattr(sync, 'check_frozen_set'):
                 sync.check_frozen_set(self._flags(), self.group_membership() if len(self.param_groups) > 1 else ())
@@ -634,13 +730,15 @@ class FusedAdam(torch.optim.Optimizer):
                     if skip:
                         # (max_grad_norm was set between arm_first_layer_update() and this step: the backward has already applied
                         #  the first layers' update, unclipped -- nothing here can take it back)
-                        raise RuntimeError('FusedAdam.step(): max_grad_norm was set after the backward of this step had folded the '
-                                           'first-layer update in (arm_first_layer_update); set it before the step begins')
+                        raise RuntimeError('FusedAdam.step(): max_grad_norm / skip_nonfinite was set after the backward of this step had '
+                                           'folded the first-layer update in (arm_first_layer_update); set it before the step begins')
                     rs = [(0, flat.numel())] if self._all_live else [(a, b - a) for a, b, *_ in self.trainable_ranges()]
                     if self._clip_accumulate(g, rs, True):
                         self._clip_nothing()              # (nothing trainable: no update; norm 0, coefficient 1)
                     else:
-                        with ops.adam_clip(self._clip_out[0:1]):
+                        if guard:         # (the one finalize of the step that counts)
+                            self._finalize(None, 2, count=True)
+                        with self._scaled():
                             update(0, flat.numel())
                 else:
                     update(0, flat.numel())
@@ -652,7 +750,7 @@ class FusedAdam(torch.optim.Optimizer):
         """a clipped step with nothing to clip: (coefficient, norm) = (1, 0), written by the finalize from a zeroed sum -- two
         tiny library launches that a command list records like the rest (the values of an earlier step must not stay)"""
         ops.zero_(self._clip_sq)
-        ops.clip_finalize(None, self._clip_sq, 2, self.grad_scale, self._clip_now, self._clip_out)
+        self._finalize(None, 2)
 
     def _step_parallel_clipped(self, sync, flat, g, args):
         """The data-parallel update with gradient clipping: EVERY bucket's reduction lands first (no update beside the tail of
@@ -682,8 +780,10 @@ class FusedAdam(torch.optim.Optimizer):
             ops.zero_(self._clip_sq)         # (nothing trainable in this rank's slices)
         if not everywhere:
             dist.all_reduce(self._clip_sq, op=dist.ReduceOp.SUM, group=sync.group)
-            ops.clip_finalize(None, self._clip_sq, 2, self.grad_scale, self._clip_now, self._clip_out)
-        with ops.adam_clip(self._clip_out[0:1]):
+        # (the all-reduced double is the same on every rank: so are the coefficient, the flag and the count -- no further collective)
+        if not everywhere or self._guard_now:
+            self._finalize(None, 2, count=True)
+        with self._scaled():
             for lo, hi in buckets:
                 a, b = sync.my_slice(lo, hi)
                 if b > a:
@@ -693,9 +793,12 @@ class FusedAdam(torch.optim.Optimizer):
 
     def _sync_state_steps(self):
         """``state[p]['step']`` tensors are refreshed when somebody looks (state_dict), not 38 times a step."""
-        lag = {id(p): self._lag.get(n, 0) for n, p in zip(self._names, self.model._plist)} if self._lag else {}
+        S = self._read_skipped()          # (one read, behind the joined streams; every counter stays as it is)
+        flags = self._guard_flags if S else self._flags()
+        got = self.updates_received(self._step, [self._lag.get(n, 0) for n in self._names], flags, S)
+        count = {id(p): k for p, k in zip(self.model._plist, got)}
         for p, st in self.state.items():
-            st['step'] = torch.tensor(float(self._step - lag.get(id(p), 0)))
+            st['step'] = torch.tensor(float(count.get(id(p), self._step)))
 
     def consolidate_state(self):
         """COLLECTIVE (every rank must call it, at the same point): under the sharded data-parallel update a rank's moments are
@@ -739,6 +842,9 @@ class FusedAdam(torch.optim.Optimizer):
         # (one step per parameter, as torch.optim.Adam keeps it: the ones behind the furthest carry the difference as their lag;
         #  a parameter without state has received no update)
         self._lag = {}
+        self._guard_flags = None            # (the loaded steps are whole: nothing skipped on top of them)
+        if self._skipped_dev is not None:
+            self._skipped_dev.zero_()
         for n, p in zip(self._names, self.model._plist):
             st = self.state.get(p)
             lag = self._step - (int(float(st['step'])) if st and 'step' in st else 0)

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import copy
 import os
+import math
 import time
 from datetime import datetime
 
@@ -30,11 +31,12 @@ _print = print
 _DP_RECORD_TRIES = 6          # data parallel: iterations 3 .. 8 of an epoch are where the ranks may agree to record the step
 
 
-def _flush_losses(pending, losses, wait=True):
+def _flush_losses(pending, losses, wait=True, finite_only=False):
     """Read queued per-iteration losses back in one transfer and feed the running average in order.  ``wait=False`` (the
     per-10-iteration log line): only the losses of steps the GPU has FINISHED are read, on a stream of their own -- a copy on
     the step's stream would wait for every step enqueued so far, i.e. drain the pipeline every ten iterations (measured: ~10 %
-    of the loop); the printed value then lags the loop by the steps still in flight.  ``wait=True`` (epoch end): everything."""
+    of the loop); the printed value then lags the loop by the steps still in flight.  ``wait=True`` (epoch end): everything.
+    ``finite_only`` (FusedAdam.skip_nonfinite): a NaN / Inf loss value -- a step the optimiser skipped -- stays out of the average."""
     if not pending:
         return
     k = len(pending)
@@ -53,6 +55,8 @@ def _flush_losses(pending, losses, wait=True):
     else:
         vals = torch.cat([v for v, _, _ in take]).cpu().tolist()
     for v, (_, n, _) in zip(vals, take):
+        if finite_only and not math.isfinite(v):
+            continue
         losses.update(v, n)
     del pending[:k]
 
@@ -116,6 +120,7 @@ def training(train_dataset, **kwargs):
         raise RuntimeError('training() under torch.distributed with %s: attach the loss -- DataParallel(model, optimizer, loss=loss) -- '
                            'so that its valid-row mean is the global batch\'s' % type(loss).__name__)
     batch_time, data_time, losses = Averaging(), Averaging(), Averaging()
+    guarded = lambda: bool(getattr(optimizer, 'skip_nonfinite', False))
     # (a dataset may bring its own collate_fn / pin_memory -- lirec_amd.features.PiecesDataset does: de-duplicated piece
     #  tables + index instead of the tiled float64 block, built by `num_workers` THREADS (lirec_amd/loader.py says why);
     #  the protocol of mlp/train.py:33-37 is otherwise unchanged)
@@ -171,7 +176,7 @@ def training(train_dataset, **kwargs):
                 end = time.time()
                 seen += nlab
                 if i % 10 == 0 and i:
-                    _flush_losses(pending, losses, wait=False)
+                    _flush_losses(pending, losses, wait=False, finite_only=guarded())
                     print('Epoch: [{0}][{1}/{2}]\tTime {bt.val:.3f} ({bt.avg:.3f})\tData {dt.val:.3f} ({dt.avg:.3f})\t'
                           'Loss {ls.val:.4f} ({ls.avg:.4f})\t'.format(epoch, i, len(loader), bt=batch_time, dt=data_time, ls=losses))
                 continue
@@ -266,15 +271,17 @@ def training(train_dataset, **kwargs):
             end = time.time()
             seen += len(labels)
             if i % 10 == 0 and i:
-                _flush_losses(pending, losses, wait=False)
+                _flush_losses(pending, losses, wait=False, finite_only=guarded())
                 print('Epoch: [{0}][{1}/{2}]\tTime {bt.val:.3f} ({bt.avg:.3f})\tData {dt.val:.3f} ({dt.avg:.3f})\t'
                       'Loss {ls.val:.4f} ({ls.avg:.4f})\t'.format(epoch, i, len(loader), bt=batch_time, dt=data_time, ls=losses))
-        _flush_losses(pending, losses)
+        _flush_losses(pending, losses, finite_only=guarded())
         if scheduler is not None and scheduler_every == 'epoch':
             scheduler.step()
         print(seen)
         print('loss: %f' % losses.avg)
         print('train clips/s: %.1f' % (seen / max(time.time() - t_epoch, 1e-9)))
+        if guarded():
+            print('skipped steps: %d' % optimizer.skipped_total())        # (one read per epoch)
         losses.reset()
         if epoch % opt.test_fr == 0:
             testing(train_dataset, model, loss, total_iter=epoch, mode='train', train_start_time=start)
