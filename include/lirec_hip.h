@@ -660,6 +660,20 @@ int lirec_set_adam_clip(const float* coef_dev);
 int lirec_clip_finalize_guard(const double* partials, double* sq_dev, int32_t mode, float grad_scale, float max_norm, float* out,
                               int64_t* skipped_dev, int32_t count, lirec_stream_t stream);
 int lirec_set_adam_guard(const float* out_dev, const int64_t* skipped_dev);
+/* ---- exponential moving average of the weights --------------------------------------
+ * torch.optim.swa_utils.get_ema_multi_avg_fn(decay) / timm's ModelEmaV2 as a launch that rides behind an Adam launch on that
+ * launch's stream: ema[i] <- fmaf(weight, p[i] - ema[i], ema[i]) for i < n, the difference rounded to fp32 first -- torch's
+ * lerp(ema, p, weight) for weight < 0.5, bit for bit.  weight = (float)(1.0 - decay), rounded by the caller.  An element with
+ * ema[i] == p[i] keeps its bits (but for ema[i] = -0, which becomes +0 as in torch: the difference of equal values is +0).  One memory-bound launch (12 bytes per element: f32x4 body, 256-thread workgroups, at most
+ * LIREC_EMA_MAX_BLOCKS of them, grid-strided), with a scalar head until the pointers reach 16-byte alignment and a scalar tail:
+ * ema and p may start at ANY element of their buffers (a data-parallel slice), as long as both sit at the same offset modulo 16
+ * bytes.  guard_dev, when not NULL, is the `out` block of lirec_clip_finalize_guard: one uniform load of word 2; non-zero, no
+ * element is read or written (a skipped step is no update of the average either).  The pointer is taken when the launch is
+ * issued: a recorded launch keeps it, every replay reads the word anew.  n == 0: no launch.  LIREC_EINVAL before any device call
+ * for: ema or p NULL, n < 0, a pointer (guard_dev included) not 4-byte aligned, ema and p differing modulo 16 bytes, weight not in
+ * (0, 0.5) (NaN included).  (Added to ABI 124 without a new number: an export only.) */
+#define LIREC_EMA_MAX_BLOCKS 2048
+int lirec_ema_step(float* ema, const float* p, int64_t n, float weight, const float* guard_dev, lirec_stream_t stream);
 /* ---- parameter groups: hyper-parameters in device memory ---------------------------
  * torch.optim.Adam's param_groups, and hyper-parameters that change between the replays of a recorded step (a learning-rate
  * schedule): lr, betas, eps and weight_decay live in a small TABLE in device memory, one 32-byte row per group, that the Adam

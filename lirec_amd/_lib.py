@@ -119,6 +119,7 @@ ADAM_MAX_GROUPS = 8           # LIREC_ADAM_MAX_GROUPS
 ADAM_MAX_RANGES = 64
 ADAM_MAP_MAX = 16             # LIREC_ADAM_MAP_MAX: the entries of lirec_set_adam_hyper_map
 CLIP_PARTIALS = 1024          # LIREC_CLIP_PARTIALS: the doubles lirec_grad_sq_partials writes
+EMA_MAX_BLOCKS = 2048         # LIREC_EMA_MAX_BLOCKS: the grid cap of lirec_ema_step (256 threads x one f32x4 a workgroup and pass)
 
 
 class LinearFwdArgs(C.Structure):
@@ -223,6 +224,7 @@ _PROTOS = {
     'lirec_set_adam_clip': (_i32, [_vp]),
     'lirec_clip_finalize_guard': (_i32, [_vp, _vp, _i32, _f32, _f32, _vp, _vp, _i32, _vp]),
     'lirec_set_adam_guard': (_i32, [_vp, _vp]),
+    'lirec_ema_step': (_i32, [_vp, _vp, _i64, _f32, _vp, _vp]),
     'lirec_eval_max_tracks': (_i32, [C.POINTER(EvalArgs), _vp]),
     'lirec_cast_f64_f32': (_i32, [_vp, _vp, _i64, _vp]),
     'lirec_grid_pool': (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i64, _vp]),

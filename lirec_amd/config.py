@@ -72,6 +72,8 @@ def defaults() -> dict:
         adam_on_side_stream=True,      # single GPU: the first gradient bucket is updated on the side stream (lirec_amd/optim.py)
         decoupled_weight_decay=False,  # FusedAdam: AdamW -- the decay multiplies the parameters by 1 - lr wd and stays out of the gradient
         skip_nonfinite=False,          # FusedAdam: a step whose trainable gradients hold a NaN / Inf is skipped, on the device (parameters, moments and the bias corrections' step untouched)
+        ema_decay=0.0,                 # in (0.5, 1): FusedAdam keeps an exponential moving average of the weights, updated on the device behind every applied step (0: off)
+        eval_ema=False,                # training(): the val / test evaluations run on the averaged weights (optimizer.ema_weights()); mode='train' stays on the live ones
         clip_grad_norm=0.0,            # > 0: FusedAdam clips the gradients to this global L2 norm, on the device, inside the update (max_grad_norm)
         gate_stage_on_side=True,       # ... with the weights staged on the side stream beside layer 1
         gate_q32=True,                 # training: the gate's forward / data gradient on staged q32b operands (lirec_gate_fwd_ws)

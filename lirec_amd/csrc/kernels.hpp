@@ -2023,6 +2023,33 @@ __global__ __launch_bounds__(256) void cast_f64_f32_kernel(const double* __restr
 }
 
 // ---------------------------------------------------------------------------
+// Exponential moving average of the weights (lirec_ema_step): e <- fmaf(w, p - e, e), torch's lerp(e, p, w) for w < 0.5.  The
+// difference is rounded on its own (__fsub_rn: never contracted into the fma), so e == p gives fmaf(w, +0, e) = e, bit for bit (e = -0 alone becomes +0, as in torch).
+// 12 bytes per element and two flops: HBM-bound.  `head` (0..3) scalar elements bring both pointers to 16-byte alignment -- the
+// host checked that they sit at the same offset modulo 16 --, then f32x4, then a scalar tail.  `guard`: the (coefficient, norm,
+// skip) block of clip_finalize_guard_kernel; one uniform load, a set flag ends the launch before any element is touched.
+// ---------------------------------------------------------------------------
+#define EMA_MAX_BLOCKS 2048
+__device__ __forceinline__ float ema1(float e, float p, float w) { return fmaf(w, __fsub_rn(p, e), e); }
+__global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ e, const float* __restrict__ p, long n, int head, float w,
+                                                  const float* __restrict__ guard) {
+  if (guard && guard[2] != 0.f) return;
+  const long stride = (long)gridDim.x * blockDim.x;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid < head) e[gid] = ema1(e[gid], p[gid], w);                   // (head <= n)
+  float* __restrict__ eb = e + head;
+  const float* __restrict__ pb = p + head;
+  const long nb = n - head, n4 = nb >> 2;
+  for (long i = gid; i < n4; i += stride) {
+    f32x4 a = reinterpret_cast<const f32x4*>(eb)[i];
+    const f32x4 b = reinterpret_cast<const f32x4*>(pb)[i];
+    a[0] = ema1(a[0], b[0], w); a[1] = ema1(a[1], b[1], w); a[2] = ema1(a[2], b[2], w); a[3] = ema1(a[3], b[3], w);
+    reinterpret_cast<f32x4*>(eb)[i] = a;
+  }
+  for (long i = (n4 << 2) + gid; i < nb; i += stride) eb[i] = ema1(eb[i], pb[i], w);
+}
+
+// ---------------------------------------------------------------------------
 // Evaluation counters (lirec_eval_max_tracks; utils/evaluation.py:114-176, :179-271).  One workgroup per clip.
 // ---------------------------------------------------------------------------
 // (value, index) with numpy argmax semantics: the larger value wins, ties go to the lower index; index 0x7fffffff = empty.

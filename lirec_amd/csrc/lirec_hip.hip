@@ -2650,6 +2650,23 @@ int lirec_set_adam_guard(const float* out_dev, const int64_t* skipped_dev) {
   return LIREC_OK;
 }
 
+int lirec_ema_step(float* ema, const float* p, int64_t n, float weight, const float* guard_dev, lirec_stream_t stream) {
+  static_assert(LIREC_EMA_MAX_BLOCKS == EMA_MAX_BLOCKS, "the header's grid cap is the kernel's");
+  if (!ema || !p || n < 0) return LIREC_EINVAL;
+  const uintptr_t ea = reinterpret_cast<uintptr_t>(ema), pa = reinterpret_cast<uintptr_t>(p);
+  if (((ea | pa | reinterpret_cast<uintptr_t>(guard_dev)) & 3) != 0 || ((ea ^ pa) & 15) != 0) return LIREC_EINVAL;
+  if (!(weight > 0.f && weight < 0.5f)) return LIREC_EINVAL;     // (NaN included; 0.5 and above is torch's other lerp branch)
+  if (n == 0) return LIREC_OK;
+  int64_t head = (int64_t)(((16 - (ea & 15)) & 15) >> 2);         // scalar elements in front of the first 16-byte boundary
+  if (head > n) head = n;
+  long blocks = (long)(((n - head) / 4 + 255) / 256);
+  if (blocks > EMA_MAX_BLOCKS) blocks = EMA_MAX_BLOCKS;
+  if (blocks < 1) blocks = 1;
+  lirec::launch(ema_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ema, p, (long)n, (int)head, weight, guard_dev);
+  LIREC_CHECK_LAUNCH();
+  return LIREC_OK;
+}
+
 int lirec_eval_max_tracks(const lirec_eval_args* a, lirec_stream_t stream) {
   if (!a || !a->ints || !a->y || !a->g || !a->counters || a->B < 1 || a->T < 1 || a->C < 1) return LIREC_EINVAL;
   if (a->rels && (!a->r || a->NR < 1)) return LIREC_EINVAL;

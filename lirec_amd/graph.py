@@ -383,6 +383,8 @@ class RecordedTrainStep:
         self.optim._opt_called = True               # (torch's lr_scheduler: an optimiser step HAS been taken -- no order warning)
         if hasattr(self.optim, '_advance_lags'):
             self.optim._advance_lags()              # (frozen parameters sat this update out, as in the eager step())
+        if hasattr(self.optim, '_advance_ema'):
+            self.optim._advance_ema()               # (the host count behind ema_updates(); skipped steps come off on the device's word)
         if hasattr(self.loss, '_sample_key'):
             self.loss._sample_calls += 1
 
@@ -407,7 +409,11 @@ class RecordedTrainStep:
         clip = getattr(optimizer, 'max_grad_norm', None)
         key = key + (('max_grad_norm', float(clip)),) if clip else key
         # (the guard: whether the guard finalize and the guarded Adam kernels were recorded.  Off: today's key.)
-        return key + (('skip_nonfinite', True),) if getattr(optimizer, 'skip_nonfinite', False) else key
+        key = key + (('skip_nonfinite', True),) if getattr(optimizer, 'skip_nonfinite', False) else key
+        # (the weight average: whether the lirec_ema_step launches were recorded, and the weight they carry by value.  Off, or an
+        #  optimiser without one: today's key.)
+        ema = getattr(optimizer, 'ema_decay', None)
+        return key + (('ema_decay', float(ema)),) if ema is not None else key
 
     def _check_core(self):
         if ops.get_gemm_mode() != self._gemm_mode:

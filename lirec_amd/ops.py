@@ -885,6 +885,29 @@ class adam_guard:
         return False
 
 
+def ema_weight(decay):
+    """the fp32 weight of one EMA update: the rounding of the double 1.0 - decay, as torch casts the Python scalar of
+    ``lerp(ema, p, 1 - decay)``; ``decay`` outside (0.5, 1) -- NaN included -- is a ValueError (torch's lerp takes another
+    branch from weight 0.5 on, which lirec_ema_step does not implement)"""
+    d = float(decay)
+    if not 0.5 < d < 1.0:
+        raise ValueError('ema_decay must satisfy 0.5 < decay < 1, not %r' % (decay,))
+    w = C.c_float(1.0 - d).value
+    if not 0.0 < w < 0.5:
+        raise ValueError('ema_decay %r leaves no fp32 weight in (0, 0.5)' % (decay,))
+    return w
+
+
+def ema_step(ema, p, weight, guard=None):
+    """lirec_ema_step: ``ema`` <- fmaf(weight, p - ema, ema) elementwise (torch's ``ema.lerp_(p, weight)``, weight < 0.5, bit
+    for bit), one launch on the current stream; ``ema`` and ``p``: contiguous fp32 device tensors of one length, at the same
+    offset modulo 16 bytes.  ``guard``: the ``out`` block of clip_finalize_guard -- the launch does nothing when ``guard[2]`` is set."""
+    n = ema.numel()
+    assert p.numel() == n and ema.is_contiguous() and p.is_contiguous() and ema.dtype == torch.float32 and p.dtype == torch.float32
+    assert guard is None or (guard.dtype == torch.float32 and guard.numel() >= 3 and guard.is_contiguous())
+    check(lib().lirec_ema_step(_p(ema), _p(p), n, float(weight), _p(guard), _stream()), 'lirec_ema_step')
+
+
 def counter_add(ctr, incs):
     """ctr[i] += incs[i] on the device (ctr: int64 device tensor, len(incs) <= 4)."""
     assert ctr.dtype == torch.int64 and ctr.is_cuda and 1 <= len(incs) <= 4 and ctr.numel() >= len(incs)

@@ -61,9 +61,22 @@ Between two changes of the frozen set a trainable parameter has received ``_step
 with steps skipped, the optimiser FOLDS S into ``_step`` and the frozen parameters' lags (one read of S, a synchronisation at a
 rare event) -- legal only where the step is by value: at the top of an eager ``step()``, before a recording attaches its counters.
 The gradients stay as backward left them, non-finite values included.
+
+An exponential moving average of the weights (``ema_decay``, off by default; ``torch.optim.swa_utils.AveragedModel(model,
+multi_avg_fn=get_ema_multi_avg_fn(decay))``, timm's ``ModelEmaV2``): ``optimizer.ema`` is a second flat buffer, a copy of the
+parameters at the moment the average is switched on, and every APPLIED step is one ``ema.lerp_(p, 1 - decay)`` -- torch's bits
+(``lirec_ema_step``).  The lerp of a stretch of the buffer is a library launch directly behind that stretch's Adam launch, on that
+launch's stream: a recorded step contains it, the side stream's bucket and a rank's own slices are averaged where they are
+updated, and on the guarded route the launch reads the flag, so a skipped step is no update of the average either.  The shadow
+covers the WHOLE buffer (lerp(e, p) with e == p is e -- up to the sign of a zero: fmaf(w, +0, -0) is +0, in torch too --: a
+parameter frozen from the start stays identical to its shadow, one frozen after it has trained keeps converging to its resting
+value; the alignment gaps, zeros in both buffers, stay zeros).  ``ema_weights()`` evaluates with the average, ``ema_state_dict()``
+is what a checkpoint keeps; ``state_dict()`` is unchanged.  timm's semantics; ``AveragedModel`` differs in its first update, which
+copies: ``ema_reset()`` after the first step reproduces it.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import torch
@@ -90,7 +103,7 @@ class FusedAdam(torch.optim.Optimizer):
             raise ValueError('Invalid weight_decay value: {}'.format(weight_decay))
 
     def __init__(self, model, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5, max_grad_norm=None, param_groups=None,
-                 device_hyper=None, amsgrad=False, decoupled_weight_decay=False, skip_nonfinite=False):
+                 device_hyper=None, amsgrad=False, decoupled_weight_decay=False, skip_nonfinite=False, ema_decay=None):
         self.model = model
         params = list(model.parameters())
         self._names = [n for n, _ in model.named_parameters()]        # (in the order of model._plist)
@@ -134,6 +147,166 @@ class FusedAdam(torch.optim.Optimizer):
         self._skipped_dev = None       # device int64[1]: S, the steps skipped since the last fold
         self._skipped_folded = 0       # skipped steps already folded into _step (skipped_total)
         self._guard_flags = None       # the requires_grad flags of the interval S counts in; None: no guarded step since the fold (S = 0)
+        self._guard_now = False
+        self._ema = None               # the flat shadow (allocated by _ensure_state once ema_decay is set; kept when it is switched off)
+        self._ema_decay = self._ema_w = None
+        self._ema_calls = 0            # steps issued with the average on since the count was last folded ...
+        self._ema_skip_base = 0        # ... and skipped_total() at that moment: ema_updates() = done + calls - skipped since
+        self._ema_done = 0
+        self.ema_decay = ema_decay     # None: off; settable between steps (a recorded step is recorded again)
+
+    # -- exponential moving average of the weights ----------------------------------
+    @property
+    def ema_decay(self):
+        return self._ema_decay
+
+    @ema_decay.setter
+    def ema_decay(self, decay):
+        w = None if decay is None else ops.ema_weight(decay)      # (ValueError unless 0.5 < decay < 1)
+        if (decay is None) != (self._ema_decay is None):
+            if decay is None:
+                self._ema_done, self._ema_calls = self.ema_updates(), 0
+            else:
+                self._ema_calls, self._ema_skip_base = 0, self.skipped_total()
+        self._ema_decay, self._ema_w = (None if decay is None else float(decay)), w
+        if decay is not None and self._m is not None:
+            self._ensure_state()       # (switched on in the middle of a run: the shadow is the parameters as they are NOW)
+
+    @property
+    def ema(self):
+        """the flat shadow (laid out as ``model.flat_params()``), or None while the average has never been on"""
+        return self._ema
+
+    def _ensure_ema(self, flat, force=False):
+        """the shadow on the parameters' device: made as a copy of them, or re-made from its per-parameter views after a move"""
+        if self._ema is not None and self._ema.device == flat.device and self._ema.numel() == flat.numel():
+            return
+        if self._ema is None and self._ema_decay is None and not force:
+            return
+        if ops.CommandList.mark() >= 0:
+            raise RuntimeError('FusedAdam: the EMA shadow cannot be made while a step is being recorded; set ema_decay before')
+        if hasattr(self.model, 'join_side_streams'):
+            self.model.join_side_streams()
+        old = getattr(self, '_ema_views', None) if self._ema is not None else None
+        self._ema = flat.clone()
+        self._ema_views = {}
+        for n, (off, k) in self.model._offsets.items():
+            view = self._ema[off:off + k]
+            if old is not None and n in old and old[n].numel() == k:
+                view.copy_(old[n])
+            self._ema_views[n] = view
+        if old is None:
+            self._ema_done, self._ema_calls, self._ema_skip_base = 0, 0, self.skipped_total()
+        if flat.is_cuda:
+            # (as for the moments in _ensure_state: the first lerp may run on another stream than the one that made the copy)
+            torch.cuda.current_stream(flat.device).synchronize()
+
+    def ema_updates(self):
+        """the lerps applied to the shadow since it was last (re)initialised, as a host int: steps taken with the average on,
+        less the ones the guard skipped (one read of the device count when a guard has been on: synchronises, as
+        ``skipped_total()`` does)"""
+        if self._ema_decay is None:
+            return self._ema_done
+        return self._ema_done + self._ema_calls - max(0, self.skipped_total() - self._ema_skip_base)
+
+    def _advance_ema(self):
+        """one step has been issued (the eager step(), a replay: lirec_amd.graph)"""
+        if self._ema_decay is not None:
+            self._ema_calls += 1
+
+    def _ema_not_recording(self, what):
+        if ops.CommandList.mark() >= 0:
+            raise RuntimeError('FusedAdam.%s: not while a step is being recorded (a command list holds launches, not this copy)' % what)
+
+    @torch.no_grad()
+    def ema_reset(self):
+        """shadow <- parameters, count <- 0 (``AveragedModel``'s first update is this copy)"""
+        self._ema_not_recording('ema_reset()')
+        self._ensure_state()
+        self._ensure_ema(self.model.flat_params(), force=True)
+        if hasattr(self.model, 'join_side_streams'):
+            self.model.join_side_streams()
+        self._ema.copy_(self.model.flat_params())
+        self._ema_done, self._ema_calls, self._ema_skip_base = 0, 0, self.skipped_total()
+
+    def _ema_stale(self):
+        sync = getattr(self.model, 'grad_sync', None)
+        return sync is not None and sync.sharded and sync.real_world > 1 and getattr(self, '_consolidated_at', None) != self._step
+
+    def ema_state_dict(self):
+        """name -> tensor, shaped like ``model.state_dict()``: the averaged parameters as views of the shadow (buffers, if the model
+        has any, as the model holds them).  Loads into a fresh model with ``load_state_dict``."""
+        from collections import OrderedDict
+        self._ensure_state()
+        self._ensure_ema(self.model.flat_params(), force=True)
+        sd = self.model.state_dict()             # (joins the side stream: its lerp may still be running behind a replayed step)
+        if self._ema_stale():
+            import warnings
+            warnings.warn('FusedAdam.ema_state_dict(): sharded data-parallel update -- the shadow outside this rank\'s slices is stale; '
+                          'call optimizer.consolidate_state() on EVERY rank first (a collective)', RuntimeWarning, stacklevel=2)
+        out = OrderedDict()
+        for k, v in sd.items():
+            if k in self.model._offsets:
+                off, n = self.model._offsets[k]
+                out[k] = self._ema[off:off + n].view(v.shape)
+            else:
+                out[k] = v
+        return out
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, sd, updates=None):
+        """the shadow from ``sd`` (every parameter of the model must be in it, with its shape); ``updates``: the count to go on from"""
+        self._ema_not_recording('load_ema_state_dict()')
+        self._ensure_state()
+        self._ensure_ema(self.model.flat_params(), force=True)
+        missing = [n for n in self.model._offsets if n not in sd]
+        if missing:
+            raise KeyError('FusedAdam.load_ema_state_dict: missing %s' % ', '.join(missing))
+        if hasattr(self.model, 'join_side_streams'):
+            self.model.join_side_streams()
+        for n, (off, k) in self.model._offsets.items():
+            t = torch.as_tensor(sd[n])
+            if t.numel() != k:
+                raise ValueError('FusedAdam.load_ema_state_dict: %s has %d elements, the model\'s has %d' % (n, t.numel(), k))
+            self._ema[off:off + k].copy_(t.reshape(-1))
+        if updates is not None:
+            self._ema_done, self._ema_calls, self._ema_skip_base = int(updates), 0, self.skipped_total()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """``with optimizer.ema_weights():`` -- the model computes with the averaged weights inside (an evaluation, a checkpoint of
+        ``model.state_dict()``), and gets its training weights back, bit for bit, on the way out.  By VALUE, through a temporary
+        copy: a recorded step holds the buffers' addresses.  In front of both directions what ``Model.load_state_dict`` does before
+        values change: the side stream joined, the q32b shadow of the first-layer weights and the gate's staged weights stale."""
+        self._ema_not_recording('ema_weights()')
+        self._ensure_state()
+        flat = self.model.flat_params()
+        self._ensure_ema(flat, force=True)
+        if self._ema_stale():
+            import warnings
+            warnings.warn('FusedAdam.ema_weights(): sharded data-parallel update -- the shadow outside this rank\'s slices is stale; '
+                          'call optimizer.consolidate_state() on EVERY rank first (a collective)', RuntimeWarning, stacklevel=3)
+
+        def about_to_write():
+            if hasattr(self.model, 'join_side_streams'):
+                self.model.join_side_streams()
+            self.model._w1q_valid = False
+            self.model._bucket0_on_side = False
+        with torch.no_grad():
+            about_to_write()
+            backup = flat.clone()
+            flat.copy_(self._ema)
+        try:
+            yield self
+        finally:
+            with torch.no_grad():
+                about_to_write()
+                flat.copy_(backup)
+
+    def _lerp(self, flat, a, b):
+        """the average of stretch [a, b) follows the stretch's update, on the stream current here; guarded on the guarded route"""
+        if self._ema_w is not None and b > a:
+            ops.ema_step(self._ema[a:b], flat[a:b], self._ema_w, guard=self._clip_out if self._guard_now else None)
 
     # -- parameter groups -------------------------------------------------------
     def resolve_device_hyper(self):
@@ -287,6 +460,7 @@ class FusedAdam(torch.optim.Optimizer):
                 #  these fills were enqueued: without this one-time wait the very first step could read the moments unzeroed.
                 #  Seen as NaN parameters in one of ~5 runs of the two-rank test, where two processes share the GPU.)
                 torch.cuda.current_stream(flat.device).synchronize()
+        self._ensure_ema(flat)
 
     def zero_grad(self, set_to_none: bool = False, counters=None, zero: bool = True):
         """One memset over the flat gradient buffer (gradient views stay attached).  ``counters`` = (int64 device tensor,
@@ -553,7 +727,14 @@ class FusedAdam(torch.optim.Optimizer):
                 if not f:
                     self._lag[n] = self._lag.get(n, 0) + 1
 
-    def _update(self, flat, g, a, b, args, g_is_slice=False, counted=None, last=True, role='main'):
+    def _update(self, flat, g, a, b, args, **kw):
+        """``_adam`` of stretch [a, b), then the stretch's share of the weight average (``ema_decay``) directly behind it on the
+        same stream -- also where nothing in the stretch is trainable and no Adam launch was issued.  Returns ``_adam``'s count."""
+        n = self._adam(flat, g, a, b, args, **kw)
+        self._lerp(flat, a, b)
+        return n
+
+    def _adam(self, flat, g, a, b, args, g_is_slice=False, counted=None, last=True, role='main'):
         """The update of stretch [a, b) of the flat buffers -- ``g``: the flat gradient buffer, or (``g_is_slice``) the b - a
         gradients of the stretch on their own.  One zero-lag range: the whole-stretch launch, as ever; nothing trainable: no
         launch; anything else: lirec_adam_step_ranges, 64 ranges a call.  ``counted`` = (count_dev, ticket): the step from the
@@ -626,6 +807,8 @@ class FusedAdam(torch.optim.Optimizer):
         # (skip_nonfinite: the clipped route, whether or not a bound is set -- `clip` from here on means "that route")
         self._guard_now = guard = bool(self.skip_nonfinite)
         clip = self._clip_now is not None or guard
+        if self._ema_w is not None and self._ema is None:
+            self._ensure_ema(flat)
         if clip:
             self._clip_buffers()
         if guard:
@@ -638,6 +821,7 @@ class FusedAdam(torch.optim.Optimizer):
                 self._step_parallel_clipped(sync, flat, g, args)
                 if self._step_dev is None:
                     self._advance_lags()
+                    self._advance_ema()
                 return loss
             # data parallel: each bucket is updated as its reduction lands, the later buckets still in flight.  Sharded
             # (the default, lirec_amd.parallel): this rank holds the summed gradients of ITS slice of the bucket only, updates
@@ -670,6 +854,8 @@ class FusedAdam(torch.optim.Optimizer):
             skip = []
             if self.model.__dict__.pop('_dw1_adam_applied', False):
                 skip.append((self.model.first_layer_range()[0], flat.numel()))
+                # (the backward's fold ran on this stream before step() was entered: the range's average follows it here)
+                self._lerp(flat, *skip[0])
             elif getattr(self.model, '_w1q_valid', False):
                 # (... unless the first layers are frozen altogether: nothing writes those weights, the shadow stays current)
                 if self._all_live or self.trainable_ranges(*self.model.first_layer_range()[:2]):
@@ -706,12 +892,16 @@ class FusedAdam(torch.optim.Optimizer):
                         # has COMPLETED; the update launch reads it (+ 1) and its last workgroup advances it (round 6: the
                         # one-thread counter launch that used to stand in front of it waited 43 us on average for a CU)
                         # (stretches with nothing trainable issue no launch; the counter is advanced all the same)
-                        rs = [(a, b) for a, b in self._minus(0, hi0, skip) if self._all_live or self.trainable_ranges(a, b)]
+                        stretches = self._minus(0, hi0, skip)
+                        rs = [(a, b) for a, b in stretches if self._all_live or self.trainable_ranges(a, b)]
                         if not rs:
                             ops.counter_add(self._step_side_dev, [1])
                         for i, (a, b) in enumerate(rs):
                             self._update(flat, g, a, b, args, counted=(self._step_side_dev, self._side_ticket), last=(i == len(rs) - 1),
                                          role='side')
+                        for a, b in stretches:            # (nothing trainable, no launch above: the average moves all the same)
+                            if (a, b) not in rs:
+                                self._lerp(flat, a, b)
                     else:
                         update(0, hi0, 'side')
                 update(hi0, flat.numel())
@@ -735,6 +925,7 @@ class FusedAdam(torch.optim.Optimizer):
                     rs = [(0, flat.numel())] if self._all_live else [(a, b - a) for a, b, *_ in self.trainable_ranges()]
                     if self._clip_accumulate(g, rs, True):
                         self._clip_nothing()              # (nothing trainable: no update; norm 0, coefficient 1)
+                        self._lerp(flat, 0, flat.numel())
                     else:
                         if guard:         # (the one finalize of the step that counts)
                             self._finalize(None, 2, count=True)
@@ -744,6 +935,7 @@ class FusedAdam(torch.optim.Optimizer):
                     update(0, flat.numel())
         if self._step_dev is None:
             self._advance_lags()          # (a recorded step's caller advances the host mirrors itself, _step included)
+            self._advance_ema()
         return loss
 
     def _clip_nothing(self):
@@ -776,6 +968,8 @@ class FusedAdam(torch.optim.Optimizer):
         if first:
             if everywhere:                   # (nothing trainable at all)
                 self._clip_nothing()
+                for lo, hi in buckets:
+                    self._lerp(flat, *sync.my_slice(lo, hi))
                 return
             ops.zero_(self._clip_sq)         # (nothing trainable in this rank's slices)
         if not everywhere:
@@ -811,6 +1005,8 @@ class FusedAdam(torch.optim.Optimizer):
             for lo, hi in sync.ranges:
                 sync.gather(self._m, lo, hi)
                 sync.gather(self._v, lo, hi)
+                if self._ema is not None:
+                    sync.gather(self._ema, lo, hi)
             sync.finish_gathers()
         self._consolidated_at = self._step
 
@@ -833,6 +1029,7 @@ class FusedAdam(torch.optim.Optimizer):
                 and self._device_hyper_arg is not None:
             raise ValueError('FusedAdam.load_state_dict: the state has groups with decoupled_weight_decay (AdamW), which need '
                              'device_hyper, and device_hyper=False was asked for')
+        self._ema_done, self._ema_calls = self.ema_updates(), 0      # (the device count of skipped steps is about to be zeroed)
         super().load_state_dict(state_dict)
         for grp in self.param_groups:        # (a state written before the key existed: coupled)
             grp.setdefault('decoupled_weight_decay', False)
@@ -853,3 +1050,4 @@ class FusedAdam(torch.optim.Optimizer):
         self._ranges_key = None
         self._m = None                      # re-flatten the loaded per-parameter moments
         self._ensure_state()
+        self._ema_skip_base = self.skipped_total()

@@ -23,7 +23,7 @@ import torch
 from .config import opt
 from .loader import ThreadedLoader
 from .test import testing
-from .util import Averaging, ModelSaver, save_checkpoint
+from .util import Averaging, ModelSaver, ema_entry, save_checkpoint
 
 
 _COPY_STREAMS = {}
@@ -121,6 +121,14 @@ def training(train_dataset, **kwargs):
                            'so that its valid-row mean is the global batch\'s' % type(loss).__name__)
     batch_time, data_time, losses = Averaging(), Averaging(), Averaging()
     guarded = lambda: bool(getattr(optimizer, 'skip_nonfinite', False))
+
+    def eval_weights():
+        """opt.eval_ema: the val / test evaluations see the averaged weights (FusedAdam.ema_weights: swapped in by value, the
+        training weights restored bit for bit); otherwise nothing"""
+        if getattr(opt, 'eval_ema', False) and getattr(optimizer, 'ema_decay', None) is not None:
+            return optimizer.ema_weights()
+        import contextlib
+        return contextlib.nullcontext()
     # (a dataset may bring its own collate_fn / pin_memory -- lirec_amd.features.PiecesDataset does: de-duplicated piece
     #  tables + index instead of the tiled float64 block, built by `num_workers` THREADS (lirec_amd/loader.py says why);
     #  the protocol of mlp/train.py:33-37 is otherwise unchanged)
@@ -287,7 +295,10 @@ def training(train_dataset, **kwargs):
             testing(train_dataset, model, loss, total_iter=epoch, mode='train', train_start_time=start)
             if opt.test and val_dataset is not None:
                 # (sharded + reduced under data parallelism: the same dict on every rank)
-                check_val = testing(val_dataset, model, loss, total_iter=epoch, train_start_time=start, mode='val')
+                if getattr(opt, 'eval_ema', False) and hasattr(optimizer, 'consolidate_state') and world > 1:
+                    optimizer.consolidate_state()         # (a collective: the shadow outside a rank's slices is stale otherwise)
+                with eval_weights():
+                    check_val = testing(val_dataset, model, loss, total_iter=epoch, train_start_time=start, mode='val')
                 keep = saver.check(check_val) if rank == 0 else False
                 if world > 1:                         # rank 0 keeps the history the decision is taken against: its verdict, everywhere
                     keep = bool(parallel.all_reduce_counters({'keep': int(keep)})['keep'])
@@ -295,10 +306,15 @@ def training(train_dataset, **kwargs):
                     if hasattr(optimizer, 'consolidate_state'):
                         optimizer.consolidate_state()     # (a collective: every rank is here)
                     if rank == 0:
-                        saver.update(check_val, {'epoch': epoch, 'state_dict': copy.deepcopy(model.state_dict()),
-                                                 'optimizer': copy.deepcopy(optimizer.state_dict())}, epoch)
+                        kept = {'epoch': epoch, 'state_dict': copy.deepcopy(model.state_dict()),
+                                'optimizer': copy.deepcopy(optimizer.state_dict())}
+                        ema = ema_entry(optimizer)
+                        if ema is not None:
+                            kept['ema'] = copy.deepcopy(ema)
+                        saver.update(check_val, kept, epoch)
                     if test_dataset is not None:
-                        testing(test_dataset, model, loss, total_iter=epoch, train_start_time=start, mode='test')
+                        with eval_weights():
+                            testing(test_dataset, model, loss, total_iter=epoch, train_start_time=start, mode='test')
             print(getattr(opt, 'log_prefix', ''))
         if opt.save_model and opt.save_model_often and epoch % 30 == 0 and rank == 0:
             saver.save()

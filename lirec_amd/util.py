@@ -105,6 +105,14 @@ class ModelSaver:
                 self.saved[key][epoch] = fn
 
 
+def ema_entry(optimizer):
+    """``ck['ema']`` of a checkpoint: {'decay', 'updates', 'state_dict'} of an optimiser whose weight average is on
+    (FusedAdam.ema_decay), else None.  The state_dict has the model's keys and shapes: it loads into a model as it is."""
+    if getattr(optimizer, 'ema_decay', None) is None or not hasattr(optimizer, 'ema_state_dict'):
+        return None
+    return {'decay': float(optimizer.ema_decay), 'updates': int(optimizer.ema_updates()), 'state_dict': optimizer.ema_state_dict()}
+
+
 def save_checkpoint(path, epoch, model, optimizer):
     """COLLECTIVE under torch.distributed (every rank calls it): the sharded update's moments are gathered by all ranks, the file
     is written by rank 0 alone, and nobody returns before it is on disk."""
@@ -117,15 +125,33 @@ def save_checkpoint(path, epoch, model, optimizer):
         ck = {'epoch': epoch, 'state_dict': model.state_dict(), 'optimizer': optimizer.state_dict()}
         if len(getattr(optimizer, 'param_groups', ())) > 1 and hasattr(optimizer, 'group_names'):
             ck['param_group_names'] = optimizer.group_names()       # (who is in which group: checkpoint_to_flat needs it)
+        ema = ema_entry(optimizer)
+        if ema is not None:
+            ck['ema'] = ema                 # (beside the optimizer state, which stays what a stock Adam loads)
         torch.save(ck, path)
     if multi:
         dist.barrier()
 
 
-def load_model(name=None, path=None):
-    """``checkpoint['state_dict']`` of ``opt.resume_str`` (utils/util_functions.py:274-281)."""
+def load_model(name=None, path=None, ema=False):
+    """``checkpoint['state_dict']`` of ``opt.resume_str`` (utils/util_functions.py:274-281); ``ema``: the averaged weights the
+    checkpoint was written with (``ck['ema']['state_dict']``: same keys and shapes) -- a KeyError when it has none."""
     ck = torch.load(path or opt.resume_str, map_location='cpu', weights_only=False)
+    if ema:
+        if 'ema' not in ck:
+            raise KeyError('%s holds no EMA weights (it was written with ema_decay off)' % (path or opt.resume_str))
+        return ck['ema']['state_dict']
     return ck['state_dict']
+
+
+def load_ema(optimizer, path=None):
+    """the shadow and its count from a checkpoint written with the average on; a checkpoint without ``'ema'`` leaves the optimiser
+    as it is -- its shadow starts from the parameters.  Returns whether anything was loaded."""
+    ck = torch.load(path or opt.resume_str, map_location='cpu', weights_only=False)
+    if 'ema' not in ck:
+        return False
+    optimizer.load_ema_state_dict(ck['ema']['state_dict'], updates=ck['ema'].get('updates'))
+    return True
 
 
 def load_optimizer(path=None):

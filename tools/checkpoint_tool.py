@@ -5,6 +5,7 @@
     python tools/checkpoint_tool.py verify   ckpt.pth.tar --recipe int_rel_ch      # keys / shapes / Adam state vs the recipe's model
     python tools/checkpoint_tool.py to-flat  ckpt.pth.tar out.pt --recipe int_rel_ch
     python tools/checkpoint_tool.py from-flat flat.pt out.pth.tar --recipe int_rel_ch
+    python tools/checkpoint_tool.py ema      ckpt.pth.tar out.pth.tar              # the EMA weights as a plain checkpoint
 
 The reference's checkpoints ({'epoch', 'state_dict', 'optimizer'}, mlp/train.py:100-106) load into lirec_amd as they
 are -- same state_dict keys and shapes, same torch.optim.Adam state layout -- so "converting" one means checking it
@@ -31,7 +32,7 @@ def build_model(recipe, n_classes, n_rels):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument('cmd', choices=['inspect', 'verify', 'to-flat', 'from-flat'])
+    ap.add_argument('cmd', choices=['inspect', 'verify', 'to-flat', 'from-flat', 'ema'])
     ap.add_argument('src')
     ap.add_argument('dst', nargs='?')
     ap.add_argument('--recipe', default='int_rel_ch', choices=['modalties', 'int_rels', 'int_ch', 'int_rel_ch'])
@@ -40,6 +41,19 @@ def main():
     a = ap.parse_args()
     from lirec_amd import util
     ck = torch.load(a.src, map_location='cpu', weights_only=False)
+    if a.cmd == 'ema':
+        # the averaged weights a checkpoint was written with (FusedAdam.ema_decay) as a plain reference-layout checkpoint:
+        # {'epoch', 'state_dict'} with the model's keys -- what the reference's load_model reads; no optimizer state goes with them
+        if 'ema' not in ck:
+            sys.exit('%s holds no EMA weights (it was written with ema_decay off)' % a.src)
+        if not a.dst:
+            sys.exit('ema: give the output path')
+        sd = ck['ema']['state_dict']
+        if list(sd) != list(ck['state_dict']) or any(tuple(sd[k].shape) != tuple(ck['state_dict'][k].shape) for k in sd):
+            sys.exit('the EMA weights of %s do not have the keys / shapes of its state_dict' % a.src)
+        torch.save({'epoch': ck.get('epoch', 0), 'state_dict': type(sd)((k, v.detach().clone()) for k, v in sd.items())}, a.dst)
+        print('wrote %s (%d tensors; decay %g, %d updates)' % (a.dst, len(sd), ck['ema']['decay'], ck['ema']['updates']))
+        return
     if a.cmd == 'inspect':
         print('keys:', sorted(ck))
         if 'state_dict' in ck:
@@ -47,6 +61,8 @@ def main():
             print('epoch %s, %d tensors, %d parameters' % (ck.get('epoch'), len(ck['state_dict']), n))
             for k, v in ck['state_dict'].items():
                 print('  %-28s %s' % (k, tuple(v.shape)))
+            if 'ema' in ck:
+                print('EMA weights: decay %g, %d updates' % (ck['ema']['decay'], ck['ema']['updates']))
             st = (ck.get('optimizer') or {}).get('state') or {}
             print('optimizer state entries: %d, step %s' % (len(st), sorted({float(s['step']) for s in st.values()})))
             for i, g in enumerate((ck.get('optimizer') or {}).get('param_groups') or ()):
