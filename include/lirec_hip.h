@@ -773,6 +773,46 @@ typedef struct {
 } lirec_eval_args;
 int lirec_eval_max_tracks(const lirec_eval_args* a, lirec_stream_t stream);
 
+/* Precision.update_probs (utils/evaluation.py:68-107), the clip-level counters of the recipes WITHOUT a maximum over tracks:
+ * top-1 / 3 / 5 of the clip's label, the two soft-label counters and the confusion matrix, accumulated on the device.
+ * The reference sorts every row (np.argsort(-x)); here the order is stated without a sort.  Class j comes BEFORE class c of a
+ * row x when x[j] > x[c], or when x[j] == x[c] and j < c (comparison by value: +0 and -0 tie); a NaN comes after every number,
+ * and among NaNs the lower index first.  This is np.argsort(-x, kind='stable'), and what the reference's default argsort gives
+ * on any row without ties.  rank(c) = the number of classes before c.  Per clip b, with x = logits + b*ld_logits (C values)
+ * and y = the clip's label:
+ *     total += 1;   top1 / top3 / top5 += rank(y) < 1 / 3 / 5;   conf[y, the class of rank 0] += 1
+ *     with soft: r* = the minimum of rank(s) over the entries s of the clip's soft row that are whole numbers in [0, C)
+ *                (rows are padded with -1; duplicates are harmless); top1_sf += (r* == 0), top5_sf += (r* < 5) -- the reference's
+ *                "first of the top five that is a soft label".  A row without a valid entry counts in neither.
+ *   counters[0..5] = total, top1, top3, top5, top1_sf, top5_sf   (int64, device; [6], [7] are not touched)
+ * A LABEL OUTSIDE [0, C) COUNTS IN total ONLY: no hit and no conf entry.  The labels are device memory, which the host cannot
+ * inspect without a visit, so the call cannot refuse them (the host restatement would raise an IndexError there).
+ * One workgroup per clip: the row goes into LDS once, every thread ranks the classes it owns with C comparisons each, and the
+ * workgroup adds its sums with one integer atomic per non-zero counter and one for conf (total: one atomic per launch).
+ * INTEGER ATOMICS ONLY: the result does not depend on the order in which the workgroups arrive, run to run and bit for bit.
+ *   logits: fp32, row b at logits + b*ld_logits; ld_logits may exceed C (int_rels evaluates row 0 of each clip's group of rows,
+ *           inters.reshape(bs, -1, C)[:, 0], in place).
+ *   y:      the label of clip b is y[b * y_stride] (elements; 0 means 1): int32, with loader_types the loader's int64.
+ *   soft:   [B, n_soft], row stride ld_soft (elements): fp32, with loader_types the loader's float64.  NULL: the two soft
+ *           counters are not touched.
+ *   conf:   int64 [C, C] row-major, or NULL.
+ * Size limit: C <= LIREC_EVAL_TOPK_MAX_C (8 bytes of LDS per class -- its key and its rank -- 32 KiB at the limit; the ranking
+ * is C*C comparisons per clip, and C is 11 to 324 here).
+ * LIREC_EINVAL before any device call for: a NULL struct, logits, y or counters; B < 0, C < 1, C over the limit,
+ * ld_logits < C, y_stride < 0; soft with n_soft < 1 or ld_soft < n_soft; logits not 4-byte, counters / conf not 8-byte, y /
+ * soft not 4-byte (loader_types: 8-byte) aligned.  B == 0: no launch, LIREC_OK.  Recorded into a command list like every other
+ * launch (added to ABI 124 without a new number: a new export and a new struct, index 13 of lirec_abi_sizeof). */
+#define LIREC_EVAL_TOPK_MAX_C 4096
+typedef struct {
+  const float* logits; int64_t ld_logits; /* [B, C] */
+  const void* y; int64_t y_stride;        /* int32 (loader_types: int64) */
+  const void* soft; int64_t ld_soft;      /* [B, n_soft] fp32 (loader_types: float64) or NULL */
+  int64_t* counters;                      /* [8] in/out (accumulated) */
+  int64_t* conf;                          /* [C, C] in/out (accumulated) or NULL */
+  int32_t B, C, n_soft, loader_types;
+} lirec_eval_topk_args;
+int lirec_eval_clip_topk(const lirec_eval_topk_args* a, lirec_stream_t stream);
+
 /* ---- feature assembly ---------------------------------------------
  * The reference's loader tiles every row of the (B, T, R+1, D) feature block on the host as
  *   [ clip piece (text | clip-visual) | track-1 piece | track-2 piece ]
@@ -816,7 +856,8 @@ int lirec_dropout_mask(uint8_t* keep, int32_t rows, int32_t cols, const lirec_dr
                        int32_t site, lirec_stream_t stream);
 int lirec_version(void);
 /* sizeof() of ABI struct `which` (5 = eval; 0 embed_fwd, 1 embed_bwd, 2 margin_loss, 3 dropout,
- * 4 rowsel, 6 linear_fwd, 7 linear_bwd, 8 embed_dx) so a binding can verify its mirror; -1 if unknown */
+ * 4 rowsel, 6 linear_fwd, 7 linear_bwd, 8 embed_dx, 9 embed_dx_indexed, 10 adam_range, 11 adam_hyper, 12 adam_group_range,
+ * 13 eval_topk) so a binding can verify its mirror; -1 if unknown */
 int lirec_abi_sizeof(int which);
 /* GEMM core: 0 exact f32-input MFMA   1 one-thread-per-output HIP GEMM (bring-up cross-check)
  *            2 split-precision bf16x3 MFMA (fp32 in/out, ~2^-16 per product, up to 5.3x the f32 core)

@@ -139,6 +139,15 @@ class EvalArgs(C.Structure):
                 ('loader_types', _i32), ('reserved_', _i32)]
 
 
+class EvalTopkArgs(C.Structure):
+    """lirec_eval_topk_args: the clip-level top-k counters (lirec_eval_clip_topk)"""
+    _fields_ = [('logits', _vp), ('ld_logits', _i64), ('y', _vp), ('y_stride', _i64), ('soft', _vp), ('ld_soft', _i64),
+                ('counters', _vp), ('conf', _vp), ('B', _i32), ('C', _i32), ('n_soft', _i32), ('loader_types', _i32)]
+
+
+EVAL_TOPK_MAX_C = 4096        # LIREC_EVAL_TOPK_MAX_C
+
+
 class LirecError(RuntimeError):
     pass
 
@@ -226,6 +235,7 @@ _PROTOS = {
     'lirec_set_adam_guard': (_i32, [_vp, _vp]),
     'lirec_ema_step': (_i32, [_vp, _vp, _i64, _f32, _vp, _vp]),
     'lirec_eval_max_tracks': (_i32, [C.POINTER(EvalArgs), _vp]),
+    'lirec_eval_clip_topk': (_i32, [C.POINTER(EvalTopkArgs), _vp]),
     'lirec_cast_f64_f32': (_i32, [_vp, _vp, _i64, _vp]),
     'lirec_grid_pool': (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i64, _vp]),
     'lirec_rows_max': (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _vp]),
@@ -274,7 +284,7 @@ def lib():
     for which, st in list(enumerate((EmbedFwdArgs, EmbedBwdArgs, MarginLossArgs, Dropout, RowSel))) + [(8, EmbedDxArgs),
                                                                                                       (9, EmbedDxIndexedArgs),
                                                                                                       (10, AdamRange), (11, AdamHyper),
-                                                                                                      (12, AdamGroupRange)]:
+                                                                                                      (12, AdamGroupRange), (13, EvalTopkArgs)]:
         if L.lirec_abi_sizeof(which) != C.sizeof(st):
             raise LirecError('ABI mismatch for %s: library %d bytes, binding %d bytes'
                              % (st.__name__, L.lirec_abi_sizeof(which), C.sizeof(st)))

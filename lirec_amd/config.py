@@ -42,7 +42,9 @@ def defaults() -> dict:
         store_root='./store', sanity_check=False, log_prefix='',
         # build-side additions (not in the reference)
         dp_shard_eval=True,       # torch.distributed: testing() evaluates each clip on ONE rank and sums the counters (lirec_amd/test.py)
-        device_metrics=True,      # max-over-tracks eval counters on the GPU (lirec_eval_max_tracks), read once at the end
+        # eval counters on the GPU, read once at the end, for all four recipes: max over tracks (lirec_eval_max_tracks) and clip-level
+        # top-k / soft labels / confusion matrix (lirec_eval_clip_topk); False: the per-batch host counters (lirec_amd/test.py)
+        device_metrics=True,
         use_ce_loss=False,        # expose MultiTaskCrossEntropyLoss (dead code in create_model)
         dropout_seed=0,           # key of the counter-based dropout generator
         compact_ctx_rows=True,    # skip context rows whose rels_mask is 0 (they cannot influence any output)

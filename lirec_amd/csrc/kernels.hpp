@@ -2218,6 +2218,74 @@ __global__ __launch_bounds__(256) void eval_max_tracks_kernel(const lirec_eval_a
   }
 }
 
+// ---------------------------------------------------------------------------
+// Clip-level top-k counters (lirec_eval_clip_topk; Precision.update_probs, utils/evaluation.py:68-107).  One workgroup per clip.
+// ---------------------------------------------------------------------------
+// The order of np.argsort(-x, kind='stable') as ONE integer comparison: a key that ascends with the value, +0 and -0 on the same
+// key (they compare equal), every NaN on the lowest key (numpy sorts NaN last, and -NaN is a NaN).  Class j comes before class c
+// when key[j] > key[c], or the keys are equal and j < c.
+__device__ __forceinline__ int topk_key(float x) {
+  const int bits = __float_as_int(x), mag = bits & 0x7fffffff;       // (on the bits: subnormals stay distinct in every float mode)
+  if (mag > 0x7f800000) return (int)0x80000000;
+  if (mag == 0) return 0;
+  return bits >= 0 ? bits : (bits ^ 0x7fffffff);      // (-inf: INT_MIN + 0x7fffff, above the NaN key)
+}
+
+__global__ __launch_bounds__(256) void eval_clip_topk_kernel(const lirec_eval_topk_args a) {
+  extern __shared__ __attribute__((aligned(16))) int tk_sm[];
+  const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  const int C = a.C;
+  int* key = tk_sm;                      // [C]
+  int* rank = key + C;                   // [C]
+  int* s_pred = rank + C;                // the class of rank 0
+  int* s_rmin = s_pred + 1;              // the best rank of a valid soft label
+  const bool lt = a.loader_types != 0;
+  const float* __restrict__ x = a.logits + (long)b * a.ld_logits;
+  for (int c = tid; c < C; c += nt) key[c] = topk_key(x[c]);
+  if (tid == 0) { *s_pred = 0; *s_rmin = 0x7fffffff; }
+  __syncthreads();
+  for (int c = tid; c < C; c += nt) {
+    const int kc = key[c];
+    int before = 0;
+    for (int j = 0; j < C; ++j) {        // (every lane reads the same word: an LDS broadcast)
+      const int kj = key[j];
+      before += (kj > kc || (kj == kc && j < c)) ? 1 : 0;
+    }
+    rank[c] = before;
+    if (before == 0) *s_pred = c;        // (the order is total: exactly one class has rank 0)
+  }
+  __syncthreads();
+  if (a.soft) {
+    int best = 0x7fffffff;
+    for (int j = tid; j < a.n_soft; j += nt) {
+      const long at = (long)b * a.ld_soft + j;
+      const double v = lt ? reinterpret_cast<const double*>(a.soft)[at] : (double)reinterpret_cast<const float*>(a.soft)[at];
+      if (v >= 0.0 && v < (double)C && v == floor(v)) best = min(best, rank[(int)v]);      // (a NaN fails the first test)
+    }
+    if (best != 0x7fffffff) atomicMin(s_rmin, best);
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const long ys = a.y_stride ? (long)a.y_stride : 1;
+    const long long y = lt ? reinterpret_cast<const long long*>(a.y)[(long)b * ys]
+                           : (long long)reinterpret_cast<const int32_t*>(a.y)[(long)b * ys];
+    unsigned long long* ctr = reinterpret_cast<unsigned long long*>(a.counters);
+    if (b == 0) atomicAdd(ctr + 0, (unsigned long long)gridDim.x);      // total += B
+    if (y >= 0 && y < C) {
+      const int ry = rank[(int)y];
+      if (ry < 1) atomicAdd(ctr + 1, 1ull);
+      if (ry < 3) atomicAdd(ctr + 2, 1ull);
+      if (ry < 5) atomicAdd(ctr + 3, 1ull);
+      if (a.conf) atomicAdd(reinterpret_cast<unsigned long long*>(a.conf) + (long)y * C + *s_pred, 1ull);
+    }
+    if (a.soft) {
+      const int r = *s_rmin;
+      if (r == 0) atomicAdd(ctr + 4, 1ull);
+      if (r < 5) atomicAdd(ctr + 5, 1ull);
+    }
+  }
+}
+
 __global__ void dropout_mask_kernel(uint8_t* __restrict__ keep, int rows, int cols, unsigned seed_lo, unsigned seed_hi,
                                     const unsigned long long* __restrict__ seed_dev, unsigned site, unsigned thresh) {
   apply_seed_offset(seed_lo, seed_hi, seed_dev);

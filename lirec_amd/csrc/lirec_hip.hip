@@ -1014,6 +1014,7 @@ int lirec_abi_sizeof(int which) {
     case 10: return (int)sizeof(lirec_adam_range);
     case 11: return (int)sizeof(lirec_adam_hyper);
     case 12: return (int)sizeof(lirec_adam_group_range);
+    case 13: return (int)sizeof(lirec_eval_topk_args);
     default: return -1;
   }
 }
@@ -2674,6 +2675,22 @@ int lirec_eval_max_tracks(const lirec_eval_args* a, lirec_stream_t stream) {
   const size_t shm = ((size_t)2 * a->T * a->C + (size_t)a->T * (NR + NR1) + 512) * sizeof(float);
   if (shm > 160 * 1024) return LIREC_EINVAL;
   lirec::launch(eval_max_tracks_kernel, dim3(a->B), dim3(256), shm, (hipStream_t)stream, *a);
+  LIREC_CHECK_LAUNCH();
+  return LIREC_OK;
+}
+
+int lirec_eval_clip_topk(const lirec_eval_topk_args* a, lirec_stream_t stream) {
+  if (!a || !a->logits || !a->y || !a->counters) return LIREC_EINVAL;
+  if (a->B < 0 || a->C < 1 || a->C > LIREC_EVAL_TOPK_MAX_C || a->ld_logits < a->C || a->y_stride < 0) return LIREC_EINVAL;
+  if (a->soft && (a->n_soft < 1 || a->ld_soft < a->n_soft)) return LIREC_EINVAL;
+  const uintptr_t wide = a->loader_types ? 7 : 3;                  // the loader's int64 / float64, or int32 / fp32
+  if ((reinterpret_cast<uintptr_t>(a->logits) & 3) != 0 || (reinterpret_cast<uintptr_t>(a->y) & wide) != 0 ||
+      (reinterpret_cast<uintptr_t>(a->soft) & wide) != 0 || (reinterpret_cast<uintptr_t>(a->counters) & 7) != 0 ||
+      (reinterpret_cast<uintptr_t>(a->conf) & 7) != 0)
+    return LIREC_EINVAL;
+  if (a->B == 0) return LIREC_OK;
+  const size_t shm = ((size_t)2 * a->C + 2) * sizeof(int);          // key and rank per class, two result words
+  lirec::launch(eval_clip_topk_kernel, dim3(a->B), dim3(256), shm, (hipStream_t)stream, *a);
   LIREC_CHECK_LAUNCH();
   return LIREC_OK;
 }

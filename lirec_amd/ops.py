@@ -13,7 +13,7 @@ import threading
 import torch
 
 from . import _lib
-from ._lib import (Dropout, FusedAdamArgs, EmbedBwdArgs, EmbedDxArgs, EmbedDxIndexedArgs, EmbedFwdArgs, EvalArgs, LinearBwdArgs,
+from ._lib import (Dropout, FusedAdamArgs, EmbedBwdArgs, EmbedDxArgs, EmbedDxIndexedArgs, EmbedFwdArgs, EvalArgs, EvalTopkArgs, LinearBwdArgs,
                    LinearFwdArgs, MarginLossArgs, Pieces, RowSel, check, lib)
 
 
@@ -1062,3 +1062,33 @@ def eval_max_tracks(ints, rels, mem, y, r, g, just_zeros, counters, B, T, Cc, NR
     a.B, a.T, a.C, a.NR = B, T, Cc, NR
     a.loader_types = int(bool(loader_types))
     check(lib().lirec_eval_max_tracks(C.byref(a), _stream()), 'lirec_eval_max_tracks')
+
+
+EVAL_TOPK_COUNTERS = ('total', '_top1', '_top3', '_top5', '_top1_sf', '_top5_sf')
+
+
+def eval_clip_topk(logits, y, counters, conf=None, soft=None, y_stride=1, loader_types=False):
+    """Adds one batch to the device-side clip-level counters (int64[8], order EVAL_TOPK_COUNTERS) and, with ``conf``, to the
+    int64 [C, C] confusion matrix; Precision.update_probs, utils/evaluation.py:68-107, with the order of
+    ``np.argsort(-x, kind='stable')`` (include/lirec_hip.h).  ``logits``: fp32 [B, C], the rows may be a strided view
+    (``inters.reshape(bs, -1, C)[:, 0]``).  ``y``: 1-D, the label of clip b is ``y[b * y_stride]`` (the tensor's own stride
+    counts too).  ``soft``: [B, n_soft], padded with -1.  ``loader_types``: y int64 and soft float64, else int32 / float32."""
+    assert counters.dtype == torch.int64 and counters.numel() >= 8 and counters.is_cuda and counters.is_contiguous()
+    assert logits.dim() == 2, tuple(logits.shape)
+    B, Cc = logits.shape
+    fdt, idt = (torch.float64, torch.int64) if loader_types else (torch.float32, torch.int32)
+    assert y.dtype == idt and y.dim() == 1 and y_stride >= 1 and (B == 0 or y.numel() > (B - 1) * y_stride), (y.dtype, tuple(y.shape))
+    assert conf is None or (conf.dtype == torch.int64 and tuple(conf.shape) == (Cc, Cc) and conf.is_contiguous())
+    assert soft is None or (soft.dtype == fdt and soft.dim() == 2 and soft.shape[0] == B and soft.stride(1) == 1), 'soft labels'
+    if B == 0:                # (an empty tensor has no address to hand over; the library's answer to B == 0 is "no launch" too)
+        return
+    a = EvalTopkArgs()
+    # (a dimension of one element may carry any stride: the row stride only matters from the second row on)
+    a.logits, a.ld_logits = _p(_f32c(logits)), (logits.stride(0) if B > 1 else Cc)
+    a.y, a.y_stride = _p(y), (y.stride(0) * y_stride if y.numel() > 1 else 1)
+    if soft is not None:
+        a.soft, a.ld_soft, a.n_soft = _p(soft), (soft.stride(0) if B > 1 else soft.shape[1]), soft.shape[1]
+    a.counters, a.conf = _p(counters), _p(conf)
+    a.B, a.C = B, Cc
+    a.loader_types = int(bool(loader_types))
+    check(lib().lirec_eval_clip_topk(C.byref(a), _stream()), 'lirec_eval_clip_topk')

@@ -2,13 +2,15 @@
 
 ``testing(dataset, model, loss, total_iter, mode, train_start_time)`` keeps the reference's
 signature, per-recipe metric routing (mlp/test.py:43-92) and returned dict (:138-145).  The
-model/loss calls run on the GPU.  For the max-over-tracks recipes (``tr_maximize``) the counters are
-accumulated ON THE GPU by ``lirec_eval_max_tracks`` and the loss is summed there too: one
-device-to-host copy per evaluation (``opt.device_metrics``) instead of the reference's
-per-batch ``.item()`` + ``.cpu()`` of every logit (:42, :50-67).  The other recipes (and
-``device_metrics=False``) keep the host counters on logits copied back once per batch.  Differences,
-on purpose: no interaction-name file is read (:29-32 only builds an unused table), and clips/s is
-printed next to the metrics.
+model/loss calls run on the GPU.  The counters are accumulated ON THE GPU and the loss is summed there
+too (``opt.device_metrics``) instead of the reference's per-batch ``.item()`` + ``.cpu()``
+of every logit (:42, :50-67): by ``lirec_eval_max_tracks`` for the max-over-tracks recipes
+(``tr_maximize``), by ``lirec_eval_clip_topk`` (top-1 / 3 / 5, soft labels, confusion matrix) for the
+others.  The per-pair relationship scores of ``rels_multitask`` are the one thing still summed on the
+host: their logits wait in a device buffer and come back in ONE copy after the loop, so the sums keep
+the host path's order bit for bit.  ``device_metrics=False`` and ``ints != 1`` keep the host
+counters on logits copied back once per batch.  Differences, on purpose: no interaction-name file is
+read (:29-32 only builds an unused table), and clips/s is printed next to the metrics.
 """
 from __future__ import annotations
 
@@ -47,8 +49,12 @@ def testing(test_dataset, model, loss, total_iter=1, mode='val', train_start_tim
     conf_mat = np.zeros((test_dataset.n_classes, test_dataset.n_classes))
     total_tracks, n_clips, t0 = 0, 0, time.time()
     on_device = bool(getattr(opt, 'device_metrics', True)) and opt.tr_maximize and not opt.soft_gt and opt.ints == 1
-    dev_counters = dev_loss = None
-    n_batches = 0
+    # the recipes without a maximum over tracks: clip-level counters by lirec_eval_clip_topk
+    on_device_topk = (bool(getattr(opt, 'device_metrics', True)) and str(opt.device).startswith('cuda') and opt.ints == 1
+                      and not opt.tr_maximize)
+    dev_counters = dev_loss = dev_conf = dev_rels = None
+    n_batches = n_out = rels_at = 0
+    rels_parts = []                                   # (offset, rows, labelled rows, their labels, their pair hashes) per batch
     with torch.no_grad():
         to_dev = getattr(test_dataset, 'to_device', None) if (on_device and str(opt.device).startswith('cuda')) else None
         for idx, batch in enumerate(loader):
@@ -81,6 +87,42 @@ def testing(test_dataset, model, loss, total_iter=1, mode='val', train_start_tim
                                     dv(batch['rels_label'].long()) if rels is not None else None,
                                     dv(batch['gt_tracks'].long()), dv(batch['just_zeros'].to(torch.bool)), dev_counters,
                                     bs, Tn, ints.shape[-1], rels.shape[-1] if rels is not None else 0, loader_types=True)
+                continue
+            if on_device_topk:
+                # counters, confusion matrix and loss stay on the GPU, the relationship logits wait there: nothing is copied back
+                # inside the loop.  The batch itself stays where the loader left it: its labels go up, a few bytes.
+                ints = out['inters']
+                if dev_counters is None:
+                    dev_counters = torch.zeros(8, dtype=torch.int64, device=ints.device)
+                    dev_conf = torch.zeros(conf_mat.shape, dtype=torch.int64, device=ints.device)
+                    dev_loss = torch.zeros(1, dtype=torch.float64, device=ints.device)
+                dev_loss += lv.detach().reshape(-1)[:1]
+                n_batches, n_out = n_batches + 1, len(out)        # sic: the average is weighted by len(output dict) (:42)
+                bs = labels.shape[0]
+                dv = lambda t: t.to(ints.device, non_blocking=True)
+                if opt.soft_gt:
+                    ops.eval_clip_topk(ints, dv(labels.long()).reshape(-1), dev_counters, conf=dev_conf,
+                                       soft=dv(batch['soft_labels'].double()).reshape(bs, -1), loader_types=True)
+                elif opt.rels_multitask:
+                    # row 0 of each clip's group of rows and labels[:, 0], both read in place
+                    ops.eval_clip_topk(ints.reshape(bs, -1, ints.shape[-1])[:, 0], dv(labels.long()).reshape(-1), dev_counters,
+                                       conf=dev_conf, y_stride=labels.numel() // bs, loader_types=True)
+                    if opt.ctx == 1:
+                        rl = out['rels'].detach().reshape(bs, -1)
+                        if dev_rels is None:              # one buffer for the clips this process evaluates
+                            n_share = len(sampler.indices()) if sampler is not None else len(test_dataset)
+                            dev_rels = torch.empty(max(n_share, bs), rl.shape[1], dtype=rl.dtype, device=rl.device)
+                        if rels_at + bs > dev_rels.shape[0]:          # (a dataset that yields more clips than its length)
+                            dev_rels = torch.cat([dev_rels, torch.empty_like(dev_rels)])
+                        dev_rels[rels_at:rels_at + bs].copy_(rl)
+                        sel = torch.nonzero(batch['rels_label'] - n_rels + 1)         # the loader's host tensors
+                        if sel.shape[0]:
+                            rels_parts.append((rels_at, bs, sel, batch['rels_label'][sel].squeeze(1), batch['hash_rel'][sel].squeeze(1)))
+                        rels_at += bs
+                else:
+                    if opt.tracks:
+                        total_tracks += int(np.sum(batch['just_zeros'].cpu().numpy()))       # (a host tensor of the loader)
+                    ops.eval_clip_topk(ints, dv(labels.long()).reshape(-1), dev_counters, conf=dev_conf, loader_types=True)
                 continue
             losses.update(lv.item(), len(out))        # sic: weighted by len(output dict) (:42)
             inters = out['inters'].cpu() if out.get('inters') is not None else None
@@ -115,6 +157,17 @@ def testing(test_dataset, model, loss, total_iter=1, mode='val', train_start_tim
     if on_device and dev_counters is not None:
         prec.add_device_counters(dev_counters)                    # the only device-to-host copies of the evaluation
         losses.update(float(dev_loss) / max(n_batches, 1), max(n_batches, 1))
+    if on_device_topk and dev_counters is not None:
+        # the evaluation's device-to-host copies: the counters, the confusion matrix, the loss and the relationship logits
+        prec.add_device_topk_counters(dev_counters)
+        conf_mat += dev_conf.cpu().numpy()
+        losses.val = float(dev_loss) / n_batches
+        losses.sum, losses.count = float(dev_loss) * n_out, n_out * n_batches
+        losses.avg = losses.sum / losses.count
+        if rels_parts:
+            rels_host = dev_rels[:rels_at].cpu()
+            for at, bs, sel, gt_rel, hashes in rels_parts:            # batch by batch, in order: the host path's sums
+                prec_rels.update(rels_host[at:at + bs][sel].squeeze(1), gt_rel, hashes)
     if sharded:
         # the ranks' sums become the dataset's: Precision's counters, the loss average's numerator and denominator, the clip
         # counts -- one small all-reduce -- then the confusion matrix and the per-pair relationship scores
@@ -161,7 +214,8 @@ def testing(test_dataset, model, loss, total_iter=1, mode='val', train_start_tim
         say('%s rel+int: %f' % (mode.upper(), out_val))
 
     out = {'total': out_val, 'ints': out_ints}
-    testing.last = {'precision': prec, 'relationships': prec_rels, 'conf_mat': conf_mat, 'loss': losses.avg, 'n_clips': n_clips}
+    testing.last = {'precision': prec, 'relationships': prec_rels, 'conf_mat': conf_mat, 'loss': losses.avg, 'n_clips': n_clips,
+                    'metrics_on_device': bool(on_device or on_device_topk)}
     if opt.rels_multitask:
         out['rels'] = out_rels
     if opt.tr_maximize:
