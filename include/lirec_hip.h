@@ -813,6 +813,54 @@ typedef struct {
 } lirec_eval_topk_args;
 int lirec_eval_clip_topk(const lirec_eval_topk_args* a, lirec_stream_t stream);
 
+/* ---- predictions on the device ---------------------------------------------------
+ * What the two evaluation calls decide per clip, WITHOUT labels: the answer for a clip instead of a counter.  One workgroup per
+ * clip; every output element has one writer, no atomics: two launches on the same inputs give the same bytes.
+ * Per clip b (lirec_eval_max_tracks stays the statement of record for these rules):
+ *   a padded track (mem[b, t] == 0) has logits of -inf;  S = sigmoid(ints), Q = sigmoid(rels), in float;
+ *   with rels a "None" column Q[t, NR] = 0 is appended;
+ *   joint score: S[t, c] (float) without rels, (double)S[t, c] + (double)Q[t, r] with rels;
+ *   (trk, cls[, rel]) = the FIRST flat index of its maximum in (t, c[, r]) order -- np.argmax over the reference's tiled tensor
+ *   (utils/evaluation.py:144-147, :229-235), pairs that round to the same double included.
+ * T = 1 with mem = NULL is the clip-level form (the recipes without a maximum over tracks).
+ * Outputs (device; every pointer except `trk` may be NULL = not wanted):
+ *   trk, cls, rel   int32 [B]     the joint prediction; rel in [0, NR] (NR = None), -1 without rels
+ *   score           double [B]    the joint maximum
+ *   trk_score       double [B, T] per track, max_c S (+ max_r Q over the NR + 1 columns, in double)
+ *   top_cls         int32 [B, K]  the first min(K, C) classes of the PREDICTED track, ordered by that track's masked logits under
+ *                                 the order of lirec_eval_clip_topk (value descending, the lower index first on ties, +0 == -0, NaN
+ *                                 last); the remaining entries are -1
+ *   top_cls_p       float [B, K]  the sigmoids of those classes; the remaining entries are 0
+ *   top_rel, top_rel_p            the same over the NR real relationship logits of the predicted track; written only with rels
+ *   flags           int32 [B]     bit 0: a NaN among the clip's unmasked logits; bit 1: no valid track (every mem entry is 0)
+ * Two corners:
+ *   top_cls[b, 0] is ordered by LOGIT, cls[b] by PROBABILITY: they can differ only where two different logits give the same float
+ *   probability (a saturated sigmoid) -- top_cls then names the larger logit, cls the lower index.
+ *   A clip with flag bit 1 has trk = cls = 0 (rel = 0 with rels) and scores of 0.  For a clip with flag bit 0 the joint fields
+ *   (trk, cls, rel, score, trk_score) are whatever the shared argmax gives on NaN -- valid indices, otherwise not pinned; the top
+ *   lists still put every NaN last.
+ * mem: fp32, with loader_types the loader's float64, read in place.
+ * Size limit: 4 * (T*C + T*(NR+1) + C + NR) + 8*T + 144 bytes of LDS per clip (the NR terms only with rels; probabilities, the two
+ * rows of keys, the per-track maxima and the reduction slots) must not exceed 160 KiB (C = 101, NR = 15: T <= 342 with rels).
+ * LIREC_EINVAL before any device call for: a NULL struct, ints or trk; B < 0, T < 1, C < 1, K outside 1..LIREC_PREDICT_MAX_K,
+ * ld_ints < C; rels with NR < 1 or ld_rels < NR; a pointer that is not 4-byte aligned (8-byte: score, trk_score, and mem with
+ * loader_types); a clip over the LDS limit.  B == 0: no launch, LIREC_OK.  Recorded into a command list like every other launch
+ * (added to ABI 124 without a new number: a new export and a new struct, index 15 of lirec_abi_sizeof). */
+#define LIREC_PREDICT_MAX_K 16
+typedef struct {
+  const float* ints; int64_t ld_ints;     /* [B*T, C] logits */
+  const float* rels; int64_t ld_rels;     /* [B*T, NR] or NULL */
+  const void* mem;                        /* [B, T] 0/1 fp32 (loader_types: float64) or NULL */
+  int32_t* trk; int32_t* cls; int32_t* rel;          /* [B] */
+  double* score;                          /* [B] */
+  double* trk_score;                      /* [B, T] */
+  int32_t* top_cls; float* top_cls_p;     /* [B, K] */
+  int32_t* top_rel; float* top_rel_p;     /* [B, K] */
+  int32_t* flags;                         /* [B] */
+  int32_t B, T, C, NR, K, loader_types;
+} lirec_predict_args;
+int lirec_predict_clips(const lirec_predict_args* a, lirec_stream_t stream);
+
 /* ---- feature assembly ---------------------------------------------
  * The reference's loader tiles every row of the (B, T, R+1, D) feature block on the host as
  *   [ clip piece (text | clip-visual) | track-1 piece | track-2 piece ]
@@ -857,7 +905,7 @@ int lirec_dropout_mask(uint8_t* keep, int32_t rows, int32_t cols, const lirec_dr
 int lirec_version(void);
 /* sizeof() of ABI struct `which` (5 = eval; 0 embed_fwd, 1 embed_bwd, 2 margin_loss, 3 dropout,
  * 4 rowsel, 6 linear_fwd, 7 linear_bwd, 8 embed_dx, 9 embed_dx_indexed, 10 adam_range, 11 adam_hyper, 12 adam_group_range,
- * 13 eval_topk) so a binding can verify its mirror; -1 if unknown */
+ * 13 eval_topk, 15 predict; 14 is not assigned) so a binding can verify its mirror; -1 if unknown */
 int lirec_abi_sizeof(int which);
 /* GEMM core: 0 exact f32-input MFMA   1 one-thread-per-output HIP GEMM (bring-up cross-check)
  *            2 split-precision bf16x3 MFMA (fp32 in/out, ~2^-16 per product, up to 5.3x the f32 core)

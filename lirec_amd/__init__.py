@@ -51,3 +51,7 @@ def check_hw_queues(strict: bool = False, what: str = 'this process', need: int 
     import warnings
     warnings.warn(msg, RuntimeWarning, stacklevel=3)
     return False
+
+
+# (last: the module it lives in has the function's name, and this binding is the one the package keeps)
+from .predict import predict  # noqa: E402,F401

@@ -148,6 +148,17 @@ class EvalTopkArgs(C.Structure):
 EVAL_TOPK_MAX_C = 4096        # LIREC_EVAL_TOPK_MAX_C
 
 
+class PredictArgs(C.Structure):
+    """lirec_predict_args: per-clip predictions without labels (lirec_predict_clips)"""
+    _fields_ = [('ints', _vp), ('ld_ints', _i64), ('rels', _vp), ('ld_rels', _i64), ('mem', _vp),
+                ('trk', _vp), ('cls', _vp), ('rel', _vp), ('score', _vp), ('trk_score', _vp),
+                ('top_cls', _vp), ('top_cls_p', _vp), ('top_rel', _vp), ('top_rel_p', _vp), ('flags', _vp),
+                ('B', _i32), ('T', _i32), ('C', _i32), ('NR', _i32), ('K', _i32), ('loader_types', _i32)]
+
+
+PREDICT_MAX_K = 16            # LIREC_PREDICT_MAX_K
+
+
 class LirecError(RuntimeError):
     pass
 
@@ -236,6 +247,7 @@ _PROTOS = {
     'lirec_ema_step': (_i32, [_vp, _vp, _i64, _f32, _vp, _vp]),
     'lirec_eval_max_tracks': (_i32, [C.POINTER(EvalArgs), _vp]),
     'lirec_eval_clip_topk': (_i32, [C.POINTER(EvalTopkArgs), _vp]),
+    'lirec_predict_clips': (_i32, [C.POINTER(PredictArgs), _vp]),
     'lirec_cast_f64_f32': (_i32, [_vp, _vp, _i64, _vp]),
     'lirec_grid_pool': (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i64, _vp]),
     'lirec_rows_max': (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _vp]),
@@ -284,7 +296,8 @@ def lib():
     for which, st in list(enumerate((EmbedFwdArgs, EmbedBwdArgs, MarginLossArgs, Dropout, RowSel))) + [(8, EmbedDxArgs),
                                                                                                       (9, EmbedDxIndexedArgs),
                                                                                                       (10, AdamRange), (11, AdamHyper),
-                                                                                                      (12, AdamGroupRange), (13, EvalTopkArgs)]:
+                                                                                                      (12, AdamGroupRange), (13, EvalTopkArgs),
+                                                                                                      (15, PredictArgs)]:
         if L.lirec_abi_sizeof(which) != C.sizeof(st):
             raise LirecError('ABI mismatch for %s: library %d bytes, binding %d bytes'
                              % (st.__name__, L.lirec_abi_sizeof(which), C.sizeof(st)))

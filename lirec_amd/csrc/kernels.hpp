@@ -2088,6 +2088,55 @@ __device__ __forceinline__ int block_argmax(int n, F f, V* vred, int* ired) {
   return ri;
 }
 
+// Mt[t] = max_c S[t,c] + max_r Q[t,r], the sum in double (NR1 == 0: max_c S[t,c] alone), one wave per track
+__device__ __forceinline__ void track_maxima(const float* S, const float* Q, int T, int C, int NR1, double* Mt) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int wave = tid >> 6, lane = tid & 63, nw = nt >> 6;
+  for (int t = wave; t < T; t += nw) {
+    float sv = -__builtin_inff(), qv = -__builtin_inff();
+    int si = 0x7fffffff, qi = 0x7fffffff;
+    for (int c = lane; c < C; c += 64) argmax_take<float>(sv, si, S[t * C + c], c);
+    for (int r = lane; r < NR1; r += 64) argmax_take<float>(qv, qi, Q[t * NR1 + r], r);
+    wave_argmax<float>(sv, si);
+    wave_argmax<float>(qv, qi);
+    if (lane == 0) Mt[t] = NR1 ? (double)sv + (double)qv : (double)sv;
+  }
+  __syncthreads();
+}
+
+// The joint prediction with relationships: the first flat index, in (t, c, r) order, of the maximum of S[t,c] + Q[t,r] (sums in
+// double) -- shared by the evaluation counters and lirec_predict_clips (the rule is explained where the former calls it).
+// T <= 64: fills Mt[0..T) (track_maxima); above, the flat search, and Mt is not touched.
+__device__ __forceinline__ void joint_argmax_rels(const float* S, const float* Q, int T, int C, int NR1, double* Mt, double* dred,
+                                                  float* vred, int* ired, int& j_trk, int& j_cls, int& j_rel) {
+  if (T <= 64) {
+    track_maxima(S, Q, T, C, NR1, Mt);
+    j_trk = block_argmax<double>(T, [&](int t) { return Mt[t]; }, dred, ired);
+    const double M = Mt[j_trk];
+    const int pair = block_argmax<float>(C, [&](int c) {
+      // (1 where the class has a matching r: block_argmax then returns the lowest such c -- c-major order)
+      const double sc = (double)S[j_trk * C + c];
+      for (int r = 0; r < NR1; ++r)
+        if (sc + (double)Q[j_trk * NR1 + r] == M) return 1.f;
+      return 0.f;
+    }, vred, ired);
+    j_cls = pair;
+    j_rel = 0;
+    const double sc = (double)S[j_trk * C + j_cls];
+    for (int r = NR1 - 1; r >= 0; --r)
+      if (sc + (double)Q[j_trk * NR1 + r] == M) j_rel = r;
+  } else {
+    const int flat = block_argmax<double>(T * C * NR1, [&](int i) {
+      const int t = i / (C * NR1), rem = i - t * (C * NR1);
+      const int c = rem / NR1, r = rem - c * NR1;
+      return (double)S[t * C + c] + (double)Q[t * NR1 + r];
+    }, dred, ired);
+    j_trk = flat / (C * NR1);
+    const int rem = flat - j_trk * (C * NR1);
+    j_cls = rem / NR1; j_rel = rem - j_cls * NR1;
+  }
+}
+
 __global__ __launch_bounds__(256) void eval_max_tracks_kernel(const lirec_eval_args a) {
   extern __shared__ float sm[];
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
@@ -2146,42 +2195,7 @@ __global__ __launch_bounds__(256) void eval_max_tracks_kernel(const lirec_eval_a
       // fl(max_c S + max_r Q): one pass per track instead of T*C*(NR+1) sums.  numpy's argmax returns the FIRST flat index
       // that reaches the maximum, which may be a pair whose exact sum is smaller but rounds to the same double: after the
       // maximum M is known, the first track that reaches it is scanned for the first (c, r) with fl(S + Q) == M.
-      if (T <= 64) {
-        const int wave = tid >> 6, lane = tid & 63, nw = nt >> 6;
-        for (int t = wave; t < T; t += nw) {
-          float sv = -__builtin_inff(), qv = -__builtin_inff();
-          int si = 0x7fffffff, qi = 0x7fffffff;
-          for (int c = lane; c < C; c += 64) argmax_take<float>(sv, si, S[t * C + c], c);
-          for (int r = lane; r < NR1; r += 64) argmax_take<float>(qv, qi, Q[t * NR1 + r], r);
-          wave_argmax<float>(sv, si);
-          wave_argmax<float>(qv, qi);
-          if (lane == 0) Mt[t] = (double)sv + (double)qv;
-        }
-        __syncthreads();
-        j_trk = block_argmax<double>(T, [&](int t) { return Mt[t]; }, dred, ired);
-        const double M = Mt[j_trk];
-        const int pair = block_argmax<float>(C, [&](int c) {
-          // (1 where the class has a matching r: block_argmax then returns the lowest such c -- c-major order)
-          const double sc = (double)S[j_trk * C + c];
-          for (int r = 0; r < NR1; ++r)
-            if (sc + (double)Q[j_trk * NR1 + r] == M) return 1.f;
-          return 0.f;
-        }, vred, ired);
-        j_cls = pair;
-        j_rel = 0;
-        const double sc = (double)S[j_trk * C + j_cls];
-        for (int r = NR1 - 1; r >= 0; --r)
-          if (sc + (double)Q[j_trk * NR1 + r] == M) j_rel = r;
-      } else {
-        const int flat = block_argmax<double>(T * C * NR1, [&](int i) {
-          const int t = i / (C * NR1), rem = i - t * (C * NR1);
-          const int c = rem / NR1, r = rem - c * NR1;
-          return (double)S[t * C + c] + (double)Q[t * NR1 + r];
-        }, dred, ired);
-        j_trk = flat / (C * NR1);
-        const int rem = flat - j_trk * (C * NR1);
-        j_cls = rem / NR1; j_rel = rem - j_cls * NR1;
-      }
+      joint_argmax_rels(S, Q, T, C, NR1, Mt, dred, vred, ired, j_trk, j_cls, j_rel);
     } else {
       pr_track = block_argmax<float>(T, [&](int t) { return S[t * C + y]; }, vred, ired);
       const int flat = block_argmax<float>(T * C, [&](int i) { return S[i]; }, vred, ired);
@@ -2283,6 +2297,115 @@ __global__ __launch_bounds__(256) void eval_clip_topk_kernel(const lirec_eval_to
       if (r == 0) atomicAdd(ctr + 4, 1ull);
       if (r < 5) atomicAdd(ctr + 5, 1ull);
     }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Predictions (lirec_predict_clips): the rules of the two evaluation kernels without labels.  One workgroup per clip; every output
+// element has one writer.
+// ---------------------------------------------------------------------------
+// The first min(K, n) entries of the order topk_key defines over key[0..n), as in eval_clip_topk_kernel: every thread counts the
+// entries that come before the ones it owns, and an entry of rank < K writes slot `rank` (the order is total: one writer per
+// slot).  Slots n..K-1: -1 / 0.
+__device__ __forceinline__ void rank_select(const int* key, int n, int K, const float* __restrict__ p, int32_t* __restrict__ oi,
+                                            float* __restrict__ op) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+  for (int c = tid; c < n; c += nt) {
+    const int kc = key[c];
+    int before = 0;
+    for (int j = 0; j < n; ++j) {
+      const int kj = key[j];
+      before += (kj > kc || (kj == kc && j < c)) ? 1 : 0;
+    }
+    if (before < K) {
+      if (oi) oi[before] = c;
+      if (op) op[before] = p[c];
+    }
+  }
+  for (int s = n + tid; s < K; s += nt) {
+    if (oi) oi[s] = -1;
+    if (op) op[s] = 0.f;
+  }
+}
+
+__global__ __launch_bounds__(256) void predict_clips_kernel(const lirec_predict_args a) {
+  extern __shared__ __attribute__((aligned(16))) float pr_sm[];
+  const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  const bool has_rels = a.rels != nullptr;
+  const int T = a.T, C = a.C, K = a.K, NR = has_rels ? a.NR : 0;
+  const int NR1 = has_rels ? NR + 1 : 0;
+  float* S = pr_sm;                      // [T*C]   sigmoid of the masked logits
+  float* Q = S + T * C;                  // [T*NR1] sigmoid + the "None" column
+  int* key = reinterpret_cast<int*>(Q + T * NR1);      // [C]  topk_key of the predicted track's masked logits
+  int* rkey = key + C;                   // [NR] ... of its relationship logits
+  // behind the tables, 8-byte aligned for the doubles (the launcher's formula covers the rounding word)
+  double* dred = reinterpret_cast<double*>(pr_sm + ((T * C + T * NR1 + C + NR + 1) & ~1));   // [8] per-wave slots
+  double* Mt = dred + 8;                 // [T] per-track maxima of the joint score
+  float* vred = reinterpret_cast<float*>(Mt + T);    // [8]
+  int* ired = reinterpret_cast<int*>(vred + 8);      // [8]
+  int* flg = ired + 8;                   // [2] a NaN seen / a valid track seen
+  const bool lt = a.loader_types != 0;
+  const float* mem = reinterpret_cast<const float*>(a.mem);
+  const float NEG_INF = -__builtin_inff();
+  if (tid == 0) { flg[0] = 0; flg[1] = 0; }
+  __syncthreads();
+  bool nan = false, valid = false;
+  for (int idx = tid; idx < T * C; idx += nt) {
+    const int t = idx / C, c = idx - t * C;
+    const bool pad = mem && ld_f(mem, (long)b * T + t, lt) == 0.f;
+    const float x = pad ? NEG_INF : a.ints[((long)b * T + t) * a.ld_ints + c];
+    nan |= x != x;
+    S[idx] = sigmoidf_(x);
+  }
+  if (has_rels) {
+    for (int idx = tid; idx < T * NR; idx += nt) {
+      const int t = idx / NR, c = idx - t * NR;
+      const bool pad = mem && ld_f(mem, (long)b * T + t, lt) == 0.f;
+      const float x = pad ? NEG_INF : a.rels[((long)b * T + t) * a.ld_rels + c];
+      nan |= x != x;
+      Q[t * NR1 + c] = sigmoidf_(x);
+    }
+    for (int t = tid; t < T; t += nt) Q[t * NR1 + NR] = 0.f;
+  }
+  for (int t = tid; t < T; t += nt) valid |= !(mem && ld_f(mem, (long)b * T + t, lt) == 0.f);
+  if (nan) flg[0] = 1;                   // (every writer stores the same word)
+  if (valid) flg[1] = 1;
+  __syncthreads();
+  int j_trk = 0, j_cls = 0, j_rel = -1;
+  if (has_rels) {
+    joint_argmax_rels(S, Q, T, C, NR1, Mt, dred, vred, ired, j_trk, j_cls, j_rel);
+  } else {
+    const int flat = block_argmax<float>(T * C, [&](int i) { return S[i]; }, vred, ired);
+    j_trk = flat / C; j_cls = flat - j_trk * C;
+  }
+  if (a.trk_score) {
+    if (!has_rels || T > 64) track_maxima(S, Q, T, C, NR1, Mt);      // (with rels and T <= 64 the joint search has filled Mt)
+    for (int t = tid; t < T; t += nt) a.trk_score[(long)b * T + t] = Mt[t];
+  }
+  // the top lists of the predicted track: its masked logits once more, as keys
+  const bool want_cls = a.top_cls || a.top_cls_p, want_rel = has_rels && (a.top_rel || a.top_rel_p);
+  if (want_cls || want_rel) {
+    const long row = (long)b * T + j_trk;
+    const bool pad = mem && ld_f(mem, row, lt) == 0.f;
+    if (want_cls)
+      for (int c = tid; c < C; c += nt) key[c] = topk_key(pad ? NEG_INF : a.ints[row * a.ld_ints + c]);
+    if (want_rel)
+      for (int c = tid; c < NR; c += nt) rkey[c] = topk_key(pad ? NEG_INF : a.rels[row * a.ld_rels + c]);
+    __syncthreads();
+    if (want_cls)
+      rank_select(key, C, K, S + j_trk * C, a.top_cls ? a.top_cls + (long)b * K : nullptr,
+                  a.top_cls_p ? a.top_cls_p + (long)b * K : nullptr);
+    if (want_rel)
+      rank_select(rkey, NR, K, Q + j_trk * NR1, a.top_rel ? a.top_rel + (long)b * K : nullptr,
+                  a.top_rel_p ? a.top_rel_p + (long)b * K : nullptr);
+  }
+  if (tid == 0) {
+    a.trk[b] = j_trk;
+    if (a.cls) a.cls[b] = j_cls;
+    if (a.rel) a.rel[b] = j_rel;
+    if (a.score)
+      a.score[b] = has_rels ? (double)S[j_trk * C + j_cls] + (double)Q[j_trk * NR1 + j_rel] : (double)S[j_trk * C + j_cls];
+    if (a.flags) a.flags[b] = flg[0] | (flg[1] ? 0 : 2);
   }
 }
 

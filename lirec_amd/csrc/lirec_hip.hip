@@ -1015,6 +1015,7 @@ int lirec_abi_sizeof(int which) {
     case 11: return (int)sizeof(lirec_adam_hyper);
     case 12: return (int)sizeof(lirec_adam_group_range);
     case 13: return (int)sizeof(lirec_eval_topk_args);
+    case 15: return (int)sizeof(lirec_predict_args);         // (14 stays unassigned)
     default: return -1;
   }
 }
@@ -2691,6 +2692,25 @@ int lirec_eval_clip_topk(const lirec_eval_topk_args* a, lirec_stream_t stream) {
   if (a->B == 0) return LIREC_OK;
   const size_t shm = ((size_t)2 * a->C + 2) * sizeof(int);          // key and rank per class, two result words
   lirec::launch(eval_clip_topk_kernel, dim3(a->B), dim3(256), shm, (hipStream_t)stream, *a);
+  LIREC_CHECK_LAUNCH();
+  return LIREC_OK;
+}
+
+int lirec_predict_clips(const lirec_predict_args* a, lirec_stream_t stream) {
+  if (!a || !a->ints || !a->trk) return LIREC_EINVAL;
+  if (a->B < 0 || a->T < 1 || a->C < 1 || a->K < 1 || a->K > LIREC_PREDICT_MAX_K || a->ld_ints < a->C) return LIREC_EINVAL;
+  if (a->rels && (a->NR < 1 || a->ld_rels < a->NR)) return LIREC_EINVAL;
+  const auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+  if (((at(a->ints) | at(a->rels) | at(a->trk) | at(a->cls) | at(a->rel) | at(a->top_cls) | at(a->top_cls_p) | at(a->top_rel) |
+        at(a->top_rel_p) | at(a->flags)) & 3) != 0 ||
+      ((at(a->score) | at(a->trk_score)) & 7) != 0 || (at(a->mem) & (a->loader_types ? 7 : 3)) != 0)
+    return LIREC_EINVAL;
+  // the header's formula, in 64 bits (T * C alone may pass 2^32)
+  const uint64_t T = (uint64_t)a->T, C = (uint64_t)a->C, NR = a->rels ? (uint64_t)a->NR : 0, NR1 = a->rels ? NR + 1 : 0;
+  const uint64_t shm = 4 * (T * C + T * NR1 + C + NR) + 8 * T + 144;
+  if (shm > 160 * 1024) return LIREC_EINVAL;
+  if (a->B == 0) return LIREC_OK;
+  lirec::launch(predict_clips_kernel, dim3(a->B), dim3(256), (unsigned)shm, (hipStream_t)stream, *a);
   LIREC_CHECK_LAUNCH();
   return LIREC_OK;
 }

@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from ._lib import (Dropout, FusedAdamArgs, EmbedBwdArgs, EmbedDxArgs, EmbedDxIndexedArgs, EmbedFwdArgs, EvalArgs, EvalTopkArgs, LinearBwdArgs,
-                   LinearFwdArgs, MarginLossArgs, Pieces, RowSel, check, lib)
+                   LinearFwdArgs, MarginLossArgs, Pieces, PredictArgs, RowSel, check, lib)
 
 
 class _ThreadCell(threading.local):
@@ -1092,3 +1092,59 @@ def eval_clip_topk(logits, y, counters, conf=None, soft=None, y_stride=1, loader
     a.B, a.C = B, Cc
     a.loader_types = int(bool(loader_types))
     check(lib().lirec_eval_clip_topk(C.byref(a), _stream()), 'lirec_eval_clip_topk')
+
+
+PREDICT_FIELDS = ('trk', 'cls', 'rel', 'score', 'trk_score', 'top_cls', 'top_cls_p', 'top_rel', 'top_rel_p', 'flags')
+
+
+def predict_buffers(n, T, K, device, with_rels=True):
+    """The output arrays of ``predict_clips`` for ``n`` clips of ``T`` tracks (include/lirec_hip.h: lirec_predict_args), on
+    ``device``; ``top_rel`` / ``top_rel_p`` only ``with_rels``."""
+    i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=device)
+    out = {'trk': i32(n), 'cls': i32(n), 'rel': i32(n), 'score': torch.empty(n, dtype=torch.float64, device=device),
+           'trk_score': torch.empty(n, T, dtype=torch.float64, device=device), 'top_cls': i32(n, K),
+           'top_cls_p': torch.empty(n, K, dtype=torch.float32, device=device), 'flags': i32(n)}
+    if with_rels:
+        out['top_rel'], out['top_rel_p'] = i32(n, K), torch.empty(n, K, dtype=torch.float32, device=device)
+    return out
+
+
+def predict_clips(ints, rels=None, mem=None, B=None, T=1, K=5, loader_types=False, out=None):
+    """Per-clip predictions without labels (lirec_predict_clips, include/lirec_hip.h): the joint (track, class[, relationship])
+    argmax of the evaluation kernels, its score, the per-track scores and the top-``K`` lists of the predicted track.
+    ``ints``: fp32 [B*T, C] and ``rels``: fp32 [B*T, NR] or None -- the rows may be strided views; ``mem``: [B, T] 0/1 fp32
+    (``loader_types``: float64) or None; ``T = 1`` with ``mem = None`` is the clip-level form.  ``out``: a dict of contiguous
+    device arrays for ``B`` clips to write into (any subset of ``PREDICT_FIELDS`` that holds ``trk``; e.g. slices of
+    ``predict_buffers`` for a whole dataset) -- None: allocated here, on the logits' device.  Returns the dict."""
+    assert ints.dim() == 2, tuple(ints.shape)
+    rows, Cc = ints.shape
+    B = rows // T if B is None else B
+    assert B * T == rows and 1 <= K <= _lib.PREDICT_MAX_K, (B, T, rows, K)
+    assert rels is None or (rels.dim() == 2 and rels.shape[0] == rows), 'rels'
+    assert mem is None or (mem.dtype == (torch.float64 if loader_types else torch.float32) and mem.numel() == rows
+                           and mem.is_contiguous()), 'mem'
+    NR = rels.shape[1] if rels is not None else 0
+    if out is None:
+        out = predict_buffers(B, T, K, ints.device, with_rels=rels is not None)
+    shapes = {'trk': (B,), 'cls': (B,), 'rel': (B,), 'score': (B,), 'trk_score': (B, T), 'top_cls': (B, K), 'top_cls_p': (B, K),
+              'top_rel': (B, K), 'top_rel_p': (B, K), 'flags': (B,)}
+    dtypes = {'score': torch.float64, 'trk_score': torch.float64, 'top_cls_p': torch.float32, 'top_rel_p': torch.float32}
+    assert 'trk' in out, 'predict_clips: the output dict must hold trk'
+    for k, t in out.items():
+        assert tuple(t.shape) == shapes[k] and t.dtype == dtypes.get(k, torch.int32) and t.is_contiguous(), (k, tuple(t.shape), t.dtype)
+    if B == 0:                # (an empty tensor has no address to hand over; the library's answer to B == 0 is "no launch" too)
+        return out
+    a = PredictArgs()
+    # (a dimension of one element may carry any stride: the row stride only matters from the second row on)
+    a.ints, a.ld_ints = _p(_f32c(ints)), (ints.stride(0) if rows > 1 else Cc)
+    if rels is not None:
+        a.rels, a.ld_rels = _p(_f32c(rels)), (rels.stride(0) if rows > 1 else NR)
+    a.mem = _p(mem)
+    for k, t in out.items():
+        if k in ('top_rel', 'top_rel_p') and rels is None:
+            continue
+        setattr(a, k, _p(t))
+    a.B, a.T, a.C, a.NR, a.K = B, T, Cc, NR, K
+    a.loader_types = int(bool(loader_types))
+    check(lib().lirec_predict_clips(C.byref(a), _stream()), 'lirec_predict_clips')
+    return out
