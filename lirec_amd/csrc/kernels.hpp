@@ -1602,119 +1602,242 @@ __global__ __launch_bounds__(256) void ce_loss_kernel(const float* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------
-// K7: fused Adam over one flat buffer (torch.optim.Adam single-tensor op order)
+// K7: fused Adam over the flat buffers (torch.optim.Adam single-tensor op order; every element goes through adam4 / adam1 of
+// gemm.hpp, so every launch form gives an element the same bits for the same step and hyper-parameters).
+//
+// Two kernels, each compiled for the three ways a launch scales its gradients (AdamScale):
+//   adam_kernel        one stretch [0, n): a grid-stride loop of f32x4, then a scalar tail
+//   adam_table_kernel  a table of up to ADAM_MAX_RANGES ranges in ONE launch (the trainable parameters of a partly frozen model;
+//                      parameter groups), the hyper-parameters by value (AdamHyperByValue) or per range from a device table
+//                      (AdamHyperTable); with a clip coefficient the two table forms run kernels of their own, adam_ranges_clip_kernel
+//                      and adam_groups_clip_kernel
+// What they share is written once: the step and the scale (adam_begin), the bias corrections (adam_bias), the block -> range
+// lookup and a block's f32x4-or-tail handling (range_of_block, range_block_apply; also grad_sq_partials_kernel's), and the
+// counter's epilogue (adam_finish).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __restrict__ g,
-                                          float* __restrict__ m, float* __restrict__ v, long n,
-                                          float step_size, float bc2_sqrt, float beta1, float beta2,
-                                          float eps, float wd, float gscale, float lr,
-                                          const long long* __restrict__ step_dev,
-                                          long long* count_dev, int* ticket, int advance,
-                                          const float* __restrict__ guard = nullptr,
-                                          const long long* __restrict__ skipped = nullptr, int step = 0) {
-  // guard / skipped / step (adam_guard_kernel; null in the other two kernels, whose code they leave as it was): see there
-  // count_dev (lirec_adam_step_counted): a counter of COMPLETED steps owned by this launch's stream -- the step is *count_dev + 1,
-  // and, `advance`, the workgroup that finishes last stores it back (every workgroup has read the counter by then: a workgroup
-  // takes its ticket behind its last element) -- the one-thread counter launch in front of the side stream's update is gone
-  long long t_counted = 0;
-  if (count_dev) t_counted = __hip_atomic_load(count_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
-  if (guard) {                        // guarded: the step less the skipped ones, always from here; a set flag empties the loops
-    if (guard[2] != 0.f) n = 0;
-    long long tg = (count_dev ? t_counted : (step_dev ? *step_dev : (long long)step)) - *skipped;
-    if (tg < 1) tg = 1;
-    step_size = (float)((double)lr / (1.0 - pow((double)beta1, (double)tg)));
-    bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)tg));
-    gscale *= guard[0];
-  } else if (step_dev || count_dev) {        // step kept on the device (graph replay): same double-precision bias corrections as the host
-    const double t = count_dev ? (double)t_counted : (double)*step_dev;
-    step_size = (float)((double)lr / (1.0 - pow((double)beta1, t)));
-    bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, t));
+#define ADAM_MAX_RANGES 64
+#define ADAM_RANGE_BLOCK 1024
+#define ADAM_MAX_GROUPS 8
+
+// How a launch scales its gradients -- a template parameter, so the plain kernels hold neither loads nor branches of the others:
+//   ADAM_CLIP   (lirec_set_adam_clip): the scale is gscale * *scale, `scale` a device float that an earlier launch wrote
+//               (clip_finalize_kernel) -- one uniform load, one fp32 multiply; nothing else differs.
+//   ADAM_GUARD  (lirec_set_adam_guard): `scale` is the three-word block (coefficient, norm, skip) that clip_finalize_kernel<true>
+//               wrote and `skipped` the device count of the steps skipped so far -- uniform loads, once per launch.  skip != 0: no
+//               element is read or written (p, m, v keep their bits); the counter's epilogue runs all the same, so a counting
+//               stream stays in step.  Otherwise the step is t - *skipped with the bias corrections ALWAYS computed on the
+//               device -- a by-value step behaves as step_dev holding it: its host-computed factors belong to t, not to
+//               t - *skipped, which only the device knows -- and the scale is gscale * scale[0]: the bits of ADAM_CLIP with
+//               that coefficient and step_dev holding t - *skipped.
+enum AdamScale { ADAM_PLAIN = 0, ADAM_CLIP = 1, ADAM_GUARD = 2 };
+
+// Where a launch takes its step t from, and the operands of its scale mode.  t = *count_dev + 1, *step_dev or `step`, in that
+// order.  count_dev (lirec_adam_step_counted): a counter of COMPLETED steps owned by this launch's stream; `advance`: the launch
+// stores t back (adam_finish) -- no one-thread counter launch in front of the side stream's update.
+struct AdamStep {
+  int step;
+  const long long* step_dev;
+  long long* count_dev; int* ticket; int advance;
+  const float* scale; const long long* skipped;             // (ADAM_CLIP / ADAM_GUARD; not read otherwise)
+};
+// The five hyper-parameters by value in the launch
+struct AdamHyperArgs { float lr, beta1, beta2, eps, wd; };
+
+// The two bias-correction factors of step t, in double as the host computes them for a by-value step.  t < 1 counts as 1 (a
+// parameter's first update; a lag or a count of skipped steps can never take it below).
+__device__ __forceinline__ void adam_bias(float lr, float beta1, float beta2, long long t, float& step_size, float& bc2_sqrt) {
+  if (t < 1) t = 1;
+  step_size = (float)((double)lr / (1.0 - pow((double)beta1, (double)t)));
+  bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)t));
+}
+
+// The head of every Adam kernel: the launch's step (ADAM_GUARD: less the skipped ones), the scale folded into `gscale`, and
+// -- ADAM_GUARD with the skip flag set -- `work` (elements or blocks) emptied, which ends the kernel's loop before it begins.
+struct AdamNow { long long t, counted; };                     // counted: *count_dev + 1, what adam_finish stores back
+template <int SCALE>
+__device__ __forceinline__ AdamNow adam_begin(const AdamStep& st, float& gscale, long& work) {
+  AdamNow now;
+  now.counted = st.count_dev ? __hip_atomic_load(st.count_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1 : 0;
+  now.t = st.count_dev ? now.counted : (st.step_dev ? *st.step_dev : (long long)st.step);
+  if constexpr (SCALE == ADAM_CLIP) gscale *= *st.scale;
+  if constexpr (SCALE == ADAM_GUARD) {
+    if (st.scale[2] != 0.f) work = 0;
+    now.t -= *st.skipped;
+    gscale *= st.scale[0];
   }
-  const AdamFuse ad{p, g, m, v, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, lr, step_dev};
+  return now;
+}
+// are the bias corrections computed on the device?  (else: the host's, by value)
+template <int SCALE>
+__device__ __forceinline__ bool adam_bias_on_device(const AdamStep& st) { return SCALE == ADAM_GUARD || st.step_dev || st.count_dev; }
+
+// The tail of every Adam kernel: with `advance`, the workgroup that finishes last stores the counter back.  Every workgroup has
+// read the counter by then: a workgroup takes its ticket behind its last element.
+__device__ __forceinline__ void adam_finish(const AdamStep& st, long long counted) {
+  if (st.count_dev && st.advance) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int tk = __hip_atomic_fetch_add(st.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (tk == (int)gridDim.x - 1) {
+        __hip_atomic_store(st.count_dev, counted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(st.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);           // ready for the next launch
+      }
+    }
+  }
+}
+
+// The flat launch.  step_size / bc2_sqrt: the host's factors of a by-value step (lirec_adam_step), replaced here when the step
+// is on the device (graph replay) or the launch is guarded.
+template <int SCALE>
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                   float* __restrict__ m, float* __restrict__ v, long n, const AdamHyperArgs hy,
+                                                   float step_size, float bc2_sqrt, float gscale, const AdamStep st) {
+  const AdamNow now = adam_begin<SCALE>(st, gscale, n);
+  if (adam_bias_on_device<SCALE>(st)) adam_bias(hy.lr, hy.beta1, hy.beta2, now.t, step_size, bc2_sqrt);
+  const AdamFuse ad{p, g, m, v, step_size, bc2_sqrt, hy.beta1, hy.beta2, hy.eps, hy.wd, gscale, hy.lr, st.step_dev};
   const long stride = (long)gridDim.x * blockDim.x;
   const long n4 = n >> 2;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride)
     (void)adam4(ad, step_size, bc2_sqrt, 4 * i, reinterpret_cast<const f32x4*>(g)[i]);
   for (long i = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) (void)adam1(ad, step_size, bc2_sqrt, i, g[i]);
-  if (count_dev && advance) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const int tk = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (tk == (int)gridDim.x - 1) {
-        __hip_atomic_store(count_dev, t_counted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);           // ready for the next launch
-      }
-    }
-  }
-}
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                   float* __restrict__ m, float* __restrict__ v, long n,
-                                                   float step_size, float bc2_sqrt, float beta1, float beta2,
-                                                   float eps, float wd, float gscale, float lr,
-                                                   const long long* __restrict__ step_dev,
-                                                   long long* count_dev = nullptr, int* ticket = nullptr, int advance = 0) {
-  adam_body(p, g, m, v, n, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, lr, step_dev, count_dev, ticket, advance);
-}
-// The same launch with the gradients clipped (lirec_set_adam_clip): the scale is gscale * *coef, `coef` a device float that an
-// earlier launch wrote (clip_finalize_kernel) -- one uniform load, one fp32 multiply; nothing else differs.
-__global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                        float* __restrict__ m, float* __restrict__ v, long n,
-                                                        float step_size, float bc2_sqrt, float beta1, float beta2,
-                                                        float eps, float wd, float gscale, float lr,
-                                                        const long long* __restrict__ step_dev,
-                                                        long long* count_dev, int* ticket, int advance,
-                                                        const float* __restrict__ coef) {
-  adam_body(p, g, m, v, n, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale * *coef, lr, step_dev, count_dev, ticket, advance);
+  adam_finish(st, now.counted);
 }
 
-// Guarded (lirec_set_adam_guard): the clipped launch plus the three-word block `guard` = (coefficient, norm, skip) that
-// clip_finalize_guard_kernel wrote and the device count `skipped` of the steps skipped so far -- uniform loads, once per launch.
-// skip != 0: no element is read or written (p, m, v keep their bits); the count_dev / ticket / advance epilogue runs all the same,
-// so a counting stream stays in step.  Otherwise the step is t - *skipped (t: `step` by value, *step_dev or *count_dev + 1),
-// clamped at 1, with the bias corrections ALWAYS computed here, in double -- a by-value step behaves as step_dev holding it --
-// and the scale is gscale * guard[0]: the bits of adam_clip_kernel with that coefficient and step_dev holding t - *skipped.
-__global__ __launch_bounds__(256) void adam_guard_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                         float* __restrict__ m, float* __restrict__ v, long n,
-                                                         float beta1, float beta2, float eps, float wd, float gscale, float lr,
-                                                         int step, const long long* __restrict__ step_dev,
-                                                         long long* count_dev, int* ticket, int advance,
-                                                         const float* __restrict__ guard, const long long* __restrict__ skipped) {
-  adam_body(p, g, m, v, n, 0.f, 0.f, beta1, beta2, eps, wd, gscale, lr, step_dev, count_dev, ticket, advance, guard, skipped, step);
-}
-
-// The same update over a scattered set of ranges of the flat buffers in ONE launch (lirec_adam_step_ranges: the trainable
-// parameters of a partly frozen model).  Range r = [off[r], off[r] + len[r]) with off a multiple of 4, updated with step t - lag[r]:
-// a parameter that sat out `lag` steps frozen has received that many updates fewer (torch.optim.Adam keeps one step per
-// parameter).  The work is dealt in blocks of ADAM_RANGE_BLOCK elements numbered across the ranges (one f32x4 per thread and
-// block), a workgroup taking every gridDim.x-th; the block -> range lookup is a loop over the by-value table with nothing but
-// workgroup-uniform values in it.  Each element goes through adam4 / adam1 -- a range gives the bits adam_kernel gives on it
-// with that step.  t: by value (the host then fills step_size / bc2_sqrt per range, as lirec_adam_step does), or from step_dev
-// or the count_dev / ticket / advance triple of adam_kernel (the two factors then computed here, in double, per range).
-#define ADAM_MAX_RANGES 64
-#define ADAM_RANGE_BLOCK 1024
-struct AdamRanges {
+// A table of ranges of a flat buffer, by value in the launch: range r = [off[r], off[r] + len[r]), off[r] a multiple of 4.  The
+// work is dealt in blocks of ADAM_RANGE_BLOCK elements numbered across the ranges (one f32x4 per thread and block), a workgroup
+// taking every gridDim.x-th.
+struct RangeTable {
   long off[ADAM_MAX_RANGES], len[ADAM_MAX_RANGES];
-  int lag[ADAM_MAX_RANGES];
-  float step_size[ADAM_MAX_RANGES], bc2_sqrt[ADAM_MAX_RANGES];       // by-value step only
   int count;
 };
-// (adam_groups_body below is this body with the hyper-parameters read per range from a device table: the block -> range lookup,
-//  the tails and the ticket are the same text -- a fix to either belongs in both.  Kept apart so that this kernel's code stays
-//  what it was.)
-__device__ __forceinline__ void adam_ranges_body(float* __restrict__ p, const float* __restrict__ g,
-                                                 float* __restrict__ m, float* __restrict__ v, const AdamRanges& rt,
-                                                 long nblocks, float beta1, float beta2, float eps, float wd,
-                                                 float gscale, float lr, const long long* __restrict__ step_dev,
-                                                 long long* count_dev, int* ticket, int advance,
-                                                 const float* __restrict__ guard = nullptr,
-                                                 const long long* __restrict__ skipped = nullptr, int step = 0) {
+// block b of the numbering -> its range, b then counting within the range: a loop over the by-value table with nothing but
+// workgroup-uniform values in it
+__device__ __forceinline__ int range_of_block(const RangeTable& rt, long& b) {
+  int r = 0;
+  for (; r < rt.count - 1; ++r) {
+    const long nb = (rt.len[r] + ADAM_RANGE_BLOCK - 1) / ADAM_RANGE_BLOCK;
+    if (b < nb) break;
+    b -= nb;
+  }
+  return r;
+}
+// this thread's share of block b of range r: f4(at) where four whole elements lie at `at` of the flat buffer, f1(at) per element
+// on the range's tail
+template <class F4, class F1>
+__device__ __forceinline__ void range_block_apply(const RangeTable& rt, int r, long b, F4 f4, F1 f1) {
+  const long first = b * ADAM_RANGE_BLOCK;                  // within the range
+  long left = rt.len[r] - first;
+  if (left > ADAM_RANGE_BLOCK) left = ADAM_RANGE_BLOCK;
+  const long e = 4L * threadIdx.x;
+  const long at = rt.off[r] + first + e;
+  if (e + 4 <= left) {
+    f4(at);
+  } else {
+    for (long j = 0; e + j < left; ++j) f1(at + j);
+  }
+}
+
+// The Adam tables.  Range r is updated with step t - lag[r]: a parameter that sat out `lag` steps frozen has received that many
+// updates fewer (torch.optim.Adam keeps one step per parameter).
+struct AdamRanges : RangeTable {
+  int lag[ADAM_MAX_RANGES];
+  float step_size[ADAM_MAX_RANGES], bc2_sqrt[ADAM_MAX_RANGES];       // a by-value step's factors per range, from the host
+};
+struct AdamGroupRanges : RangeTable {
+  int lag[ADAM_MAX_RANGES];
+  unsigned char group[ADAM_MAX_RANGES];
+};
+// Where a table launch takes the hyper-parameters and the factors of a range from -- the one difference between its two forms.
+// enter(): a workgroup comes to range r (once per range it touches, workgroup-uniform); returns whether the range is decoupled.
+// By value (lirec_adam_step_ranges): the launch arguments; the factors from the host's table for a by-value step.
+struct AdamHyperByValue : AdamHyperArgs {
+  using Table = AdamRanges;
+  static constexpr bool kMayDecouple = false;
+  __device__ __forceinline__ bool enter(const Table& rt, int r, long long t, bool on_device, AdamFuse& ad, float& step_size,
+                                        float& bc2_sqrt, float&) const {
+    ad.lr = lr; ad.beta1 = beta1; ad.beta2 = beta2; ad.eps = eps; ad.wd = wd;
+    if (on_device) adam_bias(lr, beta1, beta2, t - rt.lag[r], step_size, bc2_sqrt);
+    else { step_size = rt.step_size[r]; bc2_sqrt = rt.bc2_sqrt[r]; }
+    return false;
+  }
+};
+// Parameter groups (lirec_adam_step_groups): row group[r] of a table in DEVICE memory (AdamHyperRow, written by
+// adam_hyper_write_kernel in stream order) -- a recorded launch holds the table's address and every replay reads the values anew.
+// The factors are ALWAYS computed on the device, from the row's values -- a by-value step t behaves as step_dev holding t -- so a
+// range gets the bits of adam_kernel with step_dev on it with the row's values.  A row whose `decoupled` word is not 0 takes the
+// AdamW form of adam4 / adam1 on its ranges; a launch may mix the two.
+struct AdamHyperTable {
+  using Table = AdamGroupRanges;
+  static constexpr bool kMayDecouple = true;
+  const AdamHyperRow* __restrict__ table;
+  __device__ __forceinline__ bool enter(const Table& rt, int r, long long t, bool, AdamFuse& ad, float& step_size,
+                                        float& bc2_sqrt, float& decay) const {
+    const AdamHyperRow h = table[rt.group[r]];
+    ad.lr = h.lr; ad.beta1 = h.beta1; ad.beta2 = h.beta2; ad.eps = h.eps; ad.wd = h.wd;
+    decay = adam_decay(h);
+    adam_bias(h.lr, h.beta1, h.beta2, t - rt.lag[r], step_size, bc2_sqrt);
+    return h.decoupled != 0.f;
+  }
+};
+// The table's rows by value, as words: thread i of the one wave stores word i (vector stores)
+struct AdamHyperWords {
+  float w[ADAM_MAX_GROUPS * 8];
+};
+__global__ __launch_bounds__(64) void adam_hyper_write_kernel(float* __restrict__ table, const AdamHyperWords rows, int n_words) {
+  static_assert(sizeof(AdamHyperRow) == 32 && ADAM_MAX_GROUPS * 8 == 64, "one word per lane");
+  const int i = threadIdx.x;
+  if (i < n_words) table[i] = rows.w[i];
+}
+
+template <bool DECOUPLED>
+__device__ __forceinline__ void adam_range_block(const AdamFuse& ad, const RangeTable& rt, int r, long b, float step_size,
+                                                 float bc2_sqrt, float decay) {
+  range_block_apply(
+      rt, r, b, [&](long at) { (void)adam4<DECOUPLED>(ad, step_size, bc2_sqrt, at, *reinterpret_cast<const f32x4*>(ad.g + at), decay); },
+      [&](long at) { (void)adam1<DECOUPLED>(ad, step_size, bc2_sqrt, at, ad.g[at], decay); });
+}
+// The table launch: a range gives the bits adam_kernel gives on it with that range's step and hyper-parameters.
+template <int SCALE, class Hyper>
+__global__ __launch_bounds__(256) void adam_table_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                         float* __restrict__ m, float* __restrict__ v,
+                                                         const typename Hyper::Table rt, long nblocks, const Hyper hy,
+                                                         float gscale, const AdamStep st) {
+  const AdamNow now = adam_begin<SCALE>(st, gscale, nblocks);
+  const bool on_device = adam_bias_on_device<SCALE>(st);
+  AdamFuse ad{p, g, m, v, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, gscale, 0.f, st.step_dev};
+  int cur = -1;
+  float step_size = 0.f, bc2_sqrt = 1.f, decay = 1.f;
+  bool decoupled = false;       // (of the current range: workgroup-uniform)
+  for (long wb = blockIdx.x; wb < nblocks; wb += gridDim.x) {
+    long b = wb;
+    const int r = range_of_block(rt, b);
+    if (r != cur) {               // (uniform: a workgroup's blocks ascend, so once per range it touches)
+      cur = r;
+      decoupled = hy.enter(rt, r, now.t, on_device, ad, step_size, bc2_sqrt, decay);
+    }
+    if (Hyper::kMayDecouple && decoupled) adam_range_block<true>(ad, rt, r, b, step_size, bc2_sqrt, decay);
+    else adam_range_block<false>(ad, rt, r, b, step_size, bc2_sqrt, decay);
+  }
+  adam_finish(st, now.counted);
+}
+
+// The table launches with a clip coefficient keep kernels of their own, the table loop written out with scalar arguments.  On
+// adam_table_kernel<ADAM_CLIP, ...> these launch forms measured 0.2 - 0.6 us (up to 0.7 %) slower per launch at the model's size
+// than the kernels they replaced, beyond the run-to-run spread (profiles/adam_family_ab.json); the cause was not found --
+// register allocation and the place of the coefficient's load were ruled out.  The same arithmetic and work distribution, element
+// for element the bits of the template: a fix to adam_begin / adam_bias / adam_finish or to the table loop above belongs in these
+// two as well.  This one: lirec_adam_step_ranges under lirec_set_adam_clip.
+__global__ __launch_bounds__(256) void adam_ranges_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                               float* __restrict__ m, float* __restrict__ v, const AdamRanges rt,
+                                                               long nblocks, float beta1, float beta2, float eps, float wd,
+                                                               float gscale, float lr, const long long* __restrict__ step_dev,
+                                                               long long* count_dev, int* ticket, int advance,
+                                                               const float* __restrict__ coef) {
+  gscale *= *coef;
   long long t_counted = 0;
   if (count_dev) t_counted = __hip_atomic_load(count_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
-  // (guarded -- adam_ranges_guard_kernel; as adam_guard_kernel -- : the device-step branch below with t less the skipped steps,
-  //  a by-value step included; a set flag ends the block loop before it begins)
-  const bool dev_step = step_dev || count_dev || guard;
-  long long t_dev = count_dev ? t_counted : (step_dev ? *step_dev : (long long)step);
-  if (guard) { t_dev -= *skipped; gscale *= guard[0]; if (guard[2] != 0.f) nblocks = 0; }
+  const bool dev_step = step_dev || count_dev;
+  const long long t_dev = count_dev ? t_counted : (step_dev ? *step_dev : 0);
   const AdamFuse ad{p, g, m, v, 0.f, 0.f, beta1, beta2, eps, wd, gscale, lr, step_dev};
   int cur = -1;
   float step_size = 0.f, bc2_sqrt = 1.f;
@@ -1759,70 +1882,18 @@ __device__ __forceinline__ void adam_ranges_body(float* __restrict__ p, const fl
     }
   }
 }
-__global__ __launch_bounds__(256) void adam_ranges_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                          float* __restrict__ m, float* __restrict__ v, const AdamRanges rt,
-                                                          long nblocks, float beta1, float beta2, float eps, float wd,
-                                                          float gscale, float lr, const long long* __restrict__ step_dev,
-                                                          long long* count_dev, int* ticket, int advance) {
-  adam_ranges_body(p, g, m, v, rt, nblocks, beta1, beta2, eps, wd, gscale, lr, step_dev, count_dev, ticket, advance);
-}
-// ... clipped: as adam_clip_kernel
-__global__ __launch_bounds__(256) void adam_ranges_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                               float* __restrict__ m, float* __restrict__ v, const AdamRanges rt,
-                                                               long nblocks, float beta1, float beta2, float eps, float wd,
-                                                               float gscale, float lr, const long long* __restrict__ step_dev,
+// ... and so does the group-table launch with a clip coefficient (lirec_adam_step_groups under lirec_set_adam_clip), for the same
+// reason: on adam_table_kernel<ADAM_CLIP, AdamHyperTable> it measured 0.2 - 0.5 us slower than this loop, beyond the margin.
+__global__ __launch_bounds__(256) void adam_groups_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                               float* __restrict__ m, float* __restrict__ v, const AdamGroupRanges rt,
+                                                               long nblocks, const AdamHyperRow* __restrict__ table, int step,
+                                                               float gscale, const long long* __restrict__ step_dev,
                                                                long long* count_dev, int* ticket, int advance,
                                                                const float* __restrict__ coef) {
-  adam_ranges_body(p, g, m, v, rt, nblocks, beta1, beta2, eps, wd, gscale * *coef, lr, step_dev, count_dev, ticket, advance);
-}
-
-// ... guarded: as adam_guard_kernel (rt.step_size / rt.bc2_sqrt are not read)
-__global__ __launch_bounds__(256) void adam_ranges_guard_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                                float* __restrict__ m, float* __restrict__ v, const AdamRanges rt,
-                                                                long nblocks, float beta1, float beta2, float eps, float wd,
-                                                                float gscale, float lr, int step,
-                                                                const long long* __restrict__ step_dev, long long* count_dev,
-                                                                int* ticket, int advance, const float* __restrict__ guard,
-                                                                const long long* __restrict__ skipped) {
-  adam_ranges_body(p, g, m, v, rt, nblocks, beta1, beta2, eps, wd, gscale, lr, step_dev, count_dev, ticket, advance, guard, skipped,
-                   step);
-}
-
-// Parameter groups (lirec_adam_step_groups): adam_ranges_kernel with a group index per range and the five hyper-parameters of a
-// range taken from row `group` of a table in DEVICE memory (AdamHyperRow, written by adam_hyper_write_kernel in stream order), not
-// from the launch arguments -- a recorded launch holds the table's address and every replay reads the values anew.  The same work
-// distribution; the row is loaded once per range a workgroup touches, by a workgroup-uniform index.  The bias corrections are
-// ALWAYS computed here, in double, from the row's values -- a by-value step t behaves as step_dev holding t -- so a range gets the
-// bits of adam_kernel with step_dev on it with the row's values.  A row whose `decoupled` word is not 0 takes the AdamW form of
-// adam4 / adam1 on its ranges (one workgroup-uniform branch beside the row load); a launch may mix the two.
-#define ADAM_MAX_GROUPS 8
-struct AdamGroupRanges {
-  long off[ADAM_MAX_RANGES], len[ADAM_MAX_RANGES];
-  int lag[ADAM_MAX_RANGES];
-  unsigned char group[ADAM_MAX_RANGES];
-  int count;
-};
-// The table's rows by value, as words: thread i of the one wave stores word i (vector stores)
-struct AdamHyperWords {
-  float w[ADAM_MAX_GROUPS * 8];
-};
-__global__ __launch_bounds__(64) void adam_hyper_write_kernel(float* __restrict__ table, const AdamHyperWords rows, int n_words) {
-  static_assert(sizeof(AdamHyperRow) == 32 && ADAM_MAX_GROUPS * 8 == 64, "one word per lane");
-  const int i = threadIdx.x;
-  if (i < n_words) table[i] = rows.w[i];
-}
-// (a copy of adam_ranges_body above -- lookup, tails, ticket -- with the row load in place of the by-value arguments: a fix to
-//  either belongs in both)
-__device__ __forceinline__ void adam_groups_body(float* __restrict__ p, const float* __restrict__ g,
-                                                 float* __restrict__ m, float* __restrict__ v, const AdamGroupRanges& rt,
-                                                 long nblocks, const AdamHyperRow* __restrict__ table, int step, float gscale,
-                                                 const long long* __restrict__ step_dev, long long* count_dev, int* ticket,
-                                                 int advance, const float* __restrict__ guard = nullptr,
-                                                 const long long* __restrict__ skipped = nullptr) {
+  gscale *= *coef;
   long long t_counted = 0;
   if (count_dev) t_counted = __hip_atomic_load(count_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
-  long long t_dev = count_dev ? t_counted : (step_dev ? *step_dev : (long long)step);
-  if (guard) { t_dev -= *skipped; gscale *= guard[0]; if (guard[2] != 0.f) nblocks = 0; }      // (guarded: as adam_guard_kernel)
+  const long long t_dev = count_dev ? t_counted : (step_dev ? *step_dev : (long long)step);
   AdamFuse ad{p, g, m, v, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, gscale, 0.f, step_dev};
   int cur = -1;
   float step_size = 0.f, bc2_sqrt = 1.f, decay = 1.f;
@@ -1874,50 +1945,18 @@ __device__ __forceinline__ void adam_groups_body(float* __restrict__ p, const fl
     }
   }
 }
-__global__ __launch_bounds__(256) void adam_groups_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                          float* __restrict__ m, float* __restrict__ v, const AdamGroupRanges rt,
-                                                          long nblocks, const AdamHyperRow* __restrict__ table, int step,
-                                                          float gscale, const long long* __restrict__ step_dev,
-                                                          long long* count_dev, int* ticket, int advance) {
-  adam_groups_body(p, g, m, v, rt, nblocks, table, step, gscale, step_dev, count_dev, ticket, advance);
-}
-// ... clipped: as adam_clip_kernel
-__global__ __launch_bounds__(256) void adam_groups_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                               float* __restrict__ m, float* __restrict__ v, const AdamGroupRanges rt,
-                                                               long nblocks, const AdamHyperRow* __restrict__ table, int step,
-                                                               float gscale, const long long* __restrict__ step_dev,
-                                                               long long* count_dev, int* ticket, int advance,
-                                                               const float* __restrict__ coef) {
-  adam_groups_body(p, g, m, v, rt, nblocks, table, step, gscale * *coef, step_dev, count_dev, ticket, advance);
-}
-
-// ... guarded: as adam_guard_kernel, both branches
-__global__ __launch_bounds__(256) void adam_groups_guard_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                                float* __restrict__ m, float* __restrict__ v, const AdamGroupRanges rt,
-                                                                long nblocks, const AdamHyperRow* __restrict__ table, int step,
-                                                                float gscale, const long long* __restrict__ step_dev,
-                                                                long long* count_dev, int* ticket, int advance,
-                                                                const float* __restrict__ guard,
-                                                                const long long* __restrict__ skipped) {
-  adam_groups_body(p, g, m, v, rt, nblocks, table, step, gscale, step_dev, count_dev, ticket, advance, guard, skipped);
-}
 
 // ---------------------------------------------------------------------------
 // Global-norm gradient clipping (lirec_grad_sq_partials, lirec_clip_finalize): the clip coefficient is produced in device memory
 // and folds into the scale the Adam kernels multiply every gradient by -- no scaling pass over the gradients, no host visit.
 //
-// grad_sq_partials_kernel: the sum of squares of the flat fp32 gradient buffer over a table of ranges (the offset / length part of
-// adam_ranges_kernel's table: offsets multiples of 4).  The grid is ALWAYS CLIP_PARTIALS workgroups -- a constant, never derived
-// from the device -- and the work is dealt as in adam_ranges_kernel: blocks of ADAM_RANGE_BLOCK elements numbered across the
-// ranges, workgroup w taking blocks w, w + CLIP_PARTIALS, ...  Every thread squares and accumulates in double (the square of an
+// grad_sq_partials_kernel: the sum of squares of the flat fp32 gradient buffer over a table of ranges.  The grid is ALWAYS
+// CLIP_PARTIALS workgroups -- a constant, never derived from the device -- and the work is dealt as in adam_table_kernel: workgroup
+// w takes blocks w, w + CLIP_PARTIALS, ...  Every thread squares and accumulates in double (the square of an
 // fp32 value is exact there, so whether the compiler contracts the multiply-add changes nothing), then a fixed tree: the wave's
 // shuffles, the four waves through LDS.  Workgroup w stores ONE double to partials[w] (0 without work): the result is a pure
 // function of (values, ranges, CLIP_PARTIALS) -- the same bits on every device and in every launch form.
 #define CLIP_PARTIALS 1024
-struct SqRanges {
-  long off[ADAM_MAX_RANGES], len[ADAM_MAX_RANGES];
-  int count;
-};
 __device__ __forceinline__ double clip_block_sum(double acc, double* red) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
@@ -1925,30 +1964,21 @@ __device__ __forceinline__ double clip_block_sum(double acc, double* red) {
   __syncthreads();
   return (red[0] + red[1]) + (red[2] + red[3]);          // (meaningful in thread 0; every thread may read it)
 }
-__global__ __launch_bounds__(256) void grad_sq_partials_kernel(const float* __restrict__ g, const SqRanges rt, long nblocks,
+__global__ __launch_bounds__(256) void grad_sq_partials_kernel(const float* __restrict__ g, const RangeTable rt, long nblocks,
                                                                double* __restrict__ partials) {
   __shared__ double red[4];
   double acc = 0.0;
   for (long wb = blockIdx.x; wb < nblocks; wb += CLIP_PARTIALS) {
     long b = wb;
-    int r = 0;
-    for (; r < rt.count - 1; ++r) {
-      const long nb = (rt.len[r] + ADAM_RANGE_BLOCK - 1) / ADAM_RANGE_BLOCK;
-      if (b < nb) break;
-      b -= nb;
-    }
-    const long first = b * ADAM_RANGE_BLOCK;                  // within the range
-    long left = rt.len[r] - first;
-    if (left > ADAM_RANGE_BLOCK) left = ADAM_RANGE_BLOCK;
-    const long e = 4L * threadIdx.x;
-    const long at = rt.off[r] + first + e;
-    if (e + 4 <= left) {
-      const f32x4 x = *reinterpret_cast<const f32x4*>(g + at);
+    const int r = range_of_block(rt, b);
+    range_block_apply(
+        rt, r, b,
+        [&](long at) {
+          const f32x4 x = *reinterpret_cast<const f32x4*>(g + at);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) acc += (double)x[j] * (double)x[j];
-    } else {
-      for (long j = 0; e + j < left; ++j) acc += (double)g[at + j] * (double)g[at + j];
-    }
+          for (int j = 0; j < 4; ++j) acc += (double)x[j] * (double)x[j];
+        },
+        [&](long at) { acc += (double)g[at] * (double)g[at]; });
   }
   const double s = clip_block_sum(acc, red);
   if (threadIdx.x == 0) partials[blockIdx.x] = s;
@@ -1959,8 +1989,14 @@ __global__ __launch_bounds__(256) void grad_sq_partials_kernel(const float* __re
 // all-reduce).  norm = sqrt(*sq) * grad_scale; x = max_norm / (norm + 1e-6) -- torch.nn.utils.clip_grad_norm_'s formula --
 // out[0] = x < 1 ? x : (x is NaN ? x : 1), out[1] = norm, both fp32.  A NaN norm gives a NaN coefficient (and NaN parameters: what
 // clip_grad_norm_ without error_if_nonfinite does), an infinite one the coefficient 0.
+// GUARD (lirec_clip_finalize_guard): max_norm == 0 means no clipping, the coefficient is 1; out[2] = skip: 1.0f when the DOUBLE
+// sum itself is not finite, 0 otherwise.  The sum is non-finite exactly when an element it covers is: squares cannot cancel, and
+// the squares of finite fp32 values cannot overflow a double (each < 2^256).  `count`: *skipped += skip, the device count of
+// skipped steps that the guarded Adam kernels subtract from their step -- on ONE finalize of a step, the last.
+template <bool GUARD>
 __global__ __launch_bounds__(256) void clip_finalize_kernel(const double* __restrict__ partials, double* __restrict__ sq, int mode,
-                                                            float grad_scale, float max_norm, float* __restrict__ out) {
+                                                            float grad_scale, float max_norm, float* __restrict__ out,
+                                                            long long* __restrict__ skipped, int count) {
   __shared__ double red[4];
   static_assert(CLIP_PARTIALS % 256 == 0, "every thread sums the same number of partials");
   double acc = 0.0;
@@ -1975,40 +2011,14 @@ __global__ __launch_bounds__(256) void clip_finalize_kernel(const double* __rest
     if (mode != 2) *sq = total;
     const double norm = sqrt(total) * (double)grad_scale;
     const double x = (double)max_norm / (norm + 1e-6);
-    const double coef = x < 1.0 ? x : (x != x ? x : 1.0);
+    const double coef = (GUARD && max_norm == 0.f) ? 1.0 : (x < 1.0 ? x : (x != x ? x : 1.0));
     out[0] = (float)coef;
     out[1] = (float)norm;
-  }
-}
-
-// clip_finalize_guard_kernel (lirec_clip_finalize_guard): clip_finalize_kernel -- the same tree, modes and arithmetic for out[0]
-// and out[1]; max_norm == 0: no clipping, the coefficient is 1 -- that also writes out[2] = skip: 1.0f when the DOUBLE sum itself
-// is not finite, 0 otherwise.  The sum is non-finite exactly when an element it covers is: squares cannot cancel, and the squares
-// of finite fp32 values cannot overflow a double (each < 2^256).  `count`: *skipped += skip, the device count of skipped steps
-// that the guarded Adam kernels subtract from their step -- on ONE finalize of a step, the last.
-__global__ __launch_bounds__(256) void clip_finalize_guard_kernel(const double* __restrict__ partials, double* __restrict__ sq,
-                                                                  int mode, float grad_scale, float max_norm,
-                                                                  float* __restrict__ out, long long* __restrict__ skipped,
-                                                                  int count) {
-  __shared__ double red[4];
-  double acc = 0.0;
-  if (mode != 2) {
-    const double* q = partials + (long)threadIdx.x * (CLIP_PARTIALS / 256);
-#pragma unroll
-    for (int j = 0; j < CLIP_PARTIALS / 256; ++j) acc += q[j];
-  }
-  const double s = clip_block_sum(acc, red);
-  if (threadIdx.x == 0) {
-    double total = mode == 0 ? s : (mode == 1 ? *sq + s : *sq);
-    if (mode != 2) *sq = total;
-    const double norm = sqrt(total) * (double)grad_scale;
-    const double x = (double)max_norm / (norm + 1e-6);
-    const double coef = max_norm == 0.f ? 1.0 : (x < 1.0 ? x : (x != x ? x : 1.0));
-    const bool skip = !(fabs(total) <= 1.7976931348623157e308);      // NaN or +-Inf
-    out[0] = (float)coef;
-    out[1] = (float)norm;
-    out[2] = skip ? 1.f : 0.f;
-    if (count && skip) *skipped += 1;
+    if constexpr (GUARD) {
+      const bool skip = !(fabs(total) <= 1.7976931348623157e308);      // NaN or +-Inf
+      out[2] = skip ? 1.f : 0.f;
+      if (count && skip) *skipped += 1;
+    }
   }
 }
 
@@ -2027,7 +2037,7 @@ __global__ __launch_bounds__(256) void cast_f64_f32_kernel(const double* __restr
 // difference is rounded on its own (__fsub_rn: never contracted into the fma), so e == p gives fmaf(w, +0, e) = e, bit for bit (e = -0 alone becomes +0, as in torch).
 // 12 bytes per element and two flops: HBM-bound.  `head` (0..3) scalar elements bring both pointers to 16-byte alignment -- the
 // host checked that they sit at the same offset modulo 16 --, then f32x4, then a scalar tail.  `guard`: the (coefficient, norm,
-// skip) block of clip_finalize_guard_kernel; one uniform load, a set flag ends the launch before any element is touched.
+// skip) block of clip_finalize_kernel<true>; one uniform load, a set flag ends the launch before any element is touched.
 // ---------------------------------------------------------------------------
 #define EMA_MAX_BLOCKS 2048
 __device__ __forceinline__ float ema1(float e, float p, float w) { return fmaf(w, __fsub_rn(p, e), e); }

@@ -139,21 +139,20 @@ static inline unsigned row_magic(int gs, long max_rows) {
 static thread_local int g_grad_overwrite = 0;       // (per host thread, like the recorder and the contexts: a backward on another
                                                     //  thread -- an evaluation loop's, another model's -- never picks it up)
 static inline float grad_beta() { return g_grad_overwrite ? 0.f : 1.f; }
-// The clip coefficient of this host thread's Adam launches (lirec_set_adam_clip): a device float the launches read, NULL = off.
-// Per host thread, like g_grad_overwrite and the recorder -- NOT per context: the side streams' launches of a step are issued by
-// the thread that set it, under contexts of their own.
-static thread_local const float* t_adam_clip = nullptr;
-// The guard of this host thread's Adam launches (lirec_set_adam_guard): the (coefficient, norm, skip) block and the count of skipped
-// steps, both in device memory; NULL, NULL = off.  Set, it takes precedence over t_adam_clip.
-static thread_local const float* t_adam_guard = nullptr;
-static thread_local const int64_t* t_adam_guard_skipped = nullptr;
-// The device row a folded first-layer update issued by this host thread reads its five hyper-parameters from
-// (lirec_set_adam_hyper_row), NULL = off: the values of lirec_fused_adam, by value, and today's kernel.  Per host thread, as above.
-static thread_local const lirec_adam_hyper* t_adam_hyper_row = nullptr;
-// ... or one row PER FIRST-LAYER PARAMETER (lirec_set_adam_hyper_map): the table and the ranges of the flat layout with their
-// groups; count 0 = off.  Takes precedence over the single row.  Per host thread.
-static thread_local const lirec_adam_hyper* t_adam_map_table = nullptr;
-static thread_local AdamHyperMap t_adam_map = {};
+// What the lirec_set_adam_* calls have left for the updates this host thread issues.  Per host thread, like g_grad_overwrite and
+// the recorder -- NOT per context: the side streams' launches of a step are issued by the thread that set it, under contexts of
+// their own.  Precedence: for the Adam launches, guard over clip; for a folded first-layer update, map over row (and neither clip
+// nor guard may be set: fused_adam_fill).
+struct AdamThreadState {
+  const float* clip;                     // lirec_set_adam_clip: the device float the launches scale their gradients by; NULL = off
+  const float* guard;                    // lirec_set_adam_guard: the (coefficient, norm, skip) block and the count of skipped
+  const int64_t* guard_skipped;          //   steps, both in device memory; NULL, NULL = off
+  const lirec_adam_hyper* hyper_row;     // lirec_set_adam_hyper_row: the device row a folded update reads its five hyper-parameters
+                                         //   from; NULL = off: the values of lirec_fused_adam, by value
+  const lirec_adam_hyper* map_table;     // lirec_set_adam_hyper_map: one row PER FIRST-LAYER PARAMETER -- the table, and the ranges
+  AdamHyperMap map;                      //   of the flat layout with their groups; count 0 = off
+};
+static thread_local AdamThreadState t_adam = {};
 // While the mode is on, every weight / bias gradient target that is handed to a launch is noted: a parameter written by TWO
 // launches of one step (a tied module, a gradient cut over several launches) would silently lose the first contribution -- the
 // caller that switches the mode on asks for the count of such targets afterwards (lirec_grad_overwrite_conflicts) and keeps
@@ -673,13 +672,118 @@ static int gather_planes(const Args* const* hs, int nh) {
   return xp;
 }
 
+// The Adam kernels read and write p, g, m, v as f32x4 from the pointers they are given
+static bool adam_buffers_ok(const float* p, const float* g, const float* m, const float* v) {
+  return p && g && m && v && ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                               reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+}
+// the bias-correction factors of a by-value step, in double (the kernels' adam_bias does the same for a step on the device)
+static void adam_bias_host(float lr, float beta1, float beta2, int64_t t, float& step_size, float& bc2_sqrt) {
+  step_size = (float)((double)lr / (1.0 - pow((double)beta1, (double)t)));
+  bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)t));
+}
+
+// One Adam launch, described; the four entry points validate and fill it, adam_launch issues it.
+struct AdamLaunch {
+  float* p; const float* g; float* m; float* v;
+  int64_t n;                          // elements the launch updates: the flat form's length, a table's total
+  const AdamRanges* ranges;           // the work: a table with the hyper-parameters by value, or
+  const AdamGroupRanges* groups;      //   a table with a group per range and the groups' rows in device memory (`table`), or
+  const AdamHyperRow* table;          //   (both NULL) the flat stretch [0, n)
+  long nblocks;                       // a table's blocks of ADAM_RANGE_BLOCK elements, > 0
+  AdamHyperArgs hy;                   // by value (not with `groups`)
+  float step_size, bc2_sqrt;          // the flat form's factors for a by-value step (a table carries its own, per range)
+  float gscale;
+  AdamStep st;                        // the step's source; adam_launch adds the scale mode's operands
+};
+template <int SCALE>
+static void adam_launch_as(const AdamLaunch& d, dim3 grid, hipStream_t s) {
+  if (!d.groups && !d.ranges) {
+    lirec::launch(HIP_KERNEL_NAME(adam_kernel<SCALE>), grid, dim3(256), 0, s, d.p, d.g, d.m, d.v, (long)d.n, d.hy, d.step_size,
+                  d.bc2_sqrt, d.gscale, d.st);
+  } else if constexpr (SCALE == ADAM_CLIP) {          // (the table forms with kernels of their own: see there)
+    if (d.groups)
+      lirec::launch(adam_groups_clip_kernel, grid, dim3(256), 0, s, d.p, d.g, d.m, d.v, *d.groups, d.nblocks, d.table, d.st.step,
+                    d.gscale, d.st.step_dev, d.st.count_dev, d.st.ticket, d.st.advance, d.st.scale);
+    else
+      lirec::launch(adam_ranges_clip_kernel, grid, dim3(256), 0, s, d.p, d.g, d.m, d.v, *d.ranges, d.nblocks, d.hy.beta1, d.hy.beta2,
+                    d.hy.eps, d.hy.wd, d.gscale, d.hy.lr, d.st.step_dev, d.st.count_dev, d.st.ticket, d.st.advance, d.st.scale);
+  } else if (d.groups) {
+    lirec::launch(HIP_KERNEL_NAME(adam_table_kernel<SCALE, AdamHyperTable>), grid, dim3(256), 0, s, d.p, d.g, d.m, d.v, *d.groups,
+                  d.nblocks, AdamHyperTable{d.table}, d.gscale, d.st);
+  } else {
+    lirec::launch(HIP_KERNEL_NAME(adam_table_kernel<SCALE, AdamHyperByValue>), grid, dim3(256), 0, s, d.p, d.g, d.m, d.v, *d.ranges,
+                  d.nblocks, AdamHyperByValue{d.hy}, d.gscale, d.st);
+  }
+}
+static int adam_launch(AdamLaunch d, lirec_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  long blocks = (d.ranges || d.groups) ? d.nblocks : (long)((d.n / 4 + 255) / 256);
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  const dim3 grid((unsigned)blocks);
+  const int pi = prof_start(PS_ADAM, s);
+  if (t_adam.guard) {                   // (guard over clip: AdamThreadState)
+    d.st.scale = t_adam.guard; d.st.skipped = (const long long*)t_adam.guard_skipped;
+    adam_launch_as<ADAM_GUARD>(d, grid, s);
+  } else if (t_adam.clip) {
+    d.st.scale = t_adam.clip;
+    adam_launch_as<ADAM_CLIP>(d, grid, s);
+  } else {
+    adam_launch_as<ADAM_PLAIN>(d, grid, s);
+  }
+  prof_stop(pi, s, 0.0, 28.0 * (double)d.n);     // read p,g,m,v; write p,m,v
+  LIREC_CHECK_LAUNCH();
+  return LIREC_OK;
+}
+static AdamStep adam_step_source(int32_t step, const int64_t* step_dev, int64_t* count_dev, int32_t* ticket, int32_t advance) {
+  return AdamStep{(int)step, (const long long*)step_dev, (long long*)count_dev, (int*)ticket, (int)(advance != 0), nullptr, nullptr};
+}
+
+// One walk for every by-value table of ranges -- Adam's two and the norm's -- that checks the ranges, fills `rt` and counts the
+// blocks and the elements.  Every table: at most LIREC_ADAM_MAX_RANGES ranges, offset >= 0 and a multiple of 4, length >= 0.
+// Adam's besides: ascending and disjoint, lag >= 0, a by-value step (`step_by_value` not NULL) stays >= 1 less the lag, and with
+// groups 0 <= group < n_groups.
+template <class Table, class Range>
+static bool range_table_fill(Table& rt, const Range* ranges, int32_t count, const int32_t* step_by_value, int32_t n_groups,
+                             long& nblocks, int64_t& total) {
+  static_assert(LIREC_ADAM_MAX_RANGES == ADAM_MAX_RANGES, "the header's table size is the kernel's");
+  constexpr bool adam = !std::is_same<Table, RangeTable>::value, grouped = std::is_same<Table, AdamGroupRanges>::value;
+  if (count < 0 || count > LIREC_ADAM_MAX_RANGES || (count > 0 && !ranges)) return false;
+  memset(&rt, 0, sizeof(rt));
+  nblocks = 0; total = 0;
+  int64_t end = 0;                                             // ascending, disjoint
+  for (int r = 0; r < count; ++r) {
+    const Range& q = ranges[r];
+    if (q.length < 0 || q.offset < 0 || (q.offset & 3) != 0) return false;
+    if constexpr (adam) {
+      if (q.lag < 0 || q.offset < end) return false;
+      if (step_by_value && (int64_t)*step_by_value - q.lag < 1) return false;
+      rt.lag[r] = q.lag;
+    }
+    if constexpr (grouped) {
+      if (q.group < 0 || q.group >= n_groups) return false;
+      rt.group[r] = (unsigned char)q.group;
+    }
+    end = q.offset + q.length; total += q.length;
+    rt.off[r] = (long)q.offset; rt.len[r] = (long)q.length;
+    nblocks += (long)((q.length + ADAM_RANGE_BLOCK - 1) / ADAM_RANGE_BLOCK);
+  }
+  rt.count = count;
+  return true;
+}
+// the step arguments of the table launches: one source at the most, a counter with its ticket
+static bool adam_step_source_ok(const int64_t* step_dev, const int64_t* count_dev, const int32_t* ticket) {
+  return !(step_dev && count_dev) && !(count_dev && !ticket);
+}
+
 // lirec_fused_adam -> the kernels' AdamFuse, checked against the weight-gradient problems of the launch: every gradient of the
 // call inside the flat buffer, and together exactly the parameters the caller counts on; sets each problem's aux_out to where
 // the q32b form of its new weights goes (or NULL)
 static int fused_adam_fill(const lirec_fused_adam* adam, GemmGroup& g, AdamFuse& af) {
   // (a clip coefficient needs the norm of the FINISHED gradient, which this very launch produces: the folded update cannot be
   //  clipped, and an unclipped one beside clipped launches would be a silent error)
-  if (t_adam_clip || t_adam_guard) return LIREC_EINVAL;      // (a guard: the decision needs the finished gradient just the same)
+  if (t_adam.clip || t_adam.guard) return LIREC_EINVAL;      // (a guard: the decision needs the finished gradient just the same)
   if (!adam->p || !adam->g || !adam->m || !adam->v || adam->n < 1 || (adam->step < 1 && !adam->step_dev)) return LIREC_EINVAL;
   if (((reinterpret_cast<uintptr_t>(adam->p) | reinterpret_cast<uintptr_t>(adam->g) | reinterpret_cast<uintptr_t>(adam->m) |
         reinterpret_cast<uintptr_t>(adam->v)) & 15) != 0 || (reinterpret_cast<uintptr_t>(adam->wq) & 255) != 0) return LIREC_EINVAL;
@@ -699,8 +803,7 @@ static int fused_adam_fill(const lirec_fused_adam* adam, GemmGroup& g, AdamFuse&
   if (covered != adam->n_params) return LIREC_EINVAL;
   const int step = adam->step < 1 ? 1 : adam->step;
   af.p = adam->p; af.g = adam->g; af.m = adam->m; af.v = adam->v;
-  af.step_size = (float)((double)adam->lr / (1.0 - pow((double)adam->beta1, (double)step)));
-  af.bc2_sqrt = (float)sqrt(1.0 - pow((double)adam->beta2, (double)step));
+  adam_bias_host(adam->lr, adam->beta1, adam->beta2, step, af.step_size, af.bc2_sqrt);
   af.beta1 = adam->beta1; af.beta2 = adam->beta2; af.eps = adam->eps; af.wd = adam->weight_decay; af.gscale = adam->grad_scale;
   af.lr = adam->lr; af.step_dev = (const long long*)adam->step_dev;
   af.wq16c = g_gemm_mode == 3 ? 1 : 0;      // (the single-pass mode keeps its first-layer weights as q16c)
@@ -735,13 +838,13 @@ static int launch_p2(GemmGroup& g0, hipStream_t s, int site, const int* nt_bound
     if (g.nprob != g0.nprob) return LIREC_EINVAL;                // (a problem was dropped as empty: its parameters would miss the update)
     const int rc = fused_adam_fill(adam, g, af);
     if (rc) return rc;
-    if (t_adam_map.count > 0) {
+    if (t_adam.map.count > 0) {
       // (one row per parameter: every weight and every bias of the call lies inside an entry of the map -- the kernel takes
       //  the row of the entry it finds them in)
       auto inside = [&](const float* q, long n) {
         const long o = (long)(q - adam->g);
-        for (int i = 0; i < t_adam_map.count; ++i)
-          if (o >= t_adam_map.off[i] && o + n <= t_adam_map.end[i]) return true;
+        for (int i = 0; i < t_adam.map.count; ++i)
+          if (o >= t_adam.map.off[i] && o + n <= t_adam.map.end[i]) return true;
         return false;
       };
       for (int i = 0; i < g.nprob; ++i)
@@ -785,11 +888,11 @@ static int launch_p2(GemmGroup& g0, hipStream_t s, int site, const int* nt_bound
     // bytes: at most two partial tiles per workgroup read, every output tile written once
     const int pr = prof_start(PS_EMBED_DW1_RED, s);
     // (device-resident hyper-parameters: the row kernel, which computes the bias corrections itself from the step it is given)
-    if (adam && t_adam_map.count > 0)
-      launch_p2_tn_reduce(tiles, G, s, g, nrep, &af, reinterpret_cast<const AdamHyperRow*>(t_adam_map_table), adam->step < 1 ? 1 : adam->step,
-                          &t_adam_map);
-    else if (adam && t_adam_hyper_row)
-      launch_p2_tn_reduce(tiles, G, s, g, nrep, &af, reinterpret_cast<const AdamHyperRow*>(t_adam_hyper_row), adam->step < 1 ? 1 : adam->step);
+    if (adam && t_adam.map.count > 0)
+      launch_p2_tn_reduce(tiles, G, s, g, nrep, &af, reinterpret_cast<const AdamHyperRow*>(t_adam.map_table), adam->step < 1 ? 1 : adam->step,
+                          &t_adam.map);
+    else if (adam && t_adam.hyper_row)
+      launch_p2_tn_reduce(tiles, G, s, g, nrep, &af, reinterpret_cast<const AdamHyperRow*>(t_adam.hyper_row), adam->step < 1 ? 1 : adam->step);
     else
       launch_p2_tn_reduce(tiles, G, s, g, nrep, adam ? &af : nullptr);
     // (+ the update: p, m, v read and written, the q32b shadow written)
@@ -2387,120 +2490,52 @@ int lirec_ce_loss(const float* ints, int64_t ld_ints, const float* rels, int64_t
 }
 
 // ---------------------------------------------------------------------------
-// adam_kernel reads and writes p, g, m, v as f32x4 from the pointers it is given
-static bool adam_aligned(const float* p, const float* g, const float* m, const float* v) {
-  return ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-           reinterpret_cast<uintptr_t>(v)) & 15) == 0;
-}
-
 int lirec_adam_step(float* p, const float* g, float* m, float* v, int64_t n, int32_t step,
                     float lr, float beta1, float beta2, float eps, float weight_decay,
                     float grad_scale, const int64_t* step_dev, lirec_stream_t stream) {
-  if (!p || !g || !m || !v || n < 0 || (step < 1 && !step_dev)) return LIREC_EINVAL;
-  if (!adam_aligned(p, g, m, v)) return LIREC_EINVAL;
+  if (!adam_buffers_ok(p, g, m, v) || n < 0 || (step < 1 && !step_dev)) return LIREC_EINVAL;
   if (step < 1) step = 1;
   if (n == 0) return LIREC_OK;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float step_size = (float)((double)lr / bc1);
-  const float bc2_sqrt = (float)sqrt(bc2);
-  long blocks = (n / 4 + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  const int pi = prof_start(PS_ADAM, (hipStream_t)stream);
-  if (t_adam_guard)
-    lirec::launch(adam_guard_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n,
-                  beta1, beta2, eps, weight_decay, grad_scale, lr, (int)step, (const long long*)step_dev,
-                  (long long*)nullptr, (int*)nullptr, 0, t_adam_guard, (const long long*)t_adam_guard_skipped);
-  else if (t_adam_clip)
-    lirec::launch(adam_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n,
-                  step_size, bc2_sqrt, beta1, beta2, eps, weight_decay, grad_scale, lr, (const long long*)step_dev,
-                  (long long*)nullptr, (int*)nullptr, 0, t_adam_clip);
-  else
-    lirec::launch(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n,
-                     step_size, bc2_sqrt, beta1, beta2, eps, weight_decay, grad_scale, lr, (const long long*)step_dev,
-                     (long long*)nullptr, (int*)nullptr, 0);
-  prof_stop(pi, (hipStream_t)stream, 0.0, 28.0 * (double)n);     // read p,g,m,v; write p,m,v
-  LIREC_CHECK_LAUNCH();
-  return LIREC_OK;
+  AdamLaunch d = {p, g, m, v, n};
+  d.hy = AdamHyperArgs{lr, beta1, beta2, eps, weight_decay};
+  adam_bias_host(lr, beta1, beta2, step, d.step_size, d.bc2_sqrt);
+  d.gscale = grad_scale;
+  d.st = adam_step_source(step, step_dev, nullptr, nullptr, 0);
+  return adam_launch(d, stream);
 }
 
 int lirec_adam_step_counted(float* p, const float* g, float* m, float* v, int64_t n,
                             float lr, float beta1, float beta2, float eps, float weight_decay,
                             float grad_scale, int64_t* count_dev, int32_t* ticket, int32_t advance, lirec_stream_t stream) {
-  if (!p || !g || !m || !v || n < 1 || !count_dev || !ticket) return LIREC_EINVAL;
-  if (!adam_aligned(p, g, m, v)) return LIREC_EINVAL;
-  long blocks = (n / 4 + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  const int pi = prof_start(PS_ADAM, (hipStream_t)stream);
-  if (t_adam_guard)
-    lirec::launch(adam_guard_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n,
-                  beta1, beta2, eps, weight_decay, grad_scale, lr, 0, (const long long*)nullptr,
-                  (long long*)count_dev, (int*)ticket, (int)(advance != 0), t_adam_guard, (const long long*)t_adam_guard_skipped);
-  else if (t_adam_clip)
-    lirec::launch(adam_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n,
-                  0.f, 0.f, beta1, beta2, eps, weight_decay, grad_scale, lr, (const long long*)nullptr,
-                  (long long*)count_dev, (int*)ticket, (int)(advance != 0), t_adam_clip);
-  else
-    lirec::launch(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n,
-                     0.f, 0.f, beta1, beta2, eps, weight_decay, grad_scale, lr, (const long long*)nullptr,
-                     (long long*)count_dev, (int*)ticket, (int)(advance != 0));
-  prof_stop(pi, (hipStream_t)stream, 0.0, 28.0 * (double)n);
-  LIREC_CHECK_LAUNCH();
-  return LIREC_OK;
+  if (!adam_buffers_ok(p, g, m, v) || n < 1 || !count_dev || !ticket) return LIREC_EINVAL;
+  AdamLaunch d = {p, g, m, v, n};
+  d.hy = AdamHyperArgs{lr, beta1, beta2, eps, weight_decay};
+  d.gscale = grad_scale;
+  d.st = adam_step_source(0, nullptr, count_dev, ticket, advance);
+  return adam_launch(d, stream);
 }
 
 int lirec_adam_step_ranges(float* p, const float* g, float* m, float* v, const lirec_adam_range* ranges, int32_t count,
                            int32_t step, float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                            const int64_t* step_dev, int64_t* count_dev, int32_t* ticket, int32_t advance, lirec_stream_t stream) {
-  if (!p || !g || !m || !v || count < 0 || count > LIREC_ADAM_MAX_RANGES || (count > 0 && !ranges)) return LIREC_EINVAL;
-  if (!adam_aligned(p, g, m, v)) return LIREC_EINVAL;
-  if (step_dev && count_dev) return LIREC_EINVAL;
-  if (count_dev && !ticket) return LIREC_EINVAL;
+  if (!adam_buffers_ok(p, g, m, v) || !adam_step_source_ok(step_dev, count_dev, ticket)) return LIREC_EINVAL;
   const bool by_value = !step_dev && !count_dev;
-  static_assert(LIREC_ADAM_MAX_RANGES == ADAM_MAX_RANGES, "the header's table size is the kernel's");
   AdamRanges rt;
-  memset(&rt, 0, sizeof(rt));
-  long nblocks = 0;
-  int64_t end = 0, total = 0;                                  // ascending, disjoint
-  for (int r = 0; r < count; ++r) {
-    const lirec_adam_range& q = ranges[r];
-    if (q.length < 0 || q.offset < 0 || (q.offset & 3) != 0 || q.lag < 0 || q.offset < end) return LIREC_EINVAL;
-    if (by_value && (int64_t)step - q.lag < 1) return LIREC_EINVAL;
-    end = q.offset + q.length; total += q.length;
-    rt.off[r] = (long)q.offset; rt.len[r] = (long)q.length; rt.lag[r] = q.lag;
-    if (by_value) {
-      const double t = (double)(step - q.lag);
-      rt.step_size[r] = (float)((double)lr / (1.0 - pow((double)beta1, t)));
-      rt.bc2_sqrt[r] = (float)sqrt(1.0 - pow((double)beta2, t));
-    }
-    nblocks += (long)((q.length + ADAM_RANGE_BLOCK - 1) / ADAM_RANGE_BLOCK);
-  }
-  rt.count = count;
-  if (nblocks == 0) return LIREC_OK;
-  const long blocks = nblocks > 2048 ? 2048 : nblocks;
-  const int pi = prof_start(PS_ADAM, (hipStream_t)stream);
-  if (t_adam_guard)
-    lirec::launch(adam_ranges_guard_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, rt, nblocks,
-                  beta1, beta2, eps, weight_decay, grad_scale, lr, (int)step, (const long long*)step_dev, (long long*)count_dev,
-                  (int*)ticket, (int)(advance != 0), t_adam_guard, (const long long*)t_adam_guard_skipped);
-  else if (t_adam_clip)
-    lirec::launch(adam_ranges_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, rt, nblocks,
-                  beta1, beta2, eps, weight_decay, grad_scale, lr, (const long long*)step_dev, (long long*)count_dev,
-                  (int*)ticket, (int)(advance != 0), t_adam_clip);
-  else
-    lirec::launch(adam_ranges_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, rt, nblocks,
-                beta1, beta2, eps, weight_decay, grad_scale, lr, (const long long*)step_dev, (long long*)count_dev,
-                (int*)ticket, (int)(advance != 0));
-  prof_stop(pi, (hipStream_t)stream, 0.0, 28.0 * (double)total);
-  LIREC_CHECK_LAUNCH();
-  return LIREC_OK;
+  AdamLaunch d = {p, g, m, v};
+  if (!range_table_fill(rt, ranges, count, by_value ? &step : nullptr, 0, d.nblocks, d.n)) return LIREC_EINVAL;
+  if (d.nblocks == 0) return LIREC_OK;
+  if (by_value)                     // (as lirec_adam_step does, per range)
+    for (int r = 0; r < count; ++r) adam_bias_host(lr, beta1, beta2, (int64_t)step - rt.lag[r], rt.step_size[r], rt.bc2_sqrt[r]);
+  d.ranges = &rt;
+  d.hy = AdamHyperArgs{lr, beta1, beta2, eps, weight_decay};
+  d.gscale = grad_scale;
+  d.st = adam_step_source(step, step_dev, count_dev, ticket, advance);
+  return adam_launch(d, stream);
 }
 
 int lirec_set_adam_clip(const float* coef_dev) {
   if (reinterpret_cast<uintptr_t>(coef_dev) & 3) return LIREC_EINVAL;
-  t_adam_clip = coef_dev;
+  t_adam.clip = coef_dev;
   return LIREC_OK;
 }
 
@@ -2530,52 +2565,27 @@ int lirec_adam_hyper_write(lirec_adam_hyper* table_dev, const lirec_adam_hyper* 
 int lirec_adam_step_groups(float* p, const float* g, float* m, float* v, const lirec_adam_group_range* ranges, int32_t count,
                            const lirec_adam_hyper* table_dev, int32_t n_groups, int32_t step, float grad_scale,
                            const int64_t* step_dev, int64_t* count_dev, int32_t* ticket, int32_t advance, lirec_stream_t stream) {
-  if (!p || !g || !m || !v || count < 0 || count > LIREC_ADAM_MAX_RANGES || (count > 0 && !ranges)) return LIREC_EINVAL;
-  if (!adam_aligned(p, g, m, v)) return LIREC_EINVAL;
-  if (!hyper_table_ok(table_dev, n_groups)) return LIREC_EINVAL;
-  if (step_dev && count_dev) return LIREC_EINVAL;
-  if (count_dev && !ticket) return LIREC_EINVAL;
+  if (!adam_buffers_ok(p, g, m, v) || !hyper_table_ok(table_dev, n_groups) || !adam_step_source_ok(step_dev, count_dev, ticket))
+    return LIREC_EINVAL;
   const bool by_value = !step_dev && !count_dev;
   AdamGroupRanges rt;
-  memset(&rt, 0, sizeof(rt));
-  long nblocks = 0;
-  int64_t end = 0, total = 0;                                  // ascending, disjoint
-  for (int r = 0; r < count; ++r) {
-    const lirec_adam_group_range& q = ranges[r];
-    if (q.length < 0 || q.offset < 0 || (q.offset & 3) != 0 || q.lag < 0 || q.offset < end) return LIREC_EINVAL;
-    if (q.group < 0 || q.group >= n_groups) return LIREC_EINVAL;
-    if (by_value && (int64_t)step - q.lag < 1) return LIREC_EINVAL;
-    end = q.offset + q.length; total += q.length;
-    rt.off[r] = (long)q.offset; rt.len[r] = (long)q.length; rt.lag[r] = q.lag; rt.group[r] = (unsigned char)q.group;
-    nblocks += (long)((q.length + ADAM_RANGE_BLOCK - 1) / ADAM_RANGE_BLOCK);
-  }
-  rt.count = count;
-  if (nblocks == 0) return LIREC_OK;
-  const long blocks = nblocks > 2048 ? 2048 : nblocks;
-  const AdamHyperRow* table = reinterpret_cast<const AdamHyperRow*>(table_dev);
-  const int pi = prof_start(PS_ADAM, (hipStream_t)stream);
-  if (t_adam_guard)
-    lirec::launch(adam_groups_guard_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, rt, nblocks, table,
-                  (int)step, grad_scale, (const long long*)step_dev, (long long*)count_dev, (int*)ticket, (int)(advance != 0),
-                  t_adam_guard, (const long long*)t_adam_guard_skipped);
-  else if (t_adam_clip)
-    lirec::launch(adam_groups_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, rt, nblocks, table,
-                  (int)step, grad_scale, (const long long*)step_dev, (long long*)count_dev, (int*)ticket, (int)(advance != 0),
-                  t_adam_clip);
-  else
-    lirec::launch(adam_groups_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, rt, nblocks, table,
-                  (int)step, grad_scale, (const long long*)step_dev, (long long*)count_dev, (int*)ticket, (int)(advance != 0));
-  prof_stop(pi, (hipStream_t)stream, 0.0, 28.0 * (double)total);
-  LIREC_CHECK_LAUNCH();
-  return LIREC_OK;
+  AdamLaunch d = {p, g, m, v};
+  if (!range_table_fill(rt, ranges, count, by_value ? &step : nullptr, n_groups, d.nblocks, d.n)) return LIREC_EINVAL;
+  if (d.nblocks == 0) return LIREC_OK;
+  d.groups = &rt;
+  d.table = reinterpret_cast<const AdamHyperRow*>(table_dev);
+  d.gscale = grad_scale;
+  d.st = adam_step_source(step, step_dev, count_dev, ticket, advance);
+  return adam_launch(d, stream);
 }
 
 int lirec_set_adam_hyper_row(const lirec_adam_hyper* row_dev) {
   if (reinterpret_cast<uintptr_t>(row_dev) & 15) return LIREC_EINVAL;
-  t_adam_hyper_row = row_dev;
+  t_adam.hyper_row = row_dev;
   return LIREC_OK;
 }
 
+// (a table of its own rules -- length >= 1, lag 0, no multiple-of-4 offsets, ends that must not wrap -- and of its own size)
 int lirec_set_adam_hyper_map(const lirec_adam_hyper* table_dev, const lirec_adam_group_range* ranges, int32_t count) {
   static_assert(LIREC_ADAM_MAP_MAX == ADAM_MAP_MAX, "the header's number of map entries is the kernels'");
   if (reinterpret_cast<uintptr_t>(table_dev) & 15) return LIREC_EINVAL;
@@ -2592,26 +2602,20 @@ int lirec_set_adam_hyper_map(const lirec_adam_hyper* table_dev, const lirec_adam
     mp.off[r] = (long)q.offset; mp.end[r] = (long)end; mp.group[r] = (unsigned char)q.group;
   }
   mp.count = table_dev ? count : 0;
-  t_adam_map = mp;
-  t_adam_map_table = mp.count ? table_dev : nullptr;
+  t_adam.map = mp;
+  t_adam.map_table = mp.count ? table_dev : nullptr;
   return LIREC_OK;
 }
 
 int lirec_grad_sq_partials(const float* g, const lirec_adam_range* ranges, int32_t n_ranges, double* partials,
                            lirec_stream_t stream) {
-  if (!g || !ranges || !partials || n_ranges < 1 || n_ranges > LIREC_ADAM_MAX_RANGES) return LIREC_EINVAL;
+  if (!g || !ranges || !partials || n_ranges < 1) return LIREC_EINVAL;
   if ((reinterpret_cast<uintptr_t>(g) & 15) != 0 || (reinterpret_cast<uintptr_t>(partials) & 7) != 0) return LIREC_EINVAL;
   static_assert(LIREC_CLIP_PARTIALS == CLIP_PARTIALS, "the header's number of partials is the kernel's");
-  SqRanges rt;
-  memset(&rt, 0, sizeof(rt));
-  long nblocks = 0;
-  for (int r = 0; r < n_ranges; ++r) {
-    const lirec_adam_range& q = ranges[r];
-    if (q.length < 0 || q.offset < 0 || (q.offset & 3) != 0) return LIREC_EINVAL;
-    rt.off[r] = (long)q.offset; rt.len[r] = (long)q.length;
-    nblocks += (long)((q.length + ADAM_RANGE_BLOCK - 1) / ADAM_RANGE_BLOCK);
-  }
-  rt.count = n_ranges;
+  RangeTable rt;
+  long nblocks;
+  int64_t total;
+  if (!range_table_fill(rt, ranges, n_ranges, nullptr, 0, nblocks, total)) return LIREC_EINVAL;
   // (always launched, also with nothing to sum: every one of the partials is written)
   // (no profiling bracket: the norm pass is not part of the "adam" site, whose bytes are the update's)
   lirec::launch(grad_sq_partials_kernel, dim3(CLIP_PARTIALS), dim3(256), 0, (hipStream_t)stream, g, rt, nblocks, partials);
@@ -2619,36 +2623,36 @@ int lirec_grad_sq_partials(const float* g, const lirec_adam_range* ranges, int32
   return LIREC_OK;
 }
 
-int lirec_clip_finalize(const double* partials, double* sq_dev, int32_t mode, float grad_scale, float max_norm, float* out,
-                        lirec_stream_t stream) {
+// both finalize calls; `guard`: lirec_clip_finalize_guard's rules and kernel (max_norm 0 allowed, out[2], the skipped count)
+static int clip_finalize(bool guard, const double* partials, double* sq_dev, int32_t mode, float grad_scale, float max_norm,
+                         float* out, int64_t* skipped_dev, int32_t count, lirec_stream_t stream) {
   if (!sq_dev || !out || mode < 0 || mode > 2 || (mode != 2 && !partials)) return LIREC_EINVAL;
-  if (!(max_norm > 0.f)) return LIREC_EINVAL;                    // (NaN included)
-  if (((reinterpret_cast<uintptr_t>(partials) | reinterpret_cast<uintptr_t>(sq_dev)) & 7) != 0 ||
+  if (guard ? !(max_norm >= 0.f) : !(max_norm > 0.f)) return LIREC_EINVAL;                   // (NaN included)
+  if (count != 0 && !skipped_dev) return LIREC_EINVAL;
+  if (((reinterpret_cast<uintptr_t>(partials) | reinterpret_cast<uintptr_t>(sq_dev) | reinterpret_cast<uintptr_t>(skipped_dev)) & 7) != 0 ||
       (reinterpret_cast<uintptr_t>(out) & 3) != 0) return LIREC_EINVAL;
-  lirec::launch(clip_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, sq_dev, (int)mode, grad_scale, max_norm,
-                out);
+  auto kernel = guard ? clip_finalize_kernel<true> : clip_finalize_kernel<false>;
+  lirec::launch(kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, sq_dev, (int)mode, grad_scale, max_norm, out,
+                (long long*)skipped_dev, (int)(count != 0));
   LIREC_CHECK_LAUNCH();
   return LIREC_OK;
 }
 
+int lirec_clip_finalize(const double* partials, double* sq_dev, int32_t mode, float grad_scale, float max_norm, float* out,
+                        lirec_stream_t stream) {
+  return clip_finalize(false, partials, sq_dev, mode, grad_scale, max_norm, out, nullptr, 0, stream);
+}
+
 int lirec_clip_finalize_guard(const double* partials, double* sq_dev, int32_t mode, float grad_scale, float max_norm, float* out,
                               int64_t* skipped_dev, int32_t count, lirec_stream_t stream) {
-  if (!sq_dev || !out || mode < 0 || mode > 2 || (mode != 2 && !partials)) return LIREC_EINVAL;
-  if (!(max_norm >= 0.f)) return LIREC_EINVAL;                   // (NaN included; 0: no clipping)
-  if (count != 0 && !skipped_dev) return LIREC_EINVAL;
-  if (((reinterpret_cast<uintptr_t>(partials) | reinterpret_cast<uintptr_t>(sq_dev) | reinterpret_cast<uintptr_t>(skipped_dev)) & 7) != 0 ||
-      (reinterpret_cast<uintptr_t>(out) & 3) != 0) return LIREC_EINVAL;
-  lirec::launch(clip_finalize_guard_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, sq_dev, (int)mode, grad_scale,
-                max_norm, out, (long long*)skipped_dev, (int)(count != 0));
-  LIREC_CHECK_LAUNCH();
-  return LIREC_OK;
+  return clip_finalize(true, partials, sq_dev, mode, grad_scale, max_norm, out, skipped_dev, count, stream);
 }
 
 int lirec_set_adam_guard(const float* out_dev, const int64_t* skipped_dev) {
   if ((out_dev == nullptr) != (skipped_dev == nullptr)) return LIREC_EINVAL;
   if ((reinterpret_cast<uintptr_t>(out_dev) & 3) != 0 || (reinterpret_cast<uintptr_t>(skipped_dev) & 7) != 0) return LIREC_EINVAL;
-  t_adam_guard = out_dev;
-  t_adam_guard_skipped = skipped_dev;
+  t_adam.guard = out_dev;
+  t_adam.guard_skipped = skipped_dev;
   return LIREC_OK;
 }
 

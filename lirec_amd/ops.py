@@ -723,19 +723,27 @@ def adam_step(p, g, m, v, step, lr, beta1, beta2, eps, weight_decay, grad_scale=
                                 grad_scale, _p(step_dev), _stream()), 'lirec_adam_step')
 
 
+def _range_array(ranges, grouped=False):
+    """the ctypes table of a range call: AdamRange (``grouped``: AdamGroupRange) entries from ``ranges`` = (offset, length, lag) /
+    (offset, length, lag, group) tuples; a missing lag is 0.  An empty list gives one unused entry (the C side is handed a count)."""
+    from ._lib import AdamRange, AdamGroupRange
+    arr = ((AdamGroupRange if grouped else AdamRange) * max(len(ranges), 1))()
+    for a, r in zip(arr, ranges):
+        a.offset, a.length, a.lag = int(r[0]), int(r[1]), int(r[2]) if len(r) > 2 else 0
+        if grouped:
+            a.group = int(r[3])
+    return arr
+
+
 def adam_step_ranges(p, g, m, v, ranges, step, lr, beta1, beta2, eps, weight_decay, grad_scale=1.0, step_dev=None,
                      count_dev=None, ticket=None, advance=True):
     """lirec_adam_step_ranges: one launch over ``ranges`` = [(offset, length, lag), ...] (at most 64, ascending, offsets
     multiples of 4) of the flat buffers p, g, m, v given WHOLE (or from one common 16-byte-aligned base); range r is updated
     with step t - lag, t = ``step``, ``step_dev`` or ``count_dev`` + 1 (then ``ticket`` / ``advance`` as in adam_step_counted)."""
-    from ._lib import AdamRange
     n = p.numel()
     assert g.numel() == n and m.numel() == n and v.numel() == n
     assert all(0 <= o and 0 <= k and o + k <= n for o, k, _ in ranges), 'a range outside the buffers'
-    arr = (AdamRange * max(len(ranges), 1))()
-    for a, (o, k, lag) in zip(arr, ranges):
-        a.offset, a.length, a.lag = int(o), int(k), int(lag)
-    check(lib().lirec_adam_step_ranges(_p(p), _p(g), _p(m), _p(v), arr, len(ranges), int(step), lr, beta1, beta2, eps, weight_decay,
+    check(lib().lirec_adam_step_ranges(_p(p), _p(g), _p(m), _p(v), _range_array(ranges), len(ranges), int(step), lr, beta1, beta2, eps, weight_decay,
                                        grad_scale, _p(step_dev), _p(count_dev), _p(ticket), int(bool(advance)), _stream()),
           'lirec_adam_step_ranges')
 
@@ -758,15 +766,11 @@ def adam_step_groups(p, g, m, v, ranges, table, n_groups, step, grad_scale=1.0, 
                      advance=True):
     """lirec_adam_step_groups: adam_step_ranges over ``ranges`` = [(offset, length, lag, group), ...] with the hyper-parameters
     of a range read from row ``group`` of the device ``table`` (adam_hyper_write) of ``n_groups`` rows"""
-    from ._lib import AdamGroupRange
     n = p.numel()
     assert g.numel() == n and m.numel() == n and v.numel() == n
     assert all(0 <= o and 0 <= k and o + k <= n for o, k, _, _ in ranges), 'a range outside the buffers'
     assert table.dtype == torch.float32 and table.numel() >= 8 * n_groups
-    arr = (AdamGroupRange * max(len(ranges), 1))()
-    for a, (o, k, lag, grp) in zip(arr, ranges):
-        a.offset, a.length, a.lag, a.group = int(o), int(k), int(lag), int(grp)
-    check(lib().lirec_adam_step_groups(_p(p), _p(g), _p(m), _p(v), arr, len(ranges), _p(table), int(n_groups), int(step),
+    check(lib().lirec_adam_step_groups(_p(p), _p(g), _p(m), _p(v), _range_array(ranges, grouped=True), len(ranges), _p(table), int(n_groups), int(step),
                                        float(grad_scale), _p(step_dev), _p(count_dev), _p(ticket), int(bool(advance)), _stream()),
           'lirec_adam_step_groups')
 
@@ -801,11 +805,8 @@ class adam_hyper_map:
 
     def __enter__(self):
         if self.table is not None:
-            from ._lib import AdamGroupRange
             assert self.table.dtype == torch.float32
-            arr = (AdamGroupRange * max(len(self.ranges), 1))()
-            for a, (o, k, grp) in zip(arr, self.ranges):
-                a.offset, a.length, a.lag, a.group = int(o), int(k), 0, int(grp)
+            arr = _range_array([(o, k, 0, grp) for o, k, grp in self.ranges], grouped=True)
             check(lib().lirec_set_adam_hyper_map(_p(self.table), arr, len(self.ranges)), 'lirec_set_adam_hyper_map')
         return self
 
@@ -818,13 +819,10 @@ class adam_hyper_map:
 def grad_sq_partials(g, ranges, partials):
     """lirec_grad_sq_partials: ``partials`` (device float64[CLIP_PARTIALS]) = the fixed grid's sums of squares of ``g`` over
     ``ranges`` = [(offset, length), ...] (1..64, offsets multiples of 4; a third entry -- a lag -- is ignored)"""
-    from ._lib import AdamRange, CLIP_PARTIALS
+    from ._lib import CLIP_PARTIALS
     assert partials.dtype == torch.float64 and partials.numel() >= CLIP_PARTIALS and partials.is_contiguous()
     assert all(0 <= r[0] and 0 <= r[1] and r[0] + r[1] <= g.numel() for r in ranges), 'a range outside the buffer'
-    arr = (AdamRange * max(len(ranges), 1))()
-    for a, r in zip(arr, ranges):
-        a.offset, a.length = int(r[0]), int(r[1])
-    check(lib().lirec_grad_sq_partials(_p(_f32c(g)), arr, len(ranges), _p(partials), _stream()), 'lirec_grad_sq_partials')
+    check(lib().lirec_grad_sq_partials(_p(_f32c(g)), _range_array([r[:2] for r in ranges]), len(ranges), _p(partials), _stream()), 'lirec_grad_sq_partials')
 
 
 def clip_finalize(partials, sq, mode, grad_scale, max_norm, out):

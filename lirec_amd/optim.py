@@ -741,34 +741,33 @@ class FusedAdam(torch.optim.Optimizer):
         side stream's own counter, ``last``: this stretch is the last of the update (the last launch advances the counter).
         Under ``device_hyper`` every stretch is lirec_adam_step_groups launches, reading the table of issuing stream ``role``.
         Returns the number of launches issued."""
-        gs = g if g_is_slice else g[a:b]
+        bufs = (flat[a:b], g if g_is_slice else g[a:b], self._m[a:b], self._v[a:b])
+        step, hyper, gscale, step_dev = args[0], args[1:6], args[6], args[7]
+        if counted is not None:
+            step = 0
+        # the launch form: the groups' table, the whole stretch, or its trainable ranges
         if self.device_hyper:
-            chunks = self._chunks(self.trainable_ranges(a, b))
+            form, rs = 'groups', self.trainable_ranges(a, b)
             table, n_groups = self._table(role), len(self.param_groups)
-            for i, ch in enumerate(chunks):
-                rel = [(x - a, y - x, lag, grp) for x, y, lag, grp in ch]
-                if counted is not None:
-                    ops.adam_step_groups(flat[a:b], gs, self._m[a:b], self._v[a:b], rel, table, n_groups, 0, args[6],
-                                         count_dev=counted[0], ticket=counted[1], advance=last and i == len(chunks) - 1)
-                else:
-                    ops.adam_step_groups(flat[a:b], gs, self._m[a:b], self._v[a:b], rel, table, n_groups, args[0], args[6],
-                                         step_dev=args[7])
-            return len(chunks)
-        rs = [(a, b, 0)] if self._all_live else self.trainable_ranges(a, b)
-        if rs == [(a, b, 0)]:
-            if counted is not None:
-                ops.adam_step_counted(flat[a:b], gs, self._m[a:b], self._v[a:b], *args[1:7], counted[0], counted[1], advance=last)
-            else:
-                ops.adam_step(flat[a:b], gs, self._m[a:b], self._v[a:b], *args)
-            return 1
+        else:
+            rs = [(a, b, 0)] if self._all_live else self.trainable_ranges(a, b)
+            form = 'whole' if rs == [(a, b, 0)] else 'ranges'
         chunks = self._chunks(rs)
         for i, ch in enumerate(chunks):
-            rel = [(x - a, y - x, lag) for x, y, lag in ch]
+            rel = [(r[0] - a, r[1] - r[0]) + tuple(r[2:]) for r in ch]
+            # where the step comes from: the side stream's counter, which the update's last launch advances, or step / step_dev
             if counted is not None:
-                ops.adam_step_ranges(flat[a:b], gs, self._m[a:b], self._v[a:b], rel, 0, *args[1:7], count_dev=counted[0],
-                                     ticket=counted[1], advance=last and i == len(chunks) - 1)
+                src = dict(count_dev=counted[0], ticket=counted[1], advance=last and i == len(chunks) - 1)
             else:
-                ops.adam_step_ranges(flat[a:b], gs, self._m[a:b], self._v[a:b], rel, *args)
+                src = dict(step_dev=step_dev)
+            if form == 'groups':
+                ops.adam_step_groups(*bufs, rel, table, n_groups, step, gscale, **src)
+            elif form == 'ranges':
+                ops.adam_step_ranges(*bufs, rel, step, *hyper, gscale, **src)
+            elif counted is not None:
+                ops.adam_step_counted(*bufs, *hyper, gscale, **src)
+            else:
+                ops.adam_step(*bufs, step, *hyper, gscale, **src)
         return len(chunks)
 
     @staticmethod
