@@ -920,8 +920,26 @@ static int launch_gemm(int layout, GemmGroup& g, hipStream_t s, int site, int ta
   GemmGroup h;
   memset(&h, 0, sizeof(h));
   h.ablate = g_ablate; h.dyn_is_k = (layout == L_TN);
-  for (int i = 0; i < g.nprob; ++i)
-    if (g.p[i].M > 0 && g.p[i].N > 0) h.p[h.nprob++] = g.p[i];
+  for (int i = 0; i < g.nprob; ++i) {
+    const GemmProblem& p = g.p[i];
+    if (p.M <= 0 || p.N <= 0) continue;
+    if (p.K <= 0) {
+      // an empty reduction (the weight gradient of a head without rows): the product is zero, so an accumulating target keeps its
+      // value and an overwritten one is cleared -- no tile is planned (plan_tiles_v would divide by a chunk length of 0)
+      if (p.epi != EPI_STORE || p.bias != nullptr) return LIREC_EINVAL;
+      if (p.beta == 0.f)
+        for (int r = 0; r < (p.ldc == p.N ? 1 : p.M); ++r) {
+          const hipError_t e = lirec::memset_async(p.C + (long)r * p.ldc, 0, sizeof(float) * (size_t)(p.ldc == p.N ? (long)p.M * p.N : p.N), s);
+          if (e != hipSuccess) return (int)e;
+        }
+      if (p.dbias && p.dbias_set) {
+        const hipError_t e = lirec::memset_async(p.dbias, 0, sizeof(float) * (size_t)p.M, s);
+        if (e != hipSuccess) return (int)e;
+      }
+      continue;
+    }
+    h.p[h.nprob++] = p;
+  }
   switch (layout) {
     case L_NT: return launch_layout<L_NT>(h, meta, s);
     case L_NN: return launch_layout<L_NN>(h, meta, s);
