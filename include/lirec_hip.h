@@ -861,6 +861,59 @@ typedef struct {
 } lirec_predict_args;
 int lirec_predict_clips(const lirec_predict_args* a, lirec_stream_t stream);
 
+/* ---- collate on the device (resident piece store) ----------------------------------
+ * The loader's per-batch work for a dataset whose pieces AND whose stacked sample tables are resident: what
+ * lirec_amd.features.collate(store=, static_layout=True) + batch_to_device leave in the batch buffer, written by the device from
+ * B sample ids.  Everything is exact (integer gathers and one prefix sum), on the given stream, without a read-back or an
+ * allocation; every output element has one writer, so two calls on the same inputs give the same bytes.
+ *   ids          int32 [B]          sample ids (rows of index_rows and of every field's source)
+ *   index_rows   int32 [N, E, 3]    per sample E = T_max * (R + 1) entries: column 0 a clip-piece row, columns 1 and 2 track-piece
+ *                                   rows, -1 = zeros
+ *   n_clip_all, n_track_all         the piece stores' row counts; row n_all of a store is its zero row
+ *   fields[nf]   {src, row_bytes, dst}: field f of sample s is the row_bytes bytes at src + s * row_bytes
+ * Outputs (device):
+ *   feature_index int32 [B, E, 3]   column 0: the position of the entry's clip row in clip_rows; columns 1, 2: of its track row in
+ *                                   track_rows; a negative entry stays -1
+ *   clip_rows    int32 [n_clip_list]   the distinct non-negative values of column 0 over the batch, ascending (u of them), then
+ *                                   n_clip_all (the zero row) to the end of the list
+ *   track_rows   int32 [n_track_list]  the same over columns 1 and 2 together, padded with n_track_all
+ *   counts       int32 [2]          the used lengths with the zero-row entry: max(u, 1) + 1 per list
+ *   fields[f].dst                   [B, row_bytes] bytes: dst row b = src row ids[b], byte for byte (16-, 8- or 4-byte moves where
+ *                                   src, dst and row_bytes allow, else bytes)
+ * workspace: lirec_collate_workspace_bytes(n_clip_all, n_track_all) bytes, 16-byte aligned: a byte map and a rank table per store.
+ * The library owns its contents -- it is cleared inside every call, the caller promises nothing about it -- but two calls that
+ * share a workspace must be ordered (the same stream).  Four commands per call: the clear, the marks (plain byte stores of 1: every
+ * writer of a byte stores the same value), one workgroup per store that scans its map in chunks of 16384 rows with a carry and
+ * writes the row list, its padding and the count, and the grid that writes feature_index and copies the field rows.
+ * TRUSTED, not checked on the device: every id is in [0, N), every entry of index_rows in [-1, n_all) of its store, and the row
+ * lists are long enough for the batch (n_list >= min(B * E [* 2 for tracks], n_all) + 1, collate's static layout).  The host
+ * validates the tables once when it uploads them and the ids once per epoch.  (An entry outside its store is skipped by the
+ * kernels -- no store goes out of bounds -- and its feature_index is then not meaningful.)
+ * LIREC_EINVAL before any device call (also under the host-side dry run) for: a NULL struct; B, E, nf, n_*_all or workspace_bytes
+ * negative; nf over LIREC_COLLATE_MAX_FIELDS; a row_bytes < 1; n_clip_list or n_track_list < 2; a workspace smaller than
+ * lirec_collate_workspace_bytes or not 16-byte aligned; with B > 0: a NULL ids, index_rows, feature_index, clip_rows, track_rows,
+ * counts or workspace, E < 1, a field with a NULL src or dst; an int32 pointer that is not 4-byte aligned.  B == 0: no launch,
+ * LIREC_OK (the checks come first).  Recorded into a command list like every other launch (added to ABI 124 without a new number:
+ * two new exports and a new struct, index 17 of lirec_abi_sizeof). */
+#define LIREC_COLLATE_MAX_FIELDS 16
+typedef struct {
+  const void* src; int64_t row_bytes; void* dst;
+} lirec_collate_field;
+typedef struct {
+  const int32_t* ids;                     /* [B] */
+  const int32_t* index_rows;              /* [N, E, 3] */
+  int32_t* feature_index;                 /* [B, E, 3] */
+  int32_t* clip_rows; int32_t* track_rows;           /* [n_clip_list], [n_track_list] */
+  int32_t* counts;                        /* [2] */
+  void* workspace; int64_t workspace_bytes;
+  int64_t n_clip_all, n_track_all, n_clip_list, n_track_list;
+  int32_t B, E, nf, reserved_;
+  lirec_collate_field fields[LIREC_COLLATE_MAX_FIELDS];
+} lirec_collate_args;
+/* (pure host arithmetic; -1 for a negative count) */
+int64_t lirec_collate_workspace_bytes(int64_t n_clip_all, int64_t n_track_all);
+int lirec_collate_resident(const lirec_collate_args* a, lirec_stream_t stream);
+
 /* ---- feature assembly ---------------------------------------------
  * The reference's loader tiles every row of the (B, T, R+1, D) feature block on the host as
  *   [ clip piece (text | clip-visual) | track-1 piece | track-2 piece ]
@@ -905,7 +958,7 @@ int lirec_dropout_mask(uint8_t* keep, int32_t rows, int32_t cols, const lirec_dr
 int lirec_version(void);
 /* sizeof() of ABI struct `which` (5 = eval; 0 embed_fwd, 1 embed_bwd, 2 margin_loss, 3 dropout,
  * 4 rowsel, 6 linear_fwd, 7 linear_bwd, 8 embed_dx, 9 embed_dx_indexed, 10 adam_range, 11 adam_hyper, 12 adam_group_range,
- * 13 eval_topk, 15 predict; 14 is not assigned) so a binding can verify its mirror; -1 if unknown */
+ * 13 eval_topk, 15 predict, 17 collate; 14 and 16 are not assigned) so a binding can verify its mirror; -1 if unknown */
 int lirec_abi_sizeof(int which);
 /* GEMM core: 0 exact f32-input MFMA   1 one-thread-per-output HIP GEMM (bring-up cross-check)
  *            2 split-precision bf16x3 MFMA (fp32 in/out, ~2^-16 per product, up to 5.3x the f32 core)

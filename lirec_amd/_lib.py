@@ -157,6 +157,19 @@ class PredictArgs(C.Structure):
 
 
 PREDICT_MAX_K = 16            # LIREC_PREDICT_MAX_K
+COLLATE_MAX_FIELDS = 16       # LIREC_COLLATE_MAX_FIELDS
+
+
+class CollateField(C.Structure):
+    _fields_ = [('src', _vp), ('row_bytes', _i64), ('dst', _vp)]
+
+
+class CollateArgs(C.Structure):
+    """lirec_collate_args: a resident-store batch buffer written by the device (lirec_collate_resident)"""
+    _fields_ = [('ids', _vp), ('index_rows', _vp), ('feature_index', _vp), ('clip_rows', _vp), ('track_rows', _vp), ('counts', _vp),
+                ('workspace', _vp), ('workspace_bytes', _i64), ('n_clip_all', _i64), ('n_track_all', _i64), ('n_clip_list', _i64),
+                ('n_track_list', _i64), ('B', _i32), ('E', _i32), ('nf', _i32), ('reserved_', _i32),
+                ('fields', CollateField * COLLATE_MAX_FIELDS)]
 
 
 class LirecError(RuntimeError):
@@ -248,6 +261,8 @@ _PROTOS = {
     'lirec_eval_max_tracks': (_i32, [C.POINTER(EvalArgs), _vp]),
     'lirec_eval_clip_topk': (_i32, [C.POINTER(EvalTopkArgs), _vp]),
     'lirec_predict_clips': (_i32, [C.POINTER(PredictArgs), _vp]),
+    'lirec_collate_workspace_bytes': (_i64, [_i64, _i64]),
+    'lirec_collate_resident': (_i32, [C.POINTER(CollateArgs), _vp]),
     'lirec_cast_f64_f32': (_i32, [_vp, _vp, _i64, _vp]),
     'lirec_grid_pool': (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i64, _vp]),
     'lirec_rows_max': (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _vp]),
@@ -297,7 +312,7 @@ def lib():
                                                                                                       (9, EmbedDxIndexedArgs),
                                                                                                       (10, AdamRange), (11, AdamHyper),
                                                                                                       (12, AdamGroupRange), (13, EvalTopkArgs),
-                                                                                                      (15, PredictArgs)]:
+                                                                                                      (15, PredictArgs), (17, CollateArgs)]:
         if L.lirec_abi_sizeof(which) != C.sizeof(st):
             raise LirecError('ABI mismatch for %s: library %d bytes, binding %d bytes'
                              % (st.__name__, L.lirec_abi_sizeof(which), C.sizeof(st)))

@@ -62,6 +62,9 @@ def defaults() -> dict:
         pieces_gather=True,
         # training() over such a store: batches of a repeating buffer layout are stepped on by a recorded train step (lirec_amd.train)
         recorded_training=True,
+        # training() / testing() / predict() over such a store, gathered q32b path on a CUDA device: the batch buffer is written ON THE
+        # DEVICE from the sample ids (lirec_amd.loader.ResidentLoader, lirec_collate_resident) instead of collated by loader threads
+        device_collate=False,
         # a recorded train step (single GPU) folds the first-layer parameters' Adam update into the launch that finishes their
         # gradients, which also keeps the q32b form of the new weights for the next forward (lirec_amd/optim.py:arm_first_layer_update)
         fuse_dw1_adam=True,

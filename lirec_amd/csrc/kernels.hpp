@@ -2419,6 +2419,131 @@ __global__ __launch_bounds__(256) void predict_clips_kernel(const lirec_predict_
   }
 }
 
+// ---------------------------------------------------------------------------
+// Collate on the device (lirec_collate_resident): features._dedup + the takes of features.collate for a resident store.
+// Workspace: [ seen_clip | seen_track | rank_clip | rank_track ], every part rounded up to 256 bytes.  seen: one byte per store row
+// (+ the zero row, + the rounding: cleared with the rest, so the scan reads whole 16-byte words); rank: one int32 per store row,
+// written for the rows of the batch only -- nothing else is ever read from it.
+// ---------------------------------------------------------------------------
+constexpr int COLLATE_SCAN_THREADS = 1024;                    // one workgroup per store; 16 rows a thread: 16384 rows a round
+constexpr int COLLATE_SCAN_CHUNK = COLLATE_SCAN_THREADS * 16;
+
+struct collate_ws {
+  int64_t seen[2], rank[2], total;                            // byte offsets; seen[1] follows seen[0]: one clear
+  __host__ __device__ collate_ws(int64_t n_clip_all, int64_t n_track_all) {
+    const int64_t sc = (n_clip_all + 1 + 255) / 256 * 256, st = (n_track_all + 1 + 255) / 256 * 256;
+    seen[0] = 0;
+    seen[1] = sc;
+    rank[0] = sc + st;
+    rank[1] = rank[0] + (4 * (n_clip_all + 1) + 255) / 256 * 256;
+    total = rank[1] + (4 * (n_track_all + 1) + 255) / 256 * 256;
+  }
+};
+
+// entry i of the batch's [B, E, 3] index: its value in the stacked table and which store it names (0 clip, 1 track)
+__device__ __forceinline__ int collate_entry(const lirec_collate_args& a, long i, int& t) {
+  const long per = (long)a.E * 3, b = i / per, rem = i - b * per;
+  t = rem % 3 ? 1 : 0;
+  return a.index_rows[(long)a.ids[b] * per + rem];
+}
+
+// seen[v] = 1 for every entry v >= 0, one entry a thread: plain byte stores, every writer of a byte stores the same value
+__global__ __launch_bounds__(256) void collate_mark_kernel(const lirec_collate_args a) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)a.B * a.E * 3) return;
+  const collate_ws ws(a.n_clip_all, a.n_track_all);
+  int t;
+  const int v = collate_entry(a, i, t);
+  if (v >= 0 && (int64_t)v < (t ? a.n_track_all : a.n_clip_all)) ((unsigned char*)a.workspace + ws.seen[t])[v] = 1;
+}
+
+// One workgroup per store (blockIdx.x: 0 clip, 1 track): exclusive scan of its byte map in rounds of COLLATE_SCAN_CHUNK rows with a
+// carry -> the rank of every marked row, the row list (ascending by construction), its padding with the zero row, the used length.
+__global__ __launch_bounds__(COLLATE_SCAN_THREADS) void collate_rank_kernel(const lirec_collate_args a) {
+  __shared__ int wsum[COLLATE_SCAN_THREADS / 64];
+  const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const collate_ws ws(a.n_clip_all, a.n_track_all);
+  const int64_t n_all = t ? a.n_track_all : a.n_clip_all, n_list = t ? a.n_track_list : a.n_clip_list;
+  const uint4* seen = (const uint4*)((const unsigned char*)a.workspace + ws.seen[t]);
+  int* rank = (int*)((unsigned char*)a.workspace + ws.rank[t]);
+  int* rows = t ? a.track_rows : a.clip_rows;
+  const int64_t n16 = (n_all + 15) / 16;                      // (inside the cleared, 256-byte-rounded map)
+  int64_t carry = 0;
+  for (int64_t base = 0; base < n16; base += COLLATE_SCAN_THREADS) {
+    const int64_t u = base + tid;
+    uint4 w = make_uint4(0u, 0u, 0u, 0u);
+    if (u < n16) w = seen[u];
+    // (every byte is 0 or 1: the multiply adds the four of a word into its top byte)
+    const int c = (int)(((w.x * 0x01010101u) >> 24) + ((w.y * 0x01010101u) >> 24) + ((w.z * 0x01010101u) >> 24) +
+                        ((w.w * 0x01010101u) >> 24));
+    int inc = c;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int o = __shfl_up(inc, d, 64);
+      if (lane >= d) inc += o;
+    }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int k = 0; k < COLLATE_SCAN_THREADS / 64; ++k) {
+      const int s = wsum[k];
+      before += k < wave ? s : 0;
+      total += s;
+    }
+    if (c) {
+      int64_t r = carry + before + inc - c;
+      const unsigned words[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const int64_t row = u * 16 + j;
+        if (((words[j >> 2] >> (8 * (j & 3))) & 0xffu) && row < n_all) {
+          rank[row] = (int)r;
+          if (r < n_list) rows[r] = (int)row;
+          ++r;
+        }
+      }
+    }
+    carry += total;
+    __syncthreads();                                          // (wsum is written again in the next round)
+  }
+  for (int64_t i = carry + tid; i < n_list; i += COLLATE_SCAN_THREADS) rows[i] = (int)n_all;
+  if (tid == 0) a.counts[t] = (int)((carry > 1 ? carry : 1) + 1);
+}
+
+// blockIdx.y == 0: feature_index from the rank tables, one entry a thread.  blockIdx.y == 1 + f: the rows of field f, in moves
+// of the widest of 16 / 8 / 4 / 1 bytes that src, dst and row_bytes are all multiples of.
+template <typename V>
+__device__ __forceinline__ void collate_copy_rows(const lirec_collate_field& f, const int* __restrict__ ids, int B) {
+  const long per = f.row_bytes / (long)sizeof(V), n = (long)B * per;
+  const V* src = (const V*)f.src;
+  V* dst = (V*)f.dst;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const long b = i / per;
+    dst[i] = src[(long)ids[b] * per + (i - b * per)];
+  }
+}
+
+__global__ __launch_bounds__(256) void collate_emit_kernel(const lirec_collate_args a) {
+  if (blockIdx.y > 0) {
+    const lirec_collate_field& f = a.fields[blockIdx.y - 1];
+    const uintptr_t al = (uintptr_t)f.src | (uintptr_t)f.dst | (uintptr_t)f.row_bytes;
+    if ((al & 15) == 0) collate_copy_rows<uint4>(f, a.ids, a.B);
+    else if ((al & 7) == 0) collate_copy_rows<uint2>(f, a.ids, a.B);
+    else if ((al & 3) == 0) collate_copy_rows<unsigned>(f, a.ids, a.B);
+    else collate_copy_rows<unsigned char>(f, a.ids, a.B);
+    return;
+  }
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)a.B * a.E * 3) return;
+  const collate_ws ws(a.n_clip_all, a.n_track_all);
+  int t;
+  const int v = collate_entry(a, i, t);
+  int out = -1;
+  if (v >= 0 && (int64_t)v < (t ? a.n_track_all : a.n_clip_all)) out = ((const int*)((const unsigned char*)a.workspace + ws.rank[t]))[v];
+  a.feature_index[i] = out;
+}
+
 __global__ void dropout_mask_kernel(uint8_t* __restrict__ keep, int rows, int cols, unsigned seed_lo, unsigned seed_hi,
                                     const unsigned long long* __restrict__ seed_dev, unsigned site, unsigned thresh) {
   apply_seed_offset(seed_lo, seed_hi, seed_dev);

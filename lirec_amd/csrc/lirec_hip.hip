@@ -1137,6 +1137,7 @@ int lirec_abi_sizeof(int which) {
     case 12: return (int)sizeof(lirec_adam_group_range);
     case 13: return (int)sizeof(lirec_eval_topk_args);
     case 15: return (int)sizeof(lirec_predict_args);         // (14 stays unassigned)
+    case 17: return (int)sizeof(lirec_collate_args);         // (16 stays unassigned)
     default: return -1;
   }
 }
@@ -2733,6 +2734,45 @@ int lirec_predict_clips(const lirec_predict_args* a, lirec_stream_t stream) {
   if (shm > 160 * 1024) return LIREC_EINVAL;
   if (a->B == 0) return LIREC_OK;
   lirec::launch(predict_clips_kernel, dim3(a->B), dim3(256), (unsigned)shm, (hipStream_t)stream, *a);
+  LIREC_CHECK_LAUNCH();
+  return LIREC_OK;
+}
+
+int64_t lirec_collate_workspace_bytes(int64_t n_clip_all, int64_t n_track_all) {
+  if (n_clip_all < 0 || n_track_all < 0) return -1;
+  return collate_ws(n_clip_all, n_track_all).total;
+}
+
+int lirec_collate_resident(const lirec_collate_args* a, lirec_stream_t stream) {
+  if (!a) return LIREC_EINVAL;
+  constexpr int64_t ROWS_MAX = 0x7fffffff - 16;                   // rows and ranks are int32
+  if (a->B < 0 || a->E < 0 || a->nf < 0 || a->nf > LIREC_COLLATE_MAX_FIELDS || a->workspace_bytes < 0) return LIREC_EINVAL;
+  if (a->n_clip_all < 0 || a->n_track_all < 0 || a->n_clip_all > ROWS_MAX || a->n_track_all > ROWS_MAX) return LIREC_EINVAL;
+  if (a->n_clip_list < 2 || a->n_track_list < 2 || a->n_clip_list > ROWS_MAX || a->n_track_list > ROWS_MAX) return LIREC_EINVAL;
+  for (int f = 0; f < a->nf; ++f)
+    if (a->fields[f].row_bytes < 1) return LIREC_EINVAL;
+  if (a->workspace_bytes < lirec_collate_workspace_bytes(a->n_clip_all, a->n_track_all)) return LIREC_EINVAL;
+  const auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+  if (((at(a->ids) | at(a->index_rows) | at(a->feature_index) | at(a->clip_rows) | at(a->track_rows) | at(a->counts)) & 3) != 0 ||
+      (at(a->workspace) & 15) != 0)
+    return LIREC_EINVAL;
+  if (a->B > 0) {
+    if (!a->ids || !a->index_rows || !a->feature_index || !a->clip_rows || !a->track_rows || !a->counts || !a->workspace || a->E < 1)
+      return LIREC_EINVAL;
+    for (int f = 0; f < a->nf; ++f)
+      if (!a->fields[f].src || !a->fields[f].dst) return LIREC_EINVAL;
+  }
+  if (a->B == 0) return LIREC_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const collate_ws ws(a->n_clip_all, a->n_track_all);
+  // the two byte maps, rounding included: whatever an earlier call or another owner left there
+  const hipError_t e = lirec::memset_async(a->workspace, 0, (size_t)ws.rank[0], s);
+  if (e != hipSuccess) return (int)e;
+  const long entries = (long)a->B * a->E * 3;
+  const unsigned blocks = (unsigned)((entries + 255) / 256);
+  lirec::launch(collate_mark_kernel, dim3(blocks), dim3(256), 0, s, *a);
+  lirec::launch(collate_rank_kernel, dim3(2), dim3(COLLATE_SCAN_THREADS), 0, s, *a);
+  lirec::launch(collate_emit_kernel, dim3(blocks, 1 + a->nf), dim3(256), 0, s, *a);
   LIREC_CHECK_LAUNCH();
   return LIREC_OK;
 }

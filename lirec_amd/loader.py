@@ -68,3 +68,99 @@ class ThreadedLoader:
             stop.set()
             for _ in threads:
                 room.release()
+
+
+def device_collate_in_force(dataset, device=None) -> bool:
+    """``opt.device_collate`` asks for ``ResidentLoader``; it is used when the dataset keeps its pieces in a resident store, the
+    device is a GPU and the gathered q32b path is in force (what a recorded train step asks for, lirec_amd.train._recordable).
+    Anything else keeps ``ThreadedLoader``."""
+    from .config import opt
+    device = opt.device if device is None else device
+    return bool(getattr(opt, 'device_collate', False)) and getattr(dataset, 'store', None) is not None and \
+        getattr(dataset, 'emit', None) == 'pieces' and hasattr(dataset, 'device_tables') and str(device).startswith('cuda') and \
+        bool(getattr(opt, 'pieces_gather', True)) and bool(getattr(opt, 'pieces_q32b', False)) and bool(getattr(opt, 'layer1_planes', False))
+
+
+class ResidentLoader:
+    """Batches of a ``PiecesDataset(resident=True, emit='pieces')`` collated ON THE DEVICE: the stacked sample tables are uploaded
+    once (``PiecesDataset.device_tables``), an epoch's sample ids go up in one copy, and every ``next()`` is one
+    ``ops.collate_resident`` on the current stream -- no loader thread, no pinned staging buffer, no per-batch host-to-device copy,
+    no host read.  A batch has the keys, dtypes, shapes and values of ``batch_to_device(dataset.collate_fn(samples))`` -- device
+    views of one buffer, ``piece_store``, ``_layout``, ``_dev_blob`` -- without ``_blob`` / ``_slots`` / ``piece_counts`` (the row
+    lists' padding names the store's zero row, so their whole length may be used).  The batch sampler is drawn on the caller's
+    thread, all at once, exactly as ``ThreadedLoader`` with workers draws it: the same torch seed gives the same batches.
+
+    ``bind(layout, blob)``: from now on a batch of that layout is written straight into ``blob`` (the input buffer of a recorded
+    train step) instead of a buffer of its own; the call is stream-ordered behind whatever was enqueued before ``next()``, i.e.
+    behind the previous replay.  ``unbind()`` ends it.  ``n_collate`` / ``n_in_place`` count the collate calls and those that wrote
+    into the bound buffer.  The workspace belongs to the loader: its batches must be drawn on one stream."""
+
+    def __init__(self, dataset, batch_size=1, shuffle=False, sampler=None, drop_last=False, device='cuda'):
+        if getattr(dataset, 'store', None) is None or getattr(dataset, 'emit', None) != 'pieces':
+            raise ValueError('ResidentLoader needs a PiecesDataset(resident=True, emit=\'pieces\')')
+        self.dataset, self.device = dataset, torch.device(device)
+        if sampler is None:
+            sampler = torch.utils.data.RandomSampler(dataset) if shuffle else torch.utils.data.SequentialSampler(dataset)
+        self.batch_sampler = torch.utils.data.BatchSampler(sampler, batch_size, drop_last)
+        self.n_collate = self.n_in_place = 0
+        self._bound = None                  # (layout, blob)
+        self._layouts = {}                  # batch size -> (layout, nbytes)
+        self._tabs = self._ws = self._counts = None
+
+    def __len__(self):
+        return len(self.batch_sampler)
+
+    def bind(self, layout, blob):
+        self._bound = (tuple(layout), blob)
+
+    def unbind(self):
+        self._bound = None
+
+    def layout(self, B):
+        """(layout, bytes) of a batch of ``B`` samples: ``features.batch_layout``, the static form"""
+        if B not in self._layouts:
+            from .features import _FIELDS, batch_layout
+            st = self.dataset._stacked
+            fields = [(k, st[k].dtype, (B,) + tuple(st[k].shape[1:])) for k in _FIELDS]
+            world = self.dataset.world
+            clip_all, track_all, _ = world.piece_matrices()
+            self._layouts[B] = batch_layout((B,) + tuple(st['index_rows'].shape[1:]), fields,
+                                            n_all=(clip_all.shape[0], track_all.shape[0]))
+        return self._layouts[B]
+
+    def epoch_ids(self):
+        """the epoch's batches as lists of sample ids: the batch sampler drawn once, on the caller's thread"""
+        return [list(idx) for idx in self.batch_sampler]
+
+    def collate_ids(self, ids, B):
+        """one batch from ``B`` sample ids on the device (int32; validated by the caller)"""
+        from . import ops
+        from .features import _FIELDS, layout_views
+        if self._tabs is None:
+            self._tabs = self.dataset.device_tables(self.device)
+            self._ws = ops.collate_workspace(*self._tabs['n_all'], self.device)
+            self._counts = torch.empty(2, dtype=torch.int32, device=self.device)
+        layout, nbytes = self.layout(B)
+        in_place = self._bound is not None and self._bound[0] == tuple(layout)
+        blob = self._bound[1] if in_place else torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        out = layout_views(blob, layout)
+        tabs = self._tabs
+        ops.collate_resident(ids, tabs['index_rows'], tabs['n_all'][0], tabs['n_all'][1], out['feature_index'], out['clip_rows'],
+                             out['track_rows'], self._counts, [(tabs[k], out[k]) for k in _FIELDS], self._ws)
+        self.n_collate += 1
+        self.n_in_place += int(in_place)
+        out['piece_store'], out['_layout'], out['_dev_blob'] = self.dataset.store, layout, blob
+        return out
+
+    def __iter__(self):
+        import numpy as np
+        todo = self.epoch_ids()
+        flat = np.fromiter((i for idx in todo for i in idx), dtype=np.int64)
+        if flat.size and (int(flat.min()) < 0 or int(flat.max()) >= len(self.dataset)):
+            raise IndexError('ResidentLoader: the sampler drew a sample id outside [0, %d)' % len(self.dataset))
+        ids = torch.from_numpy(flat.astype(np.int32)).to(self.device)         # the epoch's order: one host-to-device copy
+        at = 0
+        for idx in todo:
+            B = len(idx)
+            yield self.collate_ids(ids[at:at + B], B)
+            at += B

@@ -1146,3 +1146,40 @@ def predict_clips(ints, rels=None, mem=None, B=None, T=1, K=5, loader_types=Fals
     a.loader_types = int(bool(loader_types))
     check(lib().lirec_predict_clips(C.byref(a), _stream()), 'lirec_predict_clips')
     return out
+
+
+def collate_workspace(n_clip_all, n_track_all, device):
+    """A workspace for ``collate_resident`` over stores of these row counts (uint8; the library clears it in every call)."""
+    need = int(lib().lirec_collate_workspace_bytes(int(n_clip_all), int(n_track_all)))
+    return torch.empty(max(need, 256), dtype=torch.uint8, device=device)
+
+
+def collate_resident(ids, index_rows, n_clip_all, n_track_all, feature_index, clip_rows, track_rows, counts, fields, workspace):
+    """One batch buffer of a resident-store dataset written on the device (lirec_collate_resident, include/lirec_hip.h): what
+    ``features.collate(store=, static_layout=True)`` + ``batch_to_device`` put there.  ``ids``: int32 [B] sample ids (trusted: the
+    caller validated them); ``index_rows``: int32 [N, E, 3] (or [N, T, R + 1, 3]) stacked sample table; ``feature_index`` int32
+    [B, E, 3], ``clip_rows`` / ``track_rows`` int32 row lists of the static layout's lengths, ``counts`` int32 [2]: written.
+    ``fields``: (src [N, ...], dst [B, ...]) pairs of contiguous tensors, rows copied byte for byte.  ``workspace``:
+    ``collate_workspace``.  Everything on the current stream; nothing is read back."""
+    B = ids.numel()
+    N = index_rows.shape[0]
+    E = index_rows.numel() // (3 * N) if N else 0
+    i32 = lambda t: t.dtype == torch.int32 and t.is_contiguous()
+    assert i32(ids) and i32(index_rows) and i32(feature_index) and i32(clip_rows) and i32(track_rows) and i32(counts), 'int32, contiguous'
+    assert index_rows.shape[-1] == 3 and feature_index.numel() == B * E * 3 and counts.numel() >= 2, (tuple(index_rows.shape), B, E)
+    assert workspace.dtype == torch.uint8 and workspace.is_contiguous()
+    assert len(fields) <= _lib.COLLATE_MAX_FIELDS, len(fields)
+    if B == 0:                # (an empty tensor has no address to hand over; the library's answer to B == 0 is "no launch" too)
+        return
+    a = _lib.CollateArgs()
+    a.ids, a.index_rows, a.feature_index = _p(ids), _p(index_rows), _p(feature_index)
+    a.clip_rows, a.track_rows, a.counts = _p(clip_rows), _p(track_rows), _p(counts)
+    a.workspace, a.workspace_bytes = _p(workspace), workspace.numel()
+    a.n_clip_all, a.n_track_all, a.n_clip_list, a.n_track_list = int(n_clip_all), int(n_track_all), clip_rows.numel(), track_rows.numel()
+    a.B, a.E, a.nf = B, E, len(fields)
+    for f, (src, dst) in enumerate(fields):
+        rb = src[0].numel() * src.element_size()
+        assert src.is_contiguous() and dst.is_contiguous() and src.shape[0] == N and dst.numel() * dst.element_size() == B * rb, \
+            (f, tuple(src.shape), tuple(dst.shape))
+        a.fields[f].src, a.fields[f].row_bytes, a.fields[f].dst = _p(src), rb, _p(dst)
+    check(lib().lirec_collate_resident(C.byref(a), _stream()), 'lirec_collate_resident')

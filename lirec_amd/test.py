@@ -21,7 +21,7 @@ import torch
 
 from . import ops
 from .config import opt
-from .loader import ThreadedLoader
+from .loader import ResidentLoader, ThreadedLoader, device_collate_in_force
 from .metrics import Precision, RelationshipsAcc
 from .util import Averaging
 
@@ -35,7 +35,9 @@ def testing(test_dataset, model, loss, total_iter=1, mode='val', train_start_tim
     sharded = world > 1 and bool(getattr(opt, 'dp_shard_eval', True))
     sampler = parallel.ShardSampler(len(test_dataset), opt.batch_size, shuffle=False, pad=False) if sharded else None
     verbose = verbose and (rank == 0 or not sharded)
-    if getattr(test_dataset, 'collate_fn', None) is not None:         # (piece tables + index, built on threads: lirec_amd/loader.py)
+    if device_collate_in_force(test_dataset):                          # (opt.device_collate: the batch buffer written on the device)
+        loader = ResidentLoader(test_dataset, batch_size=opt.batch_size, shuffle=False, sampler=sampler, drop_last=False, device=opt.device)
+    elif getattr(test_dataset, 'collate_fn', None) is not None:       # (piece tables + index, built on threads: lirec_amd/loader.py)
         loader = ThreadedLoader(test_dataset, batch_size=opt.batch_size, shuffle=False, sampler=sampler, num_workers=opt.num_workers,
                                 drop_last=False, collate_fn=test_dataset.collate_fn)
     else:

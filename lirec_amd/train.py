@@ -21,7 +21,7 @@ from datetime import datetime
 import torch
 
 from .config import opt
-from .loader import ThreadedLoader
+from .loader import ResidentLoader, ThreadedLoader, device_collate_in_force
 from .test import testing
 from .util import Averaging, ModelSaver, ema_entry, save_checkpoint
 
@@ -132,7 +132,13 @@ def training(train_dataset, **kwargs):
     # (a dataset may bring its own collate_fn / pin_memory -- lirec_amd.features.PiecesDataset does: de-duplicated piece
     #  tables + index instead of the tiled float64 block, built by `num_workers` THREADS (lirec_amd/loader.py says why);
     #  the protocol of mlp/train.py:33-37 is otherwise unchanged)
-    if getattr(train_dataset, 'collate_fn', None) is not None:
+    # (opt.device_collate over a resident store: the batch buffer is written on the device from the sample ids -- lirec_amd/loader.py,
+    #  ResidentLoader -- and, once a step is recorded, straight into that step's input buffer)
+    on_device_loader = device_collate_in_force(train_dataset)
+    if on_device_loader:
+        loader = ResidentLoader(train_dataset, batch_size=opt.batch_size, shuffle=sampler is None, sampler=sampler, drop_last=False,
+                                device=opt.device)
+    elif getattr(train_dataset, 'collate_fn', None) is not None:
         loader = ThreadedLoader(train_dataset, batch_size=opt.batch_size, shuffle=sampler is None, sampler=sampler,
                                 num_workers=opt.num_workers, drop_last=False, collate_fn=train_dataset.collate_fn)
     else:
@@ -142,6 +148,8 @@ def training(train_dataset, **kwargs):
     saver = ModelSaver(path=opt.store_root) if rank == 0 else None      # (the kept checkpoints live on rank 0)
     epoch = -1
     rec, last_layout, same_layout, ow_ok, dp_gave_up = None, None, 0, {}, False
+    # (what the last call did with its recorded step: replays, host- or device-side copies into its input buffer, and the loader)
+    stats = training.last = {'replays': 0, 'input_copies': 0, 'loader': loader}
     for epoch in range(opt.epochs):
         model.train()
         train_dataset.epoch = epoch
@@ -156,7 +164,22 @@ def training(train_dataset, **kwargs):
         if rec is not None and rec['flags'] != _flag_key(optimizer):       # a recipe flag changed (:49-51): the recorded step is stale
             rec['step'].release()
             rec, same_layout = None, 0
-        for i, batch in enumerate(loader):
+        def batches():
+            """the loader's batches; a device-collating loader is told before every draw where the recorded step's inputs are, so
+            that a batch of that layout is written there -- behind the previous replay on this stream -- and nowhere else"""
+            it = iter(loader)
+            while True:
+                if on_device_loader:
+                    if rec is not None:
+                        loader.bind(rec['layout'], rec['blob'])
+                    else:
+                        loader.unbind()
+                try:
+                    nxt = next(it)
+                except StopIteration:
+                    return
+                yield nxt
+        for i, batch in enumerate(batches()):
             data_time.update(time.time() - end)
             # A loader batch whose small tensors all live in ONE buffer of a layout that repeats from batch to batch (a resident
             # piece store: lirec_amd.features.collate, static_layout) is stepped on by a RECORDED train step (lirec_amd.graph):
@@ -172,8 +195,13 @@ def training(train_dataset, **kwargs):
                 if rec.get('released'):
                     rec['step'].resume()
                     rec['released'] = False
-                rec['blob'].copy_(batch['_blob'], non_blocking=True)
-                PinnedPool.copied(batch.get('_slots'))
+                if batch.get('_dev_blob') is rec['blob']:
+                    pass                          # (ResidentLoader wrote the batch into the step's inputs: nothing to copy)
+                else:
+                    rec['blob'].copy_(batch['_blob'], non_blocking=True)
+                    PinnedPool.copied(batch.get('_slots'))
+                    stats['input_copies'] += 1
+                stats['replays'] += 1
                 nlab = len(batch['labels'])
                 lval = rec['step'].step().clone()
                 sched_step()
@@ -324,3 +352,6 @@ def training(train_dataset, **kwargs):
     if opt.save_model:
         save_checkpoint(opt.resume_str, epoch, model, optimizer)
     return model
+
+
+training.last = {}
