@@ -1365,6 +1365,16 @@ static bool merge_groups(const GemmGroup& x, const GemmGroup& y, GemmGroup& out)
   return true;
 }
 
+// The same GEMM of one or two heads (`gs[0 .. n)`): one merged launch when the groups fit LIREC_MAX_PROB (two tiers of row panels
+// when the heads differ in rows), else one launch each, stopping at the first error.
+static int launch_gemm_heads(int layout, GemmGroup* gs, int n, hipStream_t s, int site, int tag = 0) {
+  GemmGroup m;
+  if (n == 2 && merge_groups(gs[0], gs[1], m)) return launch_gemm(layout, m, s, site, tag);
+  int rc = LIREC_OK;
+  for (int h = 0; !rc && h < n; ++h) rc = launch_gemm(layout, gs[h], s, site, tag);
+  return rc;
+}
+
 // Layer 1 of one or two heads (one grouped launch when they fit), then the pooling pass of the pooled heads.
 // stage_mode: 0 = stage everything, then the GEMM; 1 = stage the ROWS only (feature rows / row lists, dropout keep bytes, the
 // partition bound) and return -- parts = 4, what a caller runs for the NEXT batch beside this batch's backward; 2 = the rows are
@@ -1460,53 +1470,44 @@ static int embed_fwd_layer1_heads(const lirec_embed_fwd_args* const* hs, GemmGro
     if (stage_mode == 1) return rc;
     if (!rc) rc = launch_p2<L_NT>(m, s, PS_EMBED_L1_FWD, L[0].nt_bound, 0, L[0].gather, nullptr, L[0].gather ? gather_planes(hs, nh) : 2);
   } else {
-    GemmGroup m;
-    if (nh == 2 && merge_groups(g1[0], g1[1], m)) {
-      // both heads in one launch (two tiers of row panels when the heads differ in rows)
-      rc = launch_gemm(L_NT, m, s, PS_EMBED_L1_FWD, 1);
-    } else {
-      for (int h = 0; !rc && h < nh; ++h) rc = launch_gemm(L_NT, g1[h], s, PS_EMBED_L1_FWD, 1);
-    }
+    rc = launch_gemm_heads(L_NT, g1, nh, s, PS_EMBED_L1_FWD, 1);
   }
   for (int h = 0; !rc && h < nh; ++h) rc = embed_fwd_pool_only(hs[h], s);
   return rc;
 }
 
-int lirec_embed_fwd(const lirec_embed_fwd_args* a, lirec_stream_t stream) {
-  GemmGroup g1, g2;
-  int rc = embed_fwd_build(a, g1, g2);
-  if (rc) return rc;
-  if (a->rows == 0) return LIREC_OK;
-  if (a->parts < 0 || a->parts > 4) return LIREC_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  if (a->parts == 4) return embed_fwd_layer1_heads(&a, &g1, 1, s, 1);
-  if (a->parts == 3) rc = embed_fwd_pool_only(a, s);
-  else if (a->parts != 2) rc = embed_fwd_layer1_heads(&a, &g1, 1, s, a->rows_staged ? 2 : 0);
-  if (rc || a->parts == 1) return rc;
-  return launch_gemm(L_NT, g2, s, PS_EMBED_L2_FWD);
+// The forward of one head (lirec_embed_fwd) or two (lirec_embed_fwd2).  Every head is validated first, head 0 before head 1.  A
+// head without rows: the one-head call is done (before `parts` is looked at); the two-head call becomes the one-head calls, in order.
+static int embed_fwd_heads(const lirec_embed_fwd_args* const* hs, int nh, hipStream_t s) {
+  GemmGroup g1[2], g2[2];
+  int rc = LIREC_OK;
+  bool empty = false;
+  for (int h = 0; h < nh; ++h) {
+    rc = embed_fwd_build(hs[h], g1[h], g2[h]);
+    if (rc) return rc;
+    empty = empty || hs[h]->rows == 0;
+  }
+  if (empty) {
+    for (int h = 0; nh > 1 && !rc && h < nh; ++h) rc = embed_fwd_heads(&hs[h], 1, s);
+    return rc;
+  }
+  const int parts = hs[0]->parts;
+  if (parts < 0 || parts > 4) return LIREC_EINVAL;
+  for (int h = 1; h < nh; ++h)
+    if (hs[h]->parts != parts || (hs[h]->rows_staged != 0) != (hs[0]->rows_staged != 0)) return LIREC_EINVAL;
+  if (parts == 4) return embed_fwd_layer1_heads(hs, g1, nh, s, 1);
+  if (parts == 3) { for (int h = 0; !rc && h < nh; ++h) rc = embed_fwd_pool_only(hs[h], s); }
+  else if (parts != 2) rc = embed_fwd_layer1_heads(hs, g1, nh, s, hs[0]->rows_staged ? 2 : 0);
+  if (rc || parts == 1) return rc;
+  // the second layers of both heads run on the (pooled) candidate rows: one grouped launch
+  return launch_gemm_heads(L_NT, g2, nh, s, PS_EMBED_L2_FWD);
 }
 
+int lirec_embed_fwd(const lirec_embed_fwd_args* a, lirec_stream_t stream) { return embed_fwd_heads(&a, 1, (hipStream_t)stream); }
+
 int lirec_embed_fwd2(const lirec_embed_fwd_args* a, const lirec_embed_fwd_args* b, lirec_stream_t stream) {
-  GemmGroup g1[2], a2, b2, m2;
-  int rc = embed_fwd_build(a, g1[0], a2);
-  if (rc) return rc;
-  rc = embed_fwd_build(b, g1[1], b2);
-  if (rc) return rc;
-  if (a->rows == 0 || b->rows == 0) {
-    rc = lirec_embed_fwd(a, stream);
-    return rc ? rc : lirec_embed_fwd(b, stream);
-  }
-  hipStream_t s = (hipStream_t)stream;
-  if (a->parts < 0 || a->parts > 4 || b->parts != a->parts || (a->rows_staged != 0) != (b->rows_staged != 0)) return LIREC_EINVAL;
   const lirec_embed_fwd_args* hs[2] = {a, b};
-  if (a->parts == 4) return embed_fwd_layer1_heads(hs, g1, 2, s, 1);
-  if (a->parts == 3) { rc = embed_fwd_pool_only(a, s); if (!rc) rc = embed_fwd_pool_only(b, s); }
-  else if (a->parts != 2) rc = embed_fwd_layer1_heads(hs, g1, 2, s, a->rows_staged ? 2 : 0);
-  if (rc || a->parts == 1) return rc;
-  // the second layers of both heads run on the (pooled) candidate rows: one grouped launch
-  if (merge_groups(a2, b2, m2)) return launch_gemm(L_NT, m2, s, PS_EMBED_L2_FWD);
-  rc = launch_gemm(L_NT, a2, s, PS_EMBED_L2_FWD);
-  return rc ? rc : launch_gemm(L_NT, b2, s, PS_EMBED_L2_FWD);
+  return embed_fwd_heads(hs, 2, (hipStream_t)stream);
 }
 
 // Layer 1 of `nh` heads on the unique feature pieces (kernels.hpp, gather_act_kernel): the pre-activations of every piece
@@ -1775,21 +1776,35 @@ static int embed_bwd_tail_heads(const lirec_embed_bwd_args* const* hs, GemmGroup
   return rc;
 }
 
-int lirec_embed_bwd(const lirec_embed_bwd_args* a, lirec_stream_t stream) {
-  GemmGroup gw2, gdz, gw1;
-  int rc = embed_bwd_build(a, gw2, gdz, gw1);
-  if (rc) return rc;
-  if (a->rows == 0) return LIREC_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const int parts = a->parts;
-  if (parts < 0 || parts > 5) return LIREC_EINVAL;
-  if (parts == 5) return embed_bwd_unpool(a, s, 0);       // the un-pooling pass of 4 alone (lirec_embed_dw1_indexed follows)
-  if (parts == 0 || parts == 1) rc = launch_gemm(L_TN, gw2, s, PS_EMBED_DW2);
+// The backward of one head (lirec_embed_bwd) or two (lirec_embed_bwd2): validation order and heads without rows as in
+// embed_fwd_heads.  Part 5 is a one-head call.
+static int embed_bwd_heads(const lirec_embed_bwd_args* const* hs, int nh, hipStream_t s) {
+  GemmGroup gw2[2], gdz[2], gw1[2];
+  int rc = LIREC_OK;
+  bool empty = false;
+  for (int h = 0; h < nh; ++h) {
+    rc = embed_bwd_build(hs[h], gw2[h], gdz[h], gw1[h]);
+    if (rc) return rc;
+    empty = empty || hs[h]->rows == 0;
+  }
+  if (empty) {
+    for (int h = 0; nh > 1 && !rc && h < nh; ++h) rc = embed_bwd_heads(&hs[h], 1, s);
+    return rc;
+  }
+  const int parts = hs[0]->parts;
+  if (parts < 0 || parts > (nh == 1 ? 5 : 4)) return LIREC_EINVAL;
+  for (int h = 1; h < nh; ++h)
+    if (hs[h]->parts != parts) return LIREC_EINVAL;
+  if (parts == 5) return embed_bwd_unpool(hs[0], s, 0);   // the un-pooling pass of 4 alone (lirec_embed_dw1_indexed follows)
+  // second-layer weight gradients and the gradients w.r.t. the hidden layer: both heads in one launch each
+  if (parts == 0 || parts == 1) rc = launch_gemm_heads(L_TN, gw2, nh, s, PS_EMBED_DW2);
   if (rc || parts == 1) return rc;
-  if (parts != 4) rc = launch_gemm(L_NN, gdz, s, PS_EMBED_DZ1);
+  if (parts != 4) rc = launch_gemm_heads(L_NN, gdz, nh, s, PS_EMBED_DZ1);
   if (rc || parts == 3) return rc;
-  return embed_bwd_tail_heads(&a, &gw1, 1, s);
+  return embed_bwd_tail_heads(hs, gw1, nh, s);
 }
+
+int lirec_embed_bwd(const lirec_embed_bwd_args* a, lirec_stream_t stream) { return embed_bwd_heads(&a, 1, (hipStream_t)stream); }
 
 // The first-layer weight gradients of `nh` heads from the unique pieces (kernels.hpp, onehot_kernel): dZ1 is where parts 3
 // (+ 5 for the pooled form) left it, in the head's workspace.
@@ -1860,39 +1875,8 @@ int lirec_embed_dw1_indexed(const lirec_embed_bwd_args* const* heads, int32_t nh
 }
 
 int lirec_embed_bwd2(const lirec_embed_bwd_args* a, const lirec_embed_bwd_args* b, lirec_stream_t stream) {
-  GemmGroup aw2, adz, bw2, bdz, m, gw1[2];
-  int rc = embed_bwd_build(a, aw2, adz, gw1[0]);
-  if (rc) return rc;
-  rc = embed_bwd_build(b, bw2, bdz, gw1[1]);
-  if (rc) return rc;
-  if (a->rows == 0 || b->rows == 0) {
-    rc = lirec_embed_bwd(a, stream);
-    return rc ? rc : lirec_embed_bwd(b, stream);
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const int parts = a->parts;
-  if (parts < 0 || parts > 4 || b->parts != parts) return LIREC_EINVAL;
-  // second-layer weight gradients and the gradients w.r.t. the hidden layer: both heads in one launch each
-  if (parts == 0 || parts == 1) {
-    if (merge_groups(aw2, bw2, m)) {
-      rc = launch_gemm(L_TN, m, s, PS_EMBED_DW2);
-    } else {
-      rc = launch_gemm(L_TN, aw2, s, PS_EMBED_DW2);
-      if (!rc) rc = launch_gemm(L_TN, bw2, s, PS_EMBED_DW2);
-    }
-  }
-  if (rc || parts == 1) return rc;
-  if (parts != 4) {
-    if (merge_groups(adz, bdz, m)) {
-      rc = launch_gemm(L_NN, m, s, PS_EMBED_DZ1);
-    } else {
-      rc = launch_gemm(L_NN, adz, s, PS_EMBED_DZ1);
-      if (!rc) rc = launch_gemm(L_NN, bdz, s, PS_EMBED_DZ1);
-    }
-  }
-  if (rc || parts == 3) return rc;
   const lirec_embed_bwd_args* hs[2] = {a, b};
-  return embed_bwd_tail_heads(hs, gw1, 2, s);
+  return embed_bwd_heads(hs, 2, (hipStream_t)stream);
 }
 
 // Input-feature gradient (gemm_dx.hpp): dX = dZ1_s W1_s of every (head, segment) problem, scattered into the caller's
@@ -2094,15 +2078,48 @@ int lirec_pool_bwd(const float* dP, int64_t lddp, const float* mask, int32_t n, 
 }
 
 // ---------------------------------------------------------------------------
-int lirec_gate_fwd(const float* EE, int64_t ldee, const float* Wg, const float* bg, int32_t n, int32_t K,
-                   int32_t N, float* G, int64_t ldg, const lirec_dropout* drop, lirec_stream_t stream) {
-  if (!EE || !Wg || !G || n < 0 || K < 1 || N < 1) return LIREC_EINVAL;
-  GemmGroup g; g.nprob = 1;
+// The gate's three GEMMs, each built once with everything but its operands: the plain and the staged (_ws) entry points set
+// A / lda and B / ldb for their form of EE, Wg and dZg.
+// G = relu(EE Wg^T + bg), dropped out
+static void gate_fwd_problem(GemmGroup& g, const float* bg, int n, int K, int N, float* G, int64_t ldg, const lirec_dropout* drop) {
+  memset(&g, 0, sizeof(g)); g.nprob = 1;
   GemmProblem p = make_problem();
-  p.A = EE; p.lda = ldee; p.B = Wg; p.ldb = K; p.bias = bg; p.C = G; p.ldc = ldg;
+  p.bias = bg; p.C = G; p.ldc = ldg;
   p.M = n; p.N = N; p.K = K; p.epi = EPI_DROP_RELU;
   set_dropout(p, drop, drop ? drop->site : LIREC_SITE_GATE, 0);
   g.p[0] = p;
+}
+// dWg = dZg^T EE, dbg = column sums of dZg
+static void gate_dw_problem(GemmGroup& g, int n, int K, int N, float* dWg, float* dbg) {
+  memset(&g, 0, sizeof(g)); g.nprob = 1;
+  GemmProblem p = make_problem();
+  p.C = dWg; p.ldc = K;
+  p.M = N; p.N = K; p.K = n;
+  p.beta = grad_beta(); p.dbias_set = g_grad_overwrite; p.dbias = dbg;
+  g.p[0] = p;
+}
+// dEE = (dZg Wg) * tanh'/dropout factor: two column ranges, [0, split) and [split, K), with their own dropout streams
+static void gate_dee_problems(GemmGroup& g, int n, int K, int N, int split, const float* Tn, int64_t ldtn, float* dEE, int64_t lddee,
+                              int acc_first, const lirec_dropout* drop, int site_ctx, int site_ints) {
+  memset(&g, 0, sizeof(g)); g.nprob = 2;
+  for (int h = 0; h < 2; ++h) {
+    const int c0 = h == 0 ? 0 : split, nc = h == 0 ? split : K - split;
+    GemmProblem p = make_problem();
+    p.C = dEE + c0; p.ldc = lddee;
+    p.M = n; p.N = nc; p.K = N;
+    p.epi = EPI_TANH_BWD; p.aux = Tn + c0; p.ldaux = ldtn;
+    p.beta = (h == 0 && acc_first) ? 1.f : 0.f;
+    set_dropout(p, drop, h == 0 ? site_ctx : site_ints, 0);
+    g.p[h] = p;
+  }
+}
+
+int lirec_gate_fwd(const float* EE, int64_t ldee, const float* Wg, const float* bg, int32_t n, int32_t K,
+                   int32_t N, float* G, int64_t ldg, const lirec_dropout* drop, lirec_stream_t stream) {
+  if (!EE || !Wg || !G || n < 0 || K < 1 || N < 1) return LIREC_EINVAL;
+  GemmGroup g;
+  gate_fwd_problem(g, bg, n, K, N, G, ldg, drop);
+  g.p[0].A = EE; g.p[0].lda = ldee; g.p[0].B = Wg; g.p[0].ldb = K;
   return launch_gemm(L_NT, g, (hipStream_t)stream, PS_GATE_FWD);
 }
 
@@ -2125,27 +2142,18 @@ int lirec_gate_bwd_parts(const float* dZg, int64_t lddzg, const float* EE, int64
   hipStream_t s = (hipStream_t)stream;
   int rc = LIREC_OK;
   if (parts != 2) {
-    GemmGroup gw; gw.nprob = 1;
-    GemmProblem w = make_problem();
-    w.A = dZg; w.lda = lddzg; w.B = EE; w.ldb = ldee; w.C = dWg; w.ldc = K;
-    w.M = N; w.N = K; w.K = n; w.beta = grad_beta(); w.dbias_set = g_grad_overwrite; w.dbias = dbg;
-    gw.p[0] = w;
+    GemmGroup gw;
+    gate_dw_problem(gw, n, K, N, dWg, dbg);
+    gw.p[0].A = dZg; gw.p[0].lda = lddzg; gw.p[0].B = EE; gw.p[0].ldb = ldee;
     rc = launch_gemm(L_TN, gw, s, PS_GATE_DW);
   }
   if (rc || parts == 1) return rc;
-  // dEE = (dZg Wg) * tanh'/dropout factor, two column ranges with their own dropout streams
-  GemmGroup gd; gd.nprob = 2;
+  GemmGroup gd;
+  gate_dee_problems(gd, n, K, N, split, Tn, ldtn, dEE, lddee, acc_first, drop, site_ctx, site_ints);
   for (int h = 0; h < 2; ++h) {
-    const int c0 = h == 0 ? 0 : split, nc = h == 0 ? split : K - split;
-    GemmProblem p = make_problem();
+    GemmProblem& p = gd.p[h];
     p.A = dZg; p.lda = lddzg;
-    p.B = Wg + c0; p.ldb = K;
-    p.C = dEE + c0; p.ldc = lddee;
-    p.M = n; p.N = nc; p.K = N;
-    p.epi = EPI_TANH_BWD; p.aux = Tn + c0; p.ldaux = ldtn;
-    p.beta = (h == 0 && acc_first) ? 1.f : 0.f;
-    set_dropout(p, drop, h == 0 ? site_ctx : site_ints, 0);
-    gd.p[h] = p;
+    p.B = Wg + (h == 0 ? 0 : split); p.ldb = K;
   }
   return launch_gemm(L_NN, gd, s, PS_GATE_DEE);
 }
@@ -2264,15 +2272,9 @@ int lirec_gate_fwd_ws(const float* EE, int64_t ldee, const float* Wg, const floa
   int rc = launch_gate_stage(q, s);
   if (rc) return rc;
   GemmGroup g;
-  memset(&g, 0, sizeof(g));
-  g.nprob = 1;
-  GemmProblem p = make_problem();
-  p.A = reinterpret_cast<const float*>(w.eq); p.lda = K;
-  p.B = reinterpret_cast<const float*>(w.wq); p.ldb = K;
-  p.bias = bg; p.C = G; p.ldc = ldg;
-  p.M = n; p.N = N; p.K = K; p.epi = EPI_DROP_RELU;
-  set_dropout(p, drop, drop ? drop->site : LIREC_SITE_GATE, 0);
-  g.p[0] = p;
+  gate_fwd_problem(g, bg, n, K, N, G, ldg, drop);
+  g.p[0].A = reinterpret_cast<const float*>(w.eq); g.p[0].lda = K;
+  g.p[0].B = reinterpret_cast<const float*>(w.wq); g.p[0].ldb = K;
   if (gate_p3_ok(n, K, N, K / 2)) {
     // wave-specialised persistent kernel (gemm_p3.hpp), 128 x 96 tiles: 256 of them at the bench shape
     const int ni = p3_pick_ni(n, N, (N & 127) == 0);
@@ -2322,15 +2324,9 @@ int lirec_gate_bwd_ws(const float* dZg, int64_t lddzg, const float* EE, int64_t 
     if (p3 && ldee == K) {
       // dWg = dZg^T EE (+ dbg = row sums of dZg^T) from the transposed rows of both (EE^T: staged by the forward call)
       GemmGroup gw;
-      memset(&gw, 0, sizeof(gw));
-      gw.nprob = 1;
-      GemmProblem p = make_problem();
-      p.A = reinterpret_cast<const float*>(w.zqT); p.lda = n;
-      p.B = reinterpret_cast<const float*>(w.eqT); p.ldb = n;
-      p.C = dWg; p.ldc = K;
-      p.M = N; p.N = K; p.K = n;
-      p.beta = grad_beta(); p.dbias_set = g_grad_overwrite; p.dbias = dbg;
-      gw.p[0] = p;
+      gate_dw_problem(gw, n, K, N, dWg, dbg);
+      gw.p[0].A = reinterpret_cast<const float*>(w.zqT); gw.p[0].lda = n;
+      gw.p[0].B = reinterpret_cast<const float*>(w.eqT); gw.p[0].ldb = n;
       ow_note_group(gw);
       const unsigned grid = p3_setup(gw, 128, 96, !(g_ablate & 32768));
       const int pi = prof_start(PS_GATE_DW, s);
@@ -2346,20 +2342,13 @@ int lirec_gate_bwd_ws(const float* dZg, int64_t lddzg, const float* EE, int64_t 
   if (rc || parts == 1) return rc;
   // dEE = (dZg Wg) * tanh'/dropout factor on the staged rows of dZg and the q32b Wg (p3: Wg^T) the FORWARD call staged
   GemmGroup gd;
-  memset(&gd, 0, sizeof(gd));
-  gd.nprob = 2;
+  gate_dee_problems(gd, n, K, N, split, Tn, ldtn, dEE, lddee, acc_first, drop, site_ctx, site_ints);
   for (int h = 0; h < 2; ++h) {
-    const int c0 = h == 0 ? 0 : split, nc = h == 0 ? split : K - split;
-    GemmProblem p = make_problem();
+    const int c0 = h == 0 ? 0 : split;
+    GemmProblem& p = gd.p[h];
     p.A = reinterpret_cast<const float*>(w.zq); p.lda = N;
     if (p3) { p.B = reinterpret_cast<const float*>(w.wqT + 4096L * (c0 / 32) * (g_gemm_mode == 3 ? N / 64 : N / 32)); p.ldb = N; }    // rows c0 .. of Wg^T [K][N] (single pass: q16c)
     else { p.B = reinterpret_cast<const float*>(w.wq + 4096L * (c0 / 32)); p.ldb = K; }
-    p.C = dEE + c0; p.ldc = lddee;
-    p.M = n; p.N = nc; p.K = N;
-    p.epi = EPI_TANH_BWD; p.aux = Tn + c0; p.ldaux = ldtn;
-    p.beta = (h == 0 && acc_first) ? 1.f : 0.f;
-    set_dropout(p, drop, h == 0 ? site_ctx : site_ints, 0);
-    gd.p[h] = p;
   }
   if (p3) {
     const int ni = p3_pick_ni(n, K, (split & 127) == 0 && ((K - split) & 127) == 0);

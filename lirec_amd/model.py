@@ -24,6 +24,7 @@ GPU raises.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 import torch
@@ -55,6 +56,31 @@ def _dev_tensor(t, device, dtype):
         return ops.keep(t.to(device=device, non_blocking=True).to(dtype).contiguous())
     # (ops.keep: a copy made here while a step is being RECORDED is referred to by address from the command list)
     return ops.keep(t.to(device=device, dtype=dtype, non_blocking=True).contiguous())
+
+
+class _Head(collections.namedtuple('_Head', 'mods segs pooled sites col')):
+    """One embedding head, described once (where ``_mods_*`` / ``_segs_*`` are set): its (layer-1, layer-2) module names, its
+    ``ops.Segments``, whether it is the pooled (context) head, and its two dropout sites (H1, E).  A candidate's block is R + 1
+    feature rows: the interaction head runs on row 0 of each, the context head on rows 1..R (pooled over R); in [E_ctx | E_ints]
+    (EE, Tn, dEE) the context head's columns come first: ``col`` is the head's first column there."""
+
+    def rows(self, n, R, Rp1):
+        """(row selector (group, stride, off), row count) for n candidates"""
+        return ((R, Rp1, 1), n * R) if self.pooled else ((1, Rp1, 0), n)
+
+    def weights(self, model):
+        """(W1, b1, W2, b2), one tensor per segment each"""
+        W1, b1 = zip(*[model._W(a) for a, _ in self.mods])
+        W2, b2 = zip(*[model._W(b) for _, b in self.mods])
+        return W1, b1, W2, b2
+
+    def layer_weights(self, model, layer):
+        """the weight tensors of layer 1 (``layer`` 0) or layer 2 (1) alone, one per segment"""
+        return [model._W(m[layer])[0] for m in self.mods]
+
+    def grads(self, model):
+        """(dW1, db1, dW2, db2): the views of the flat gradient buffer, one per segment each"""
+        return tuple([model._g(m[layer] + kind) for m in self.mods] for layer in (0, 1) for kind in ('.weight', '.bias'))
 
 
 # ---------------------------------------------------------------------------
@@ -201,6 +227,16 @@ class _HotPathModule(nn.Module):
             mods.append(('tracks1_' + h, 'tracks12_' + h)); off.append(td + vd); dim.append(kd); out.append(J // 2)
             mods.append(('tracks2_' + h, 'tracks22_' + h)); off.append(td + vd + kd); dim.append(kd); out.append(J // 2)
         return mods, ops.Segments(off, dim, out)
+
+    def _describe_head(self, which, h, *use):
+        """``_head_i`` / ``_head_c`` (and its ``_mods_*`` / ``_segs_*``): the head as prestage, forward and backward take it.  The
+        context head first: the interaction head's columns lie behind its"""
+        mods, segs = self._segments(h, *use)
+        ctx = which == 'c'
+        head = _Head(mods, segs, ctx, (SITE_H1_CTX, SITE_E_CTX) if ctx else (SITE_H1_INTS, SITE_E_INTS),
+                     0 if (ctx or not self._has_ctx) else self._segs_c.width)
+        for name, value in (('_mods_', mods), ('_segs_', segs), ('_head_', head)):
+            setattr(self, name + which, value)
 
     def _finish_init(self):
         self._plist = [p for _, p in self.named_parameters()]
@@ -489,16 +525,13 @@ class _HotPathModule(nn.Module):
         p = float(opt.dropout)
         d = into['dummy'] if into else ops.new(64, dtype=torch.float32, device=dev)
         args = []
-        for mods, segs, sel, rows, sites, pool in ((self._mods_i, self._segs_i, (1, Rp1, 0), n, (SITE_H1_INTS, SITE_E_INTS), None),
-                                                   (self._mods_c, self._segs_c, (R, Rp1, 1), n * R, (SITE_H1_CTX, SITE_E_CTX),
-                                                    (None, R, clamp, d, d, cmp))):
-            W1, b1 = zip(*[self._W(a) for a, _ in mods])
-            W2, b2 = zip(*[self._W(b) for _, b in mods])
-            a = ops.embed_fwd_args(X, D, sel, rows, J, segs, W1, b1, W2, b2, d, _ptr(d), 4, _ptr(d), 4, 1,
-                                   ops.make_dropout(seed, p, sites[0], sites[1], self._seed_dev), pool=pool,
-                                   planes=pl_i if pool is None else pl_c)
-            args.append(ops.with_parts(a, 4))
-        ops.embed_fwd2(args[0], args[1])
+        for head in (self._head_i, self._head_c):
+            sel, rows = head.rows(n, R, Rp1)
+            args.append(ops.embed_fwd_args(X, D, sel, rows, J, head.segs, *head.weights(self), d, _ptr(d), 4, _ptr(d), 4, 1,
+                                           ops.make_dropout(seed, p, *head.sites, self._seed_dev),
+                                           pool=(None, R, clamp, d, d, cmp) if head.pooled else None,
+                                           planes=pl_c if head.pooled else pl_i))
+        ops.embed_fwd_heads(args, 4)
         return {'X': X.data_ptr(), 'mask': mask.data_ptr(), 'n': n, 'R': R, 'seed': fwd_seed, 'seed_dev': self._seed_dev is not None,
                 'cmp': cmp, 'planes_i': pl_i, 'planes_c': pl_c, 'dummy': d, '_keep': (X, mask)}
 
@@ -540,26 +573,26 @@ class _HotPathModule(nn.Module):
         EE = ops.new((n, Wc + Wi), dtype=torch.float32, device=dev)     # [E_ctx | E_ints]
         Tn = ops.new_like(EE)
         ldee = Wc + Wi
+        args_i = args_c = None
+
+        def head_args(head, H1, pl, **kw):
+            sel, rows = head.rows(n, R, Rp1)
+            return ops.embed_fwd_args(X, D, sel, rows, J, head.segs, *head.weights(self), H1, _ptr(EE, head.col), ldee, _ptr(Tn, head.col), ldee,
+                                      1, self._dropout(*head.sites), planes=pl, pieces=pq, rows_staged=pre is not None,
+                                      W1q=self._w1q_of(head.mods, pl), **kw)
         if has_i:
-            mods, segs = self._mods_i, self._segs_i
-            H1 = ops.new((n, segs.n * J), dtype=torch.float32, device=dev)
-            W1, b1 = zip(*[self._W(a) for a, _ in mods])
-            W2, b2 = zip(*[self._W(b) for _, b in mods])
-            pl = pre['planes_i'] if pre is not None else self._planes_buffer(X, n, segs, J)
-            args_i = ops.embed_fwd_args(X, D, (1, Rp1, 0), n, J, segs, W1, b1, W2, b2, H1, _ptr(EE, Wc), ldee,
-                                        _ptr(Tn, Wc), ldee, 1, self._dropout(SITE_H1_INTS, SITE_E_INTS), planes=pl, pieces=pq,
-                                        rows_staged=pre is not None, W1q=self._w1q_of(mods, pl))
+            H1 = ops.new((n, self._segs_i.n * J), dtype=torch.float32, device=dev)
+            pl = pre['planes_i'] if pre is not None else self._planes_buffer(X, n, self._segs_i, J)
+            args_i = head_args(self._head_i, H1, pl)
             st['H1_i'], st['planes_i'] = H1, pl
         if has_c:
             # context head in the pooled form: layer 1 on the n*R context rows, masked mean over R
             # applied to H1 (linear, so it commutes with the second Linear), layer 2 + tanh + dropout
             # on the n pooled rows
-            mods, segs = self._mods_c, self._segs_c
+            segs = self._segs_c
             H1 = ops.new((n * R, segs.n * J), dtype=torch.float32, device=dev)
             Hbar = ops.new((n, segs.n * J), dtype=torch.float32, device=dev)
             fsc = ops.new((n,), dtype=torch.float32, device=dev)
-            W1, b1 = zip(*[self._W(a) for a, _ in mods])
-            W2, b2 = zip(*[self._W(b) for _, b in mods])
             # only context rows with a non-zero mask can influence anything: compact them on the device
             # (no host sync) and run layer 1 / pooling / un-pooling / dW1 on the valid rows only
             # (the mask is read in the loader's own dtype -- int64 -- by the compaction kernel, which also leaves the
@@ -580,9 +613,7 @@ class _HotPathModule(nn.Module):
             hb = None
             if self.training and getattr(opt, 'h1_sign_bits', True) and R <= 64 and W_c % 4 == 0:
                 hb = ops.new(max(ops.hbits_bytes(n * R, W_c), 16), dtype=torch.uint8, device=dev)
-            args_c = ops.embed_fwd_args(X, D, (R, Rp1, 1), n * R, J, segs, W1, b1, W2, b2, H1, _ptr(EE), ldee, _ptr(Tn), ldee,
-                                        1, self._dropout(SITE_H1_CTX, SITE_E_CTX), pool=(mask, R, clamp, Hbar, fsc, cmp),
-                                        planes=pl, pieces=pq, hbits=hb, rows_staged=pre is not None, W1q=self._w1q_of(mods, pl))
+            args_c = head_args(self._head_c, H1, pl, pool=(mask, R, clamp, Hbar, fsc, cmp), hbits=hb)
             st['Hbar'], st['fsc'], st['cmp'], st['planes_c'], st['hbits_c'] = Hbar, fsc, cmp, pl, hb
             st['H1_c'] = H1 if (hb is None or self.debug_keep_state) else None
         st['EE'], st['Tn'] = EE, Tn
@@ -625,6 +656,8 @@ class _HotPathModule(nn.Module):
             lane0 = self._wgrad_lane()
             if lane0 is not None:
                 deferred_join = (ops.current_stream_handle(), C.c_void_p(lane0[0].cuda_stream))
+        # (waiter, signaller) of the wait in front of the second layers: the staging's pair, else the deferred pair, else none
+        join = w_side if (has_g and w_side is not None) else deferred_join
         st['pieces'] = pieces if pq is None else None          # (q32b rows staged from the pieces: backward is the dense path's)
         # (rows GATHERED from q32b piece tables: backward reads them through the same tables and index)
         st['pieces_gather'] = pq if (pq is not None and isinstance(pieces['clip'], ops.Q32Block)) else None
@@ -636,44 +669,27 @@ class _HotPathModule(nn.Module):
             nc, nt = pieces['clip'].shape[0], pieces['track'].shape[0]
             zs = [ops.new((m, 2 * J), dtype=torch.float32, device=dev) for m in (nc, nt, nc, nt)]
             ops.embed_l1_indexed([args_i, args_c], pc, [zs[0], zs[2]], [zs[1], zs[3]])
-            if has_g and w_side is not None:
-                ops.stream_wait(*w_side)            # (in front of the second layers: see the dense path below)
-            elif deferred_join is not None:
-                ops.stream_wait(*deferred_join)
-            ops.embed_fwd2(ops.with_parts(args_i, 3), ops.with_parts(args_c, 3))
-            if has_g:
-                ops.gate_fwd(EE, ldee, Wg, bg, n, ldee, N, G, N, self._dropout(SITE_GATE), ws=st['gate_ws'],
-                             weights_staged=w_side is not None)
+            if join is not None:
+                ops.stream_wait(*join)              # (in front of the second layers: see the dense path below)
+            ops.embed_fwd_heads([args_i, args_c], 3)
+        elif join is not None:
+            # The step's stream joins the side stream IN FRONT OF THE SECOND LAYERS, not just in front of the gate: a replayed
+            # step leaves that stream un-joined (`_defer_side_join`), and what it may still be running from the previous step
+            # reads the heads' inputs -- EE, which the second layers are about to overwrite (the context / relationship heads'
+            # weight gradients), and the gate's staged rows.  Behind layer 1 and the pooling pass (~250 us into the step) the
+            # join waits for nothing in practice; in front of them it would give the deferral's overlap away.  Same launches in
+            # the same order: layer 1 + pooling (parts = 1), then the second layers (parts = 2).
+            # (the deferred join without the staging of the gate's weights on the side stream -- strict-f32 core, shapes the
+            #  q32b gate does not take, opt.gate_stage_on_side off: the same join at the same place, unconditionally)
+            ops.embed_fwd_heads([args_i, args_c], 1)
+            ops.stream_wait(*join)
+            ops.embed_fwd_heads([args_i, args_c], 2)
         else:
             # both heads in one library call when the model has both: their second layers share a launch
-            def layers(parts):
-                if has_i and has_c:
-                    ops.embed_fwd2(ops.with_parts(args_i, parts), ops.with_parts(args_c, parts)) if parts else ops.embed_fwd2(args_i, args_c)
-                elif has_i:
-                    ops.embed_fwd(args=ops.with_parts(args_i, parts) if parts else args_i)
-                elif has_c:
-                    ops.embed_fwd(args=ops.with_parts(args_c, parts) if parts else args_c)
-            if has_g and w_side is not None:
-                # The step's stream joins the side stream IN FRONT OF THE SECOND LAYERS, not just in front of the gate: a replayed
-                # step leaves that stream un-joined (`_defer_side_join`), and what it may still be running from the previous step
-                # reads the heads' inputs -- EE, which the second layers are about to overwrite (the context / relationship heads'
-                # weight gradients), and the gate's staged rows.  Behind layer 1 and the pooling pass (~250 us into the step) the
-                # join waits for nothing in practice; in front of them it would give the deferral's overlap away.  Same launches in
-                # the same order: layer 1 + pooling (parts = 1), then the second layers (parts = 2).
-                layers(1)
-                ops.stream_wait(*w_side)
-                layers(2)
-            elif deferred_join is not None:
-                # (the deferred join without the staging of the gate's weights on the side stream -- strict-f32 core, shapes the
-                #  q32b gate does not take, opt.gate_stage_on_side off: the same join at the same place, unconditionally)
-                layers(1)
-                ops.stream_wait(*deferred_join)
-                layers(2)
-            else:
-                layers(0)
-            if has_g:
-                ops.gate_fwd(EE, ldee, Wg, bg, n, ldee, N, G, N, self._dropout(SITE_GATE), ws=st['gate_ws'],
-                             weights_staged=w_side is not None)
+            ops.embed_fwd_heads([args_i, args_c])
+        if has_g:
+            ops.gate_fwd(EE, ldee, Wg, bg, n, ldee, N, G, N, self._dropout(SITE_GATE), ws=st['gate_ws'],
+                         weights_staged=w_side is not None)
         heads = []
         if has_i:
             Wo, bo = self._W('out_ints')
@@ -897,42 +913,27 @@ class _HotPathModule(nn.Module):
         self._dw1_adam_applied = adam is not None
         work_i = has_i and ('dW2_i' in need or 'tail_i' in need)
         work_c = has_c and ('dW2_c' in need or 'tail_c' in need)
+        def head_args(head, H1, planes, **kw):
+            # (the workspaces stay referenced by the structs until this function returns: they hold raw pointers into them)
+            sel, rows = head.rows(n, R, Rp1)
+            ws = ops.new(ops.workspace_bytes(rows + (n if head.pooled else 0), head.segs.n, J) // 4, dtype=torch.float32, device=dev)
+            return ops.embed_bwd_args(X, D, sel, rows, J, head.segs, head.layer_weights(self, 1), H1, _ptr(dEE, head.col), ldee,
+                                      *head.grads(self), ws, drop(head.sites[0]), planes=planes, pieces=st.get('pieces_gather'),
+                                      adam=adam, **kw)
         if work_i:
-            mods, segs = self._mods_i, self._segs_i
-            ws_i = ops.new(ops.workspace_bytes(n, segs.n, J) // 4, dtype=torch.float32, device=dev)
-            args_i = ops.embed_bwd_args(X, D, (1, Rp1, 0), n, J, segs, [self._W(b)[0] for _, b in mods], st['H1_i'],
-                                        _ptr(dEE, Wc), ldee,
-                                        [self._g(a + '.weight') for a, _ in mods], [self._g(a + '.bias') for a, _ in mods],
-                                        [self._g(b + '.weight') for _, b in mods], [self._g(b + '.bias') for _, b in mods],
-                                        ws_i, drop(SITE_H1_INTS), planes=st.get('planes_i'), pieces=st.get('pieces_gather'), adam=adam)
+            args_i = head_args(self._head_i, st['H1_i'], st.get('planes_i'))
         if work_c:
             # context embed (pooled form): dW2/db2 and d(Hbar) on the n pooled rows, un-pool fused with the
             # relu/dropout backward, then dW1/db1 over the n*R context rows
-            mods, segs = self._mods_c, self._segs_c
-            # (ws_i and ws_c stay referenced until this function returns: the argument structs hold raw pointers into them)
-            ws_c = ops.new(ops.workspace_bytes(n * R + n, segs.n, J) // 4, dtype=torch.float32, device=dev)
-            args_c = ops.embed_bwd_args(X, D, (R, Rp1, 1), n * R, J, segs, [self._W(b)[0] for _, b in mods], st['H1_c'],
-                                        _ptr(dEE), ldee,
-                                        [self._g(a + '.weight') for a, _ in mods], [self._g(a + '.bias') for a, _ in mods],
-                                        [self._g(b + '.weight') for _, b in mods], [self._g(b + '.bias') for _, b in mods],
-                                        ws_c, drop(SITE_H1_CTX),
-                                        pool=(st['mask'], R, st['clamp'], st['Hbar'], st['fsc'], st['cmp']),
-                                        planes=st.get('planes_c'), hbits=st.get('hbits_c'), pieces=st.get('pieces_gather'), adam=adam)
+            args_c = head_args(self._head_c, st['H1_c'], st.get('planes_c'), hbits=st.get('hbits_c'),
+                               pool=(st['mask'], R, st['clamp'], st['Hbar'], st['fsc'], st['cmp']))
 
-        def run(parts, which=None):
-            """parts of the embed backward (include/lirec_hip.h: 1 second-layer weight gradients, 2 the rest, 3 hidden-layer
-            gradients only, 4 the tail -- un-pool and dW1 -- only); both heads share launches where a part covers both.  A head
-            whose parameters of that part are frozen (and whose input gradient nobody wants) is left out: the other one's call is
-            then the single-head lirec_embed_bwd"""
-            key = 'dW2_' if parts == 1 else 'tail_'
-            a_i = args_i if key + 'i' in need else None
-            a_c = args_c if key + 'c' in need else None
-            if which is None and a_i is not None and a_c is not None:
-                ops.embed_bwd2(ops.with_parts(a_i, parts), ops.with_parts(a_c, parts))
-            else:
-                for a in ((a_i, a_c) if which is None else (which,)):
-                    if a is not None:
-                        ops.embed_bwd(args=ops.with_parts(a, parts))
+        # The heads of each part of the embed backward (include/lirec_hip.h: 1 second-layer weight gradients, 2 the rest, 3
+        # hidden-layer gradients only, 4 the tail -- un-pool and dW1 -- only); both heads share launches where a part covers both
+        # (ops.embed_bwd_heads).  A head whose parameters of that part are frozen (and whose input gradient nobody wants) is left
+        # out: the other one's call is then the single-head lirec_embed_bwd.
+        heads_w2 = [args_i if 'dW2_i' in need else None, args_c if 'dW2_c' in need else None]
+        heads_tail = [args_i if 'tail_i' in need else None, args_c if 'tail_c' in need else None]
         # (the interaction head's dW1 on the side stream as well measured 2.5 % SLOWER: it competes with the context head's
         #  256x256 split-K launch for whole CUs)
         forked2 = False
@@ -942,12 +943,12 @@ class _HotPathModule(nn.Module):
             if lane2 is not None and (heads_w or 'gate_dW' in need):
                 ops.stream_wait(side_h, main)
         elif lane2 is not None:
-            on_side2(lambda: run(1))         # second-layer weight gradients beside the rest of the chain, on their own stream
+            on_side2(lambda: ops.embed_bwd_heads(heads_w2, 1))         # second-layer weight gradients beside the rest of the chain, on their own stream
             forked2 = True
         elif lane is not None:
-            on_side(lambda: run(1))
+            on_side(lambda: ops.embed_bwd_heads(heads_w2, 1))
         else:
-            run(1)
+            ops.embed_bwd_heads(heads_w2, 1)
         if self.grad_sync is not None:
             self.grad_sync.bucket_ready(1, also=side2_h if lane2 is not None else side_h)   # second layers of both embeddings: final here
         dClip = dTrack = None
@@ -956,7 +957,7 @@ class _HotPathModule(nn.Module):
         elif pieces is not None:
             # batch given as unique pieces + index: hidden-layer gradients as usual, the context head's un-pool pass, then
             # the first-layer weight gradients from the pieces (incidence matrix of the index, two small GEMM stages)
-            run(3)
+            ops.embed_bwd_heads(heads_tail, 3)
             ops.embed_bwd(args=ops.with_parts(args_c, 5))
             pc = ops.make_pieces(pieces['clip'], pieces['track'], pieces['index'], opt.text_dim, opt.visual_dim)
             nc1, nt1 = pieces['clip'].shape[0], pieces['track'].shape[0]
@@ -969,23 +970,23 @@ class _HotPathModule(nn.Module):
                 # with the weights the forward read -- like dX below, before the last bucket is announced
                 dClip = ops.new(pieces['clip'].shape, dtype=torch.float32, device=dev)
                 dTrack = ops.new(pieces['track'].shape, dtype=torch.float32, device=dev)
-                W1 = [[self._W(m1)[0] for m1, _ in mods] for mods in (self._mods_i, self._mods_c)]
+                W1 = [head.layer_weights(self, 0) for head in (self._head_i, self._head_c)]
                 ops.embed_dx_indexed([args_i, args_c], Ss, W1, pc, dClip, dTrack)
         else:
             # (data parallel or not: both heads' tails share their launches -- the first-layer weight gradients of the two
             #  heads are ONE persistent launch, so their bucket is announced once, at the end)
             with ops.adam_hyper_row(hyper_row if adam is not None else None), \
                     ops.adam_hyper_map(*(hyper_map if adam is not None and hyper_map is not None else (None,))):
-                run(2)
+                ops.embed_bwd_heads(heads_tail, 2)
         dX = None
         if want_dx:
             # dX = dZ1 W1 per (head, segment), on this stream right behind the tail that left dZ1 in the workspaces, with the weights
             # the forward read (nothing has updated them yet), and before the last bucket is announced -- a data-parallel update of
             # that bucket starts only after this launch
             dX = ops.new(X.shape, dtype=X.dtype, device=dev)
-            hs = [(a, mods) for a, mods in ((args_i, getattr(self, '_mods_i', None)), (args_c, getattr(self, '_mods_c', None)))
+            hs = [(a, head) for a, head in ((args_i, getattr(self, '_head_i', None)), (args_c, getattr(self, '_head_c', None)))
                   if a is not None]
-            ops.embed_dx([a for a, _ in hs], [[self._W(m1)[0] for m1, _ in mods] for _, mods in hs], dX)
+            ops.embed_dx([a for a, _ in hs], [head.layer_weights(self, 0) for _, head in hs], dX)
         join_side()
         if self.grad_sync is not None:
             self.grad_sync.bucket_ready(2)
@@ -1126,7 +1127,7 @@ class Modalities(_HotPathModule):
         self.dropout = nn.Dropout(p=opt.dropout)
         self._has_ints, self._has_ctx, self._has_gate = True, False, False
         self._flags = (ut, uv, uk)
-        self._mods_i, self._segs_i = self._segments('ints', ut, uv, uk)
+        self._describe_head('i', 'ints', ut, uv, uk)
         self._finish_init()
 
     def forward(self, x):
@@ -1164,10 +1165,10 @@ class _MidFusionBase(_HotPathModule):
         if self._has_gate and not (self._has_ints and self._has_ctx):
             raise ValueError('gates=1 needs ints=1 and ctx=1 (GatingUnit concatenates both embeddings, '
                              'mlp/model.py:352)')
-        if self._has_ints:
-            self._mods_i, self._segs_i = self._segments('ints')
         if self._has_ctx:
-            self._mods_c, self._segs_c = self._segments('ctx')
+            self._describe_head('c', 'ctx')
+        if self._has_ints:
+            self._describe_head('i', 'ints')
         self._finish_init()
 
 

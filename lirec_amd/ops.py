@@ -302,6 +302,18 @@ def embed_fwd_args(X, ldx, sel, rows, J, segs: Segments, W1, b1, W2, b2, H1, Z2,
     a.rows_staged = int(bool(rows_staged))
     if W1q is not None:       # the first-layer weights kept as q32b (addresses; lirec_embed_fwd_args::W1q)
         _fill(a.W1q, [int(w) for w in W1q])
+    _fill_head_common(a, X, ldx, sel, rows, J, segs, drop, pool, planes, pieces, hbits)
+    _fill(a.W1, [_p(w) for w in W1]); _fill(a.b1, [_p(w) for w in b1])
+    _fill(a.W2, [_p(w) for w in W2]); _fill(a.b2, [_p(w) for w in b2])
+    a.H1, a.Z2, a.ldz2 = _p(H1), Z2, ldz2
+    a.Tn, a.ldtn = Tn, ldtn
+    a.epilogue = epilogue
+    return a
+
+
+def _fill_head_common(a, X, ldx, sel, rows, J, segs, drop, pool, planes, pieces, hbits):
+    """what a head's forward and backward structs share: the feature block and its storage form, the row selector, the
+    segments, the dropout stream, and the optional pooled / compact tuple, planes workspace, piece tables and sign bits"""
     if hbits is not None:
         a.hbits = _p(hbits)
     if pieces is not None:
@@ -318,15 +330,10 @@ def embed_fwd_args(X, ldx, sel, rows, J, segs: Segments, W1, b1, W2, b2, H1, Z2,
     a.X, a.ldx = _p(X), ldx
     a.x_bf16 = int(X.dtype == torch.bfloat16)
     a.x_q32 = X.x_q32 if isinstance(X, Q32Block) else 0
-    _fill(a.W1, [_p(w) for w in W1]); _fill(a.b1, [_p(w) for w in b1])
-    _fill(a.W2, [_p(w) for w in W2]); _fill(a.b2, [_p(w) for w in b2])
-    a.H1, a.Z2, a.ldz2 = _p(H1), Z2, ldz2
-    a.Tn, a.ldtn = Tn, ldtn
     _fill(a.in_off, segs.in_off); _fill(a.in_dim, segs.in_dim); _fill(a.out_dim, segs.out_dim)
-    a.rows, a.nseg, a.J, a.epilogue = rows, segs.n, J, epilogue
+    a.rows, a.nseg, a.J = rows, segs.n, J
     a.sel = RowSel(*sel)
     a.drop = drop
-    return a
 
 
 def embed_fwd(*args, **kw):
@@ -339,6 +346,21 @@ def embed_fwd2(a, b):
     check(lib().lirec_embed_fwd2(C.byref(a), C.byref(b), _stream()), 'lirec_embed_fwd2')
 
 
+def embed_fwd_heads(heads, parts=None):
+    """The forward of one head (lirec_embed_fwd) or of two in one call (lirec_embed_fwd2): ``heads`` is a list of one or two
+    embed_fwd_args structs, None entries are dropped and an empty list is a no-op.  ``parts``: run ``with_parts`` copies."""
+    heads = [h if parts is None else with_parts(h, parts) for h in heads if h is not None]
+    if heads:
+        embed_fwd(args=heads[0]) if len(heads) == 1 else embed_fwd2(*heads)
+
+
+def embed_bwd_heads(heads, parts=None):
+    """The backward of one head (lirec_embed_bwd) or of two in one call (lirec_embed_bwd2); arguments as embed_fwd_heads."""
+    heads = [h if parts is None else with_parts(h, parts) for h in heads if h is not None]
+    if heads:
+        embed_bwd(args=heads[0]) if len(heads) == 1 else embed_bwd2(*heads)
+
+
 def embed_bwd_args(X, ldx, sel, rows, J, segs: Segments, W2, H1, dZ2, lddz2, dW1, db1, dW2, db2, workspace, drop,
                    pool=None, planes=None, parts=0, hbits=None, pieces=None, adam=None):
     """``H1`` may be None when ``hbits`` (the sign bits the forward call left) is given.  ``pieces``: the forward call's, when its
@@ -349,31 +371,12 @@ def embed_bwd_args(X, ldx, sel, rows, J, segs: Segments, W2, H1, dZ2, lddz2, dW1
     if adam is not None:
         a.adam = C.cast(C.pointer(adam), C.c_void_p)
         a._adam_ref = adam
-    if pieces is not None:
-        a.pieces = C.cast(C.pointer(pieces), C.c_void_p)
-        a._pieces_ref = pieces
-    if hbits is not None:
-        a.hbits = _p(hbits)
-    if planes is not None:
-        a.planes, a.planes_bytes = _p(planes), planes.numel() * planes.element_size()
-    if pool is not None:
-        mask, R, clamp, Hbar, fscale = pool[:5]
-        a.mask, a.R, a.clamp_zero, a.Hbar, a.fscale = _p(mask), R, int(clamp), _p(Hbar), _p(fscale)
-        if len(pool) > 5 and pool[5] is not None:          # compact form: (rowmap, cstart, count[, wts])
-            a.rowmap, a.cstart, a.count = (_p(t) for t in pool[5][:3])
-            a.wts = _p(pool[5][3]) if len(pool[5]) > 3 else None
-    a.X, a.ldx = _p(X), ldx
-    a.x_bf16 = int(X.dtype == torch.bfloat16)
-    a.x_q32 = X.x_q32 if isinstance(X, Q32Block) else 0
+    _fill_head_common(a, X, ldx, sel, rows, J, segs, drop, pool, planes, pieces, hbits)
     _fill(a.W2, [_p(w) for w in W2])
     a.H1, a.dZ2, a.lddz2 = (_p(H1) if H1 is not None else None), dZ2, lddz2
     _fill(a.dW1, [_p(w) for w in dW1]); _fill(a.db1, [_p(w) for w in db1])
     _fill(a.dW2, [_p(w) for w in dW2]); _fill(a.db2, [_p(w) for w in db2])
     a.workspace, a.workspace_bytes = _p(workspace), workspace.numel() * workspace.element_size()
-    _fill(a.in_off, segs.in_off); _fill(a.in_dim, segs.in_dim); _fill(a.out_dim, segs.out_dim)
-    a.rows, a.nseg, a.J = rows, segs.n, J
-    a.sel = RowSel(*sel)
-    a.drop = drop
     # the struct only holds raw pointers: keep what it points into alive for as long as the struct (or a with_parts copy) is
     a._refs = (X, H1, workspace, planes, pool, hbits)
     return a
