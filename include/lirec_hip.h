@@ -531,6 +531,36 @@ typedef struct {
 } lirec_margin_loss_args;
 int lirec_margin_loss(const lirec_margin_loss_args* a, lirec_stream_t stream);
 
+/* Per-clip weights and per-clip loss values of the fused losses (added to ABI 124 without a new number: three new exports and a
+ * new struct, index 19 of lirec_abi_sizeof; 18 stays unassigned).  With li_b / lr_b the interaction and relationship terms of
+ * clip b as the kernels compute them before the batch means' coefficients, and weights w_b >= 0, finite:
+ *     loss = lymbda * sum_b w_b li_b / D_i  +  sum_b w_b lr_b / D_r
+ * and the gradients are exactly its derivative (the coefficients become per-clip, the positive element's term included).
+ *   norm 0 ('sum'):   a weighted mean, the convention of F.cross_entropy(weight=): D_i = sum_b w_b; D_r = the sum of w_b over the
+ *                     clips whose label != NR for the two multitask clip losses (rels_mean_valid; the CE loss's relationship
+ *                     half), sum_b w_b otherwise.  In lirec_ce_loss the clip weight multiplies the class weight:
+ *                     scale_b = w_b cw[y_b] / sum_b w_b cw[y_b].
+ *   norm 1 ('count'): the denominators stay the counts (B, the labelled clips); the weights are plain multipliers.
+ * A denominator of 0 (every weight 0; no labelled clip) gives loss 0 and all-zero gradients for that half, never NaN.  Weights
+ * all 1.0 give, under either norm, the bits of the unweighted call.  Every workgroup forms the sums itself in one fixed order:
+ * no extra launch, deterministic.  The weights are read as given: a negative or non-finite weight is the caller's to refuse.
+ * The data-parallel denominators (batch_divisor / rels_divisor / divisors_dev; den_ints / den_rels / dens_dev) keep their
+ * meaning, "the global denominators over world": with norm 0 those are the global weight sums.
+ * A NULL struct, or one whose `w` is NULL, issues the launches and gives the bits of the unweighted call; with only `clip_loss`
+ * set it is the unweighted loss that also reports the per-clip values.  LIREC_EINVAL before any device call: `w` and `clip_loss`
+ * both NULL; norm outside {0, 1}; `w` not aligned to its type (8 / 4 bytes); `clip_loss` not aligned to 4 bytes; sample == 2
+ * (probabilities only) with a struct.  The LDS need is that of the unweighted call. */
+typedef struct {
+  const void* w;        /* [B] clip weights, or NULL = all ones */
+  int32_t w_f64;        /* 1: w is float64 (the loader's dtype), 0: float32 */
+  int32_t norm;         /* 0 'sum', 1 'count' */
+  float* clip_loss;     /* [B, 2] out, optional: (lymbda * li_b, lr_b) UNWEIGHTED and UNDIVIDED, so that
+                           sum_b w_b (clip_loss[b,0] / D_i + clip_loss[b,1] / D_r) = loss; column 1 is 0 where the clip has no
+                           relationship term.  lirec_ce_loss: (cw[y_b] * CE_b of the interaction row, CE_b of the relationship row) */
+} lirec_clip_weights;
+/* lirec_margin_loss with clip weights; lirec_margin_loss(a, s) is lirec_margin_loss_weighted(a, NULL, s) */
+int lirec_margin_loss_weighted(const lirec_margin_loss_args* a, const lirec_clip_weights* cw, lirec_stream_t stream);
+
 /* SURVEY 8(b)'s K5 boundary call: the output heads, the loss and the heads' data gradient as ONE library call --
  *   out_ints / out_ctx (mlp/model.py:332-336, :205-209)   heads[0..n_heads): Y = A W^T + b          (one grouped launch)
  *   the max-margin loss on those logits (:381-575)         loss: fused forward + d(loss)/d(logits)   (one launch)
@@ -543,6 +573,10 @@ int lirec_margin_loss(const lirec_margin_loss_args* a, lirec_stream_t stream);
  * the heads only. */
 int lirec_heads_loss_fwd_bwd(const lirec_linear_fwd_args* heads, const lirec_linear_bwd_args* back, int32_t n_heads,
                              const lirec_margin_loss_args* loss, lirec_stream_t stream);
+/* The same boundary call with clip weights on its loss (lirec_clip_weights; NULL: the call above).  NULL `loss` with a struct:
+ * LIREC_EINVAL. */
+int lirec_heads_loss_fwd_bwd_weighted(const lirec_linear_fwd_args* heads, const lirec_linear_bwd_args* back, int32_t n_heads,
+                                      const lirec_margin_loss_args* loss, const lirec_clip_weights* cw, lirec_stream_t stream);
 
 /* MultiTaskCrossEntropyLoss.forward (mlp/model.py:367-378): mean CE over `ints` rows plus
  * mean CE over the `rels` rows whose label != NR.  class_w ([C]) may be NULL.
@@ -554,6 +588,15 @@ int lirec_ce_loss(const float* ints, int64_t ld_ints, const float* rels, int64_t
                   int32_t B, int32_t C, int32_t NR, float* d_ints, int64_t ld_dints,
                   float* d_rels, int64_t ld_drels, float* loss, float* partial,
                   float den_ints, float den_rels, const float* dens_dev, lirec_stream_t stream);
+/* The same with clip weights (lirec_clip_weights; NULL: the call above).  Norm 0: the interaction denominator is
+ * sum_b w_b cw[y_b], the relationship denominator the sum of w_b over the labelled rows; den_ints / den_rels / dens_dev, when
+ * given, are those sums of the global batch over world. */
+int lirec_ce_loss_weighted(const float* ints, int64_t ld_ints, const float* rels, int64_t ld_rels,
+                           const int32_t* y, const int32_t* r, const float* class_w,
+                           int32_t B, int32_t C, int32_t NR, float* d_ints, int64_t ld_dints,
+                           float* d_rels, int64_t ld_drels, float* loss, float* partial,
+                           float den_ints, float den_rels, const float* dens_dev, const lirec_clip_weights* cw,
+                           lirec_stream_t stream);
 
 /* ---- optimiser --------------------------------------------------------------
  * torch.optim.Adam(lr, weight_decay) as configured at mlp/model.py:599-601, fused over
@@ -958,7 +1001,8 @@ int lirec_dropout_mask(uint8_t* keep, int32_t rows, int32_t cols, const lirec_dr
 int lirec_version(void);
 /* sizeof() of ABI struct `which` (5 = eval; 0 embed_fwd, 1 embed_bwd, 2 margin_loss, 3 dropout,
  * 4 rowsel, 6 linear_fwd, 7 linear_bwd, 8 embed_dx, 9 embed_dx_indexed, 10 adam_range, 11 adam_hyper, 12 adam_group_range,
- * 13 eval_topk, 15 predict, 17 collate; 14 and 16 are not assigned) so a binding can verify its mirror; -1 if unknown */
+ * 13 eval_topk, 15 predict, 17 collate, 19 clip_weights; 14, 16 and 18 are not assigned) so a binding can verify its mirror;
+ * -1 if unknown */
 int lirec_abi_sizeof(int which);
 /* GEMM core: 0 exact f32-input MFMA   1 one-thread-per-output HIP GEMM (bring-up cross-check)
  *            2 split-precision bf16x3 MFMA (fp32 in/out, ~2^-16 per product, up to 5.3x the f32 core)

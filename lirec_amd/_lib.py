@@ -85,6 +85,14 @@ class MarginLossArgs(C.Structure):
                 ('batch_divisor', _f32), ('rels_divisor', _f32), ('divisors_dev', _vp), ('y_stride', _i32), ('reserved_', _i32)]
 
 
+class ClipWeights(C.Structure):
+    """lirec_clip_weights: per-clip weights and per-clip loss values of the fused losses"""
+    _fields_ = [('w', _vp), ('w_f64', _i32), ('norm', _i32), ('clip_loss', _vp)]
+
+
+CLIP_WEIGHT_NORMS = {'sum': 0, 'count': 1}
+
+
 class Pieces(C.Structure):
     """lirec_pieces: the de-duplicated piece tables and the index of a batch (lirec_amd/features.py)."""
     _fields_ = [('clip', _vp), ('ld_clip', _i64), ('n_clip', _i32), ('track', _vp), ('ld_track', _i64), ('n_track', _i32),
@@ -242,6 +250,11 @@ _PROTOS = {
     'lirec_margin_loss': (_i32, [C.POINTER(MarginLossArgs), _vp]),
     'lirec_heads_loss_fwd_bwd': (_i32, [C.POINTER(LinearFwdArgs), C.POINTER(LinearBwdArgs), _i32, C.POINTER(MarginLossArgs), _vp]),
     'lirec_ce_loss': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _f32, _f32, _vp, _vp]),
+    'lirec_margin_loss_weighted': (_i32, [C.POINTER(MarginLossArgs), C.POINTER(ClipWeights), _vp]),
+    'lirec_heads_loss_fwd_bwd_weighted': (_i32, [C.POINTER(LinearFwdArgs), C.POINTER(LinearBwdArgs), _i32, C.POINTER(MarginLossArgs),
+                                                 C.POINTER(ClipWeights), _vp]),
+    'lirec_ce_loss_weighted': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _f32, _f32,
+                                      _vp, C.POINTER(ClipWeights), _vp]),
     'lirec_adam_step': (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _vp]),
     'lirec_adam_step_counted': (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _i32, _vp]),
     'lirec_adam_step_ranges': (_i32, [_vp, _vp, _vp, _vp, C.POINTER(AdamRange), _i32, _i32, _f32, _f32, _f32, _f32, _f32, _f32,
@@ -312,7 +325,8 @@ def lib():
                                                                                                       (9, EmbedDxIndexedArgs),
                                                                                                       (10, AdamRange), (11, AdamHyper),
                                                                                                       (12, AdamGroupRange), (13, EvalTopkArgs),
-                                                                                                      (15, PredictArgs), (17, CollateArgs)]:
+                                                                                                      (15, PredictArgs), (17, CollateArgs),
+                                                                                                      (19, ClipWeights)]:
         if L.lirec_abi_sizeof(which) != C.sizeof(st):
             raise LirecError('ABI mismatch for %s: library %d bytes, binding %d bytes'
                              % (st.__name__, L.lirec_abi_sizeof(which), C.sizeof(st)))

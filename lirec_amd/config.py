@@ -79,6 +79,10 @@ def defaults() -> dict:
         skip_nonfinite=False,          # FusedAdam: a step whose trainable gradients hold a NaN / Inf is skipped, on the device (parameters, moments and the bias corrections' step untouched)
         ema_decay=0.0,                 # in (0.5, 1): FusedAdam keeps an exponential moving average of the weights, updated on the device behind every applied step (0: off)
         eval_ema=False,                # training(): the val / test evaluations run on the averaged weights (optimizer.ema_weights()); mode='train' stays on the live ones
+        # per-clip loss weights (batch['clip_weight'], read by all five losses inside the loss kernel): 'sum' divides by the weight
+        # sums (a weighted mean, as F.cross_entropy(weight=)), 'count' keeps the counts and the weights are plain multipliers
+        clip_weight_norm='sum',
+        class_balance='',              # '' | 'inverse' | 'effective': training() weights every clip by its interaction class's frequency in the train set (lirec_amd.data.class_balanced_weights)
         clip_grad_norm=0.0,            # > 0: FusedAdam clips the gradients to this global L2 norm, on the device, inside the update (max_grad_norm)
         gate_stage_on_side=True,       # ... with the weights staged on the side stream beside layer 1
         gate_q32=True,                 # training: the gate's forward / data gradient on staged q32b operands (lirec_gate_fwd_ws)

@@ -1254,7 +1254,10 @@ __device__ __forceinline__ int ld_i(const int32_t* p, long i, bool i64) {
   return i64 ? (int)reinterpret_cast<const long long*>(p)[i] : p[i];
 }
 
-__global__ __launch_bounds__(256) void margin_loss_kernel(const lirec_margin_loss_args a) {
+// `cw` (lirec_clip_weights by value, all zero for the unweighted calls): per-clip weights and the per-clip loss values.  Every
+// workgroup forms the weight sums itself -- one strided loop over the B weights and a block_sum, the same order everywhere, as
+// nvalid -- and a weight of 1.0 leaves every product what it was, so unit weights are the unweighted bits.
+__global__ __launch_bounds__(256) void margin_loss_kernel(const lirec_margin_loss_args a, const lirec_clip_weights cw) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   const int T = a.T, C = a.C, NR = a.NR;
@@ -1409,18 +1412,37 @@ __global__ __launch_bounds__(256) void margin_loss_kernel(const lirec_margin_los
     for (int i = tid; i < a.B; i += nt) cnt += (ld_i(a.r, (long)i * T, lt) != NR) ? 1.f : 0.f;
     nvalid = (int)(block_sum(cnt, red) + 0.5f);
   }
+  // this batch's own denominators: the counts, or -- clip weights with norm 'sum' -- the weight sums (all clips; labelled clips)
+  float den_b = (float)a.B, den_r = (float)nvalid, wb = 1.f;
+  if (cw.w) {
+    const float* wp = reinterpret_cast<const float*>(cw.w);
+    const bool wf64 = cw.w_f64 != 0;
+    if (cw.norm == 0) {
+      float sw = 0.f, swr = 0.f;
+      for (int i = tid; i < a.B; i += nt) {
+        const float wi = ld_f(wp, i, wf64);
+        sw += wi;
+        if (has_rels && a.rels_mean_valid && ld_i(a.r, (long)i * T, lt) != NR) swr += wi;
+      }
+      den_b = block_sum(sw, red);
+      if (has_rels && a.rels_mean_valid) den_r = block_sum(swr, red);
+    }
+    wb = ld_f(wp, b, wf64);
+  }
   __syncthreads();
   const int k = ish[0];
   const float pos = S[k * C + y];
   const float posr = has_rels ? Q[k * NR1 + r0] : 0.f;
   // denominators of the batch means: this batch's own (the reference, single device), or the data-parallel caller's
-  // (lirec_margin_loss_args::batch_divisor: the global batch's, divided by world)
+  // (lirec_margin_loss_args::batch_divisor: the global batch's, divided by world).  A denominator of 0 (every weight 0; no
+  // labelled clip): that half of the loss and its gradients are 0, not NaN.
   float div_b = a.divisors_dev ? a.divisors_dev[0] : a.batch_divisor;
   float div_r = a.divisors_dev ? a.divisors_dev[1] : a.rels_divisor;
-  if (!(div_b > 0.f)) div_b = (float)a.B;
-  if (!(div_r > 0.f)) div_r = (float)nvalid;
-  const float coef_i = a.lymbda / div_b;
-  const float coef_r = has_rels ? (a.rels_mean_valid ? (nvalid > 0 ? 1.f / div_r : 0.f) : 1.f / div_b) : 0.f;
+  if (!(div_b > 0.f)) div_b = den_b;
+  if (!(div_r > 0.f)) div_r = den_r;
+  const float inv_b = den_b > 0.f ? 1.f / div_b : 0.f;
+  const float coef_i = (den_b > 0.f ? a.lymbda / div_b : 0.f) * wb;
+  const float coef_r = (has_rels ? (a.rels_mean_valid ? (den_r > 0.f ? 1.f / div_r : 0.f) : inv_b) : 0.f) * wb;
   const float m = a.margin;
 
   float li = 0.f, ci = 0.f, lr = 0.f, cr = 0.f;
@@ -1512,6 +1534,10 @@ __global__ __launch_bounds__(256) void margin_loss_kernel(const lirec_margin_los
     // d(loss)/d(pos): every active hinge term carries -1
     a.d_ints[((long)b * T + k) * a.ld_dints + y] += -ci * coef_i * pos * (1.f - pos);
     if (has_rels && r0 < NR) a.d_rels[((long)b * T + k) * a.ld_drels + r0] += -cr * coef_r * posr * (1.f - posr);
+    if (cw.clip_loss) {                                            // unweighted, undivided: (lymbda * li_b, lr_b)
+      cw.clip_loss[2 * b] = a.lymbda * li;
+      cw.clip_loss[2 * b + 1] = lr;
+    }
     if (!a.arrive) {
       a.partial[2 * b] = li * coef_i;
       a.partial[2 * b + 1] = lr * coef_r;
@@ -1561,7 +1587,7 @@ __global__ __launch_bounds__(256) void ce_loss_kernel(const float* __restrict__ 
                                                       float* __restrict__ d_ints, long ld_dints,
                                                       float* __restrict__ d_rels, long ld_drels,
                                                       float* __restrict__ partial, float den_ints, float den_rels,
-                                                      const float* __restrict__ dens_dev) {
+                                                      const float* __restrict__ dens_dev, const lirec_clip_weights cw) {
   __shared__ float red[16];
   const int tid = threadIdx.x, nt = blockDim.x;
   const bool is_rel = blockIdx.x >= B;
@@ -1571,8 +1597,12 @@ __global__ __launch_bounds__(256) void ce_loss_kernel(const float* __restrict__ 
   const int n = is_rel ? NR : C;
   const int tgt = is_rel ? r[row] : y[row];
   // denominators: sum of class weights of the targets (ints), count of labelled rows (rels)
+  // (clip weights, norm 'sum': each term times its clip's weight -- the clip weight multiplies the class weight)
+  const float* wp = reinterpret_cast<const float*>(cw.w);
+  const bool wf64 = cw.w_f64 != 0, wsum = wp && cw.norm == 0;
   float den = 0.f;
-  for (int i = tid; i < B; i += nt) den += is_rel ? ((r[i] != NR) ? 1.f : 0.f) : (class_w ? class_w[y[i]] : 1.f);
+  for (int i = tid; i < B; i += nt)
+    den += (is_rel ? ((r[i] != NR) ? 1.f : 0.f) : (class_w ? class_w[y[i]] : 1.f)) * (wsum ? ld_f(wp, i, wf64) : 1.f);
   den = block_sum(den, red);
   {   // the data-parallel caller's denominators (lirec_ce_loss: den_ints / den_rels / dens_dev), when given
     const float given = dens_dev ? dens_dev[is_rel ? 1 : 0] : (is_rel ? den_rels : den_ints);
@@ -1580,7 +1610,10 @@ __global__ __launch_bounds__(256) void ce_loss_kernel(const float* __restrict__ 
   }
   if (is_rel && tgt == NR) {
     for (int c = tid; c < n; c += nt) dx[c] = 0.f;
-    if (tid == 0) partial[blockIdx.x] = 0.f;
+    if (tid == 0) {
+      partial[blockIdx.x] = 0.f;
+      if (cw.clip_loss) cw.clip_loss[2 * row + 1] = 0.f;
+    }
     return;
   }
   float mx = -__builtin_inff();
@@ -1596,9 +1629,16 @@ __global__ __launch_bounds__(256) void ce_loss_kernel(const float* __restrict__ 
   se = block_sum(se, red);
   const float lse = mx + logf(se);
   const float wt = (!is_rel && class_w) ? class_w[tgt] : 1.f;
-  const float scale = wt / den;
+  // (a denominator of 0 -- every weight 0 -- gives loss 0 and zero gradients for that half, not NaN)
+  const float scale = (den > 0.f ? wt / den : 0.f) * (wp ? ld_f(wp, row, wf64) : 1.f);
   for (int c = tid; c < n; c += nt) dx[c] = scale * (expf(x[c] - lse) - (c == tgt ? 1.f : 0.f));
-  if (tid == 0) partial[blockIdx.x] = scale * (lse - x[tgt]);
+  if (tid == 0) {
+    partial[blockIdx.x] = scale * (lse - x[tgt]);
+    if (cw.clip_loss) {                                            // unweighted by the clip, undivided
+      cw.clip_loss[2 * row + (is_rel ? 1 : 0)] = wt * (lse - x[tgt]);
+      if (!rels) cw.clip_loss[2 * row + 1] = 0.f;
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------

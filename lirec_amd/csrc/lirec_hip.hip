@@ -1138,6 +1138,7 @@ int lirec_abi_sizeof(int which) {
     case 13: return (int)sizeof(lirec_eval_topk_args);
     case 15: return (int)sizeof(lirec_predict_args);         // (14 stays unassigned)
     case 17: return (int)sizeof(lirec_collate_args);         // (16 stays unassigned)
+    case 19: return (int)sizeof(lirec_clip_weights);         // (18 stays unassigned)
     default: return -1;
   }
 }
@@ -2441,7 +2442,22 @@ int lirec_linear_bwd(const float* dY, int64_t lddy, const float* A, int64_t lda,
 }
 
 // ---------------------------------------------------------------------------
+// A lirec_clip_weights as the caller may give it (include/lirec_hip.h); NULL is the unweighted call.
+static bool clip_weights_ok(const lirec_clip_weights* cw) {
+  if (!cw) return true;
+  if (!cw->w && !cw->clip_loss) return false;
+  if (cw->norm < 0 || cw->norm > 1) return false;
+  if ((uintptr_t)cw->w % (cw->w_f64 ? 8 : 4) != 0) return false;
+  return (uintptr_t)cw->clip_loss % 4 == 0;
+}
+static const lirec_clip_weights NO_CLIP_WEIGHTS = {nullptr, 0, 0, nullptr};
+
 int lirec_margin_loss(const lirec_margin_loss_args* a, lirec_stream_t stream) {
+  return lirec_margin_loss_weighted(a, nullptr, stream);
+}
+
+int lirec_margin_loss_weighted(const lirec_margin_loss_args* a, const lirec_clip_weights* cw, lirec_stream_t stream) {
+  if (!clip_weights_ok(cw) || (cw && a && a->sample == 2)) return LIREC_EINVAL;
   if (!a || !a->ints || !a->y || a->B < 1 || a->T < 1 || a->C < 1 || a->sample < 0 || a->sample > 2) return LIREC_EINVAL;
   const bool probs_only = a->sample == 2;
   if (probs_only ? !(a->probs_out || a->sel_out) : (!a->d_ints || !a->loss || !a->partial)) return LIREC_EINVAL;
@@ -2454,7 +2470,7 @@ int lirec_margin_loss(const lirec_margin_loss_args* a, lirec_stream_t stream) {
   const size_t shm = ((size_t)a->T * a->C + (size_t)a->T * NR1 + 16 + 4 + 2 * (size_t)a->T + a->C) * sizeof(float);
   if (shm > 160 * 1024) return LIREC_EINVAL;
   const int pi = prof_start(PS_LOSS, s);
-  lirec::launch(margin_loss_kernel, dim3(a->B), dim3(256), shm, s, *a);
+  lirec::launch(margin_loss_kernel, dim3(a->B), dim3(256), shm, s, *a, cw ? *cw : NO_CLIP_WEIGHTS);
   if (!probs_only && !a->arrive) {
     LIREC_CHECK_LAUNCH();
     lirec::launch(loss_finalize_kernel, dim3(1), dim3(256), 0, s, (const float*)a->partial, 2 * a->B, a->loss);
@@ -2466,6 +2482,12 @@ int lirec_margin_loss(const lirec_margin_loss_args* a, lirec_stream_t stream) {
 
 int lirec_heads_loss_fwd_bwd(const lirec_linear_fwd_args* heads, const lirec_linear_bwd_args* back, int32_t n_heads,
                              const lirec_margin_loss_args* loss, lirec_stream_t stream) {
+  return lirec_heads_loss_fwd_bwd_weighted(heads, back, n_heads, loss, nullptr, stream);
+}
+
+int lirec_heads_loss_fwd_bwd_weighted(const lirec_linear_fwd_args* heads, const lirec_linear_bwd_args* back, int32_t n_heads,
+                                      const lirec_margin_loss_args* loss, const lirec_clip_weights* cw, lirec_stream_t stream) {
+  if (!clip_weights_ok(cw) || (cw && (!loss || loss->sample == 2))) return LIREC_EINVAL;
   if (!heads || n_heads < 1 || n_heads > LIREC_MAX_PROB || (loss && !back)) return LIREC_EINVAL;
   int rc = lirec_linear_fwd_group(heads, n_heads, stream);
   if (rc || !loss) return rc;
@@ -2473,7 +2495,7 @@ int lirec_heads_loss_fwd_bwd(const lirec_linear_fwd_args* heads, const lirec_lin
   bool ints_ok = false;
   for (int h = 0; h < n_heads; ++h) ints_ok = ints_ok || heads[h].Y == loss->ints;
   if (!ints_ok) return LIREC_EINVAL;
-  rc = lirec_margin_loss(loss, stream);
+  rc = lirec_margin_loss_weighted(loss, cw, stream);
   if (rc) return rc;
   lirec_linear_bwd_args b[LIREC_MAX_PROB];
   for (int h = 0; h < n_heads; ++h) { b[h] = back[h]; b[h].parts = 2; }
@@ -2485,12 +2507,24 @@ int lirec_ce_loss(const float* ints, int64_t ld_ints, const float* rels, int64_t
                   int32_t B, int32_t C, int32_t NR, float* d_ints, int64_t ld_dints,
                   float* d_rels, int64_t ld_drels, float* loss, float* partial,
                   float den_ints, float den_rels, const float* dens_dev, lirec_stream_t stream) {
+  return lirec_ce_loss_weighted(ints, ld_ints, rels, ld_rels, y, r, class_w, B, C, NR, d_ints, ld_dints, d_rels, ld_drels, loss,
+                                partial, den_ints, den_rels, dens_dev, nullptr, stream);
+}
+
+int lirec_ce_loss_weighted(const float* ints, int64_t ld_ints, const float* rels, int64_t ld_rels,
+                           const int32_t* y, const int32_t* r, const float* class_w,
+                           int32_t B, int32_t C, int32_t NR, float* d_ints, int64_t ld_dints,
+                           float* d_rels, int64_t ld_drels, float* loss, float* partial,
+                           float den_ints, float den_rels, const float* dens_dev, const lirec_clip_weights* cw,
+                           lirec_stream_t stream) {
+  if (!clip_weights_ok(cw)) return LIREC_EINVAL;
   if (!ints || !y || !d_ints || !loss || !partial || B < 1 || C < 1 || den_ints < 0.f || den_rels < 0.f) return LIREC_EINVAL;
   if (rels && (!r || !d_rels || NR < 1)) return LIREC_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const int nblk = rels ? 2 * B : B;
   lirec::launch(ce_loss_kernel, dim3(nblk), dim3(256), 0, s, ints, (long)ld_ints, rels, (long)ld_rels, y, r,
-                     class_w, B, C, NR, d_ints, (long)ld_dints, d_rels, (long)ld_drels, partial, den_ints, den_rels, dens_dev);
+                     class_w, B, C, NR, d_ints, (long)ld_dints, d_rels, (long)ld_drels, partial, den_ints, den_rels, dens_dev,
+                     cw ? *cw : NO_CLIP_WEIGHTS);
   LIREC_CHECK_LAUNCH();
   lirec::launch(loss_finalize_kernel, dim3(1), dim3(256), 0, s, (const float*)partial, nblk, loss);
   LIREC_CHECK_LAUNCH();

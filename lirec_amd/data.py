@@ -148,3 +148,85 @@ def to_device_batch(batch: dict, device, feature_dtype=torch.float32) -> dict:
         else:
             out[k] = v.to(device=device, non_blocking=True)
     return out
+
+
+# ---------------------------------------------------------------------------
+# per-clip loss weights (batch['clip_weight'], read by the loss kernels: include/lirec_hip.h, lirec_clip_weights)
+# ---------------------------------------------------------------------------
+
+def class_balanced_weights(labels, n_classes: int, how: str = 'inverse', beta: float = 0.999) -> np.ndarray:
+    """One weight per sample from the frequency of its class (numpy, on the host): float64 ``[n]``, normalised to mean 1.
+    ``how='inverse'``: 1 / n_c, the count of the sample's class; ``'effective'``: (1 - beta) / (1 - beta ** n_c), the inverse of
+    the effective number of samples (Cui et al., "Class-Balanced Loss Based on Effective Number of Samples", CVPR 2019).  A class
+    without samples carries no weight and takes no part."""
+    if how not in ('inverse', 'effective'):
+        raise ValueError("class_balanced_weights: how must be 'inverse' or 'effective', not %r" % (how,))
+    y = np.asarray(labels).reshape(-1).astype(np.int64)
+    if y.size == 0:
+        return np.zeros(0, dtype=np.float64)
+    if int(y.min()) < 0 or int(y.max()) >= int(n_classes):
+        raise ValueError('class_balanced_weights: a label outside [0, %d)' % int(n_classes))
+    counts = np.bincount(y, minlength=int(n_classes)).astype(np.float64)
+    per_class = np.zeros(int(n_classes), dtype=np.float64)
+    seen = counts > 0
+    if how == 'inverse':
+        per_class[seen] = 1.0 / counts[seen]
+    else:
+        if not 0.0 <= beta < 1.0:
+            raise ValueError('class_balanced_weights: beta must lie in [0, 1)')
+        per_class[seen] = (1.0 - beta) / (1.0 - np.power(beta, counts[seen]))
+    w = per_class[y]
+    return w / w.mean()
+
+
+class WeightedDataset(Dataset):
+    """A map-style dataset whose samples (dicts) carry ``clip_weight`` (float64): ``weights[i]`` for sample ``i``; default-collated
+    to the ``[B]`` float64 tensor the losses read.  The weights are checked once, here: finite and non-negative.  Attributes of
+    the wrapped dataset (``n_classes``, ``n_rels``, ...) read through; ``epoch`` is passed on.  (A ``PiecesDataset`` takes its
+    weights itself -- ``PiecesDataset(..., clip_weight=)`` -- since its batches are built by its own ``collate_fn``.)"""
+    carries_clip_weights = True
+
+    def __init__(self, dataset, weights):
+        from .features import checked_clip_weights
+        self.dataset = dataset
+        self.weights = checked_clip_weights(weights, len(dataset))
+
+    def __len__(self):
+        return len(self.dataset)
+
+    def __getitem__(self, idx):
+        out = dict(self.dataset[idx])
+        out['clip_weight'] = np.float64(self.weights[idx])
+        return out
+
+    def __getattr__(self, name):                 # (only reached for what the wrapper itself does not have)
+        if name in ('dataset', 'weights'):
+            raise AttributeError(name)
+        return getattr(self.dataset, name)
+
+    @property
+    def epoch(self):
+        return getattr(self.dataset, 'epoch', 0)
+
+    @epoch.setter
+    def epoch(self, value):
+        self.dataset.epoch = value
+
+
+def interaction_labels(dataset) -> np.ndarray:
+    """the interaction label of every sample of a map-style dataset (``labels`` of the sample; the clip's own, entry 0, where a
+    sample carries its context clips' labels too)"""
+    stacked = getattr(dataset, '_stacked', None)
+    if stacked is not None and 'labels' in stacked:
+        lab = np.asarray(stacked['labels'])
+        return lab.reshape(lab.shape[0], -1)[:, 0].astype(np.int64)
+    return np.array([int(np.asarray(dataset[i]['labels']).reshape(-1)[0]) for i in range(len(dataset))], dtype=np.int64)
+
+
+def with_clip_weights(dataset, weights):
+    """``dataset`` carrying ``weights``: a dataset that can hold them itself (``set_clip_weights``: PiecesDataset) is given them and
+    returned, anything else is wrapped in a ``WeightedDataset``."""
+    if hasattr(dataset, 'set_clip_weights'):
+        dataset.set_clip_weights(weights)
+        return dataset
+    return WeightedDataset(dataset, weights)

@@ -73,9 +73,13 @@ class ThreadedLoader:
 def device_collate_in_force(dataset, device=None) -> bool:
     """``opt.device_collate`` asks for ``ResidentLoader``; it is used when the dataset keeps its pieces in a resident store, the
     device is a GPU and the gathered q32b path is in force (what a recorded train step asks for, lirec_amd.train._recordable).
-    Anything else keeps ``ThreadedLoader``."""
+    Anything else keeps ``ThreadedLoader`` -- a dataset that carries per-clip loss weights too: ``lirec_collate_resident`` gathers
+    the nine fields, not the weights."""
     from .config import opt
+    from .features import CLIP_WEIGHT
     device = opt.device if device is None else device
+    if CLIP_WEIGHT in (getattr(dataset, '_stacked', None) or ()) or getattr(dataset, 'carries_clip_weights', False):
+        return False
     return bool(getattr(opt, 'device_collate', False)) and getattr(dataset, 'store', None) is not None and \
         getattr(dataset, 'emit', None) == 'pieces' and hasattr(dataset, 'device_tables') and str(device).startswith('cuda') and \
         bool(getattr(opt, 'pieces_gather', True)) and bool(getattr(opt, 'pieces_q32b', False)) and bool(getattr(opt, 'layer1_planes', False))

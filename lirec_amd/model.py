@@ -1363,9 +1363,49 @@ class _DPMeans:
         """this rank's denominators as a list of 0-d tensors / numbers: [clips, labelled rows]"""
         raise NotImplementedError
 
+    # Per-clip weights (DESIGN 4.o): ``batch['clip_weight']`` ([B], float64 or float32) weights every clip's terms inside the loss
+    # kernel; ``opt.clip_weight_norm`` ('sum' | 'count') selects the denominators.  A HOST tensor is checked for finite,
+    # non-negative values; a DEVICE tensor is taken as given (checking it would be a synchronisation in every step).
+    # ``keep_clip_losses = True``: every call leaves ``last_clip_losses`` (device [B, 2]: lymbda * li_b, lr_b, unweighted).
+    keep_clip_losses = False
+    last_clip_losses = None
+    _cw = None                    # the clip weights of the last call, as the kernel read them
+
+    def _clip_weight(self, args, B, dev):
+        w = args.get('clip_weight') if hasattr(args, 'get') else None
+        if w is None:
+            self._cw = None
+            return None
+        w = w if torch.is_tensor(w) else torch.as_tensor(w)
+        if w.numel() != B:
+            raise LirecError("batch['clip_weight'] holds %d weights for %d clips" % (w.numel(), B))
+        if w.device.type == 'cpu' and not bool((torch.isfinite(w) & (w >= 0)).all()):
+            raise LirecError("batch['clip_weight'] must be finite and non-negative")
+        self._cw = _dev_tensor(w.reshape(-1), dev, torch.float64 if w.dtype == torch.float64 else torch.float32)
+        return self._cw
+
+    def _clip_norm(self):
+        norm = getattr(opt, 'clip_weight_norm', 'sum') or 'sum'
+        if norm not in ('sum', 'count'):
+            raise LirecError("opt.clip_weight_norm must be 'sum' or 'count', not %r" % (norm,))
+        return norm
+
+    def _clip_loss_out(self, B, dev):
+        # (ops.new: a recorded step's loss launch writes to this address on every replay)
+        self.last_clip_losses = ops.new((B, 2), dtype=torch.float32, device=dev) if self.keep_clip_losses else None
+        return self.last_clip_losses
+
+    def _dp_wanted(self):
+        """Are the global denominators needed?  A label-dependent mean, uneven batches, or a weighted mean (norm 'sum'): the
+        ranks' weight sums differ even when their batches are even."""
+        dp = self._dp
+        if dp is None or dp.world <= 1:
+            return False
+        return self.dp_valid_mean or dp.uneven_batches or (self._cw is not None and self._clip_norm() == 'sum')
+
     def dp_divisors(self, args, dev):
         dp = self._dp
-        if dp is None or dp.world <= 1 or not (self.dp_valid_mean or dp.uneven_batches):
+        if not self._dp_wanted():
             return None
         div = dp.global_divisors(self._dp_local(args), dev)
         # (one device buffer for the life of the loss: a recorded step's loss launch keeps reading this address)
@@ -1398,8 +1438,11 @@ class _MarginBase(_DPMeans, nn.Module):
         return k
 
     def _run(self, inters, rels, *, B, T, C, NR, mem, w, y, r, g, sel, margin, lymbda, max_neg, tr_correct,
-             mask_inplace, rels_mean_valid, shape1, sample=False, y_stride=1):
+             mask_inplace, rels_mean_valid, shape1, sample=False, y_stride=1, args=None):
         dev = inters.device
+        cwt = self._clip_weight(args, B, dev)
+        norm = self._clip_norm()
+        clip_loss = self._clip_loss_out(B, dev)
         # the loader delivers float64 masks / weights and int64 labels: the kernel reads those
         # dtypes in place (no cast kernels); anything else is converted to the fp32 / int32 form of the ABI
         fl = [t for t in (mem, w) if t is not None]
@@ -1421,6 +1464,7 @@ class _MarginBase(_DPMeans, nn.Module):
         tail = (B, T, C, NR, margin, lymbda, max_neg, tr_correct, mask_inplace, rels_mean_valid)
         self._dp_args = (B, r if rels_mean_valid else None, NR)
         divisors = self.dp_divisors(None, dev)
+        weighted = dict(clip_weight=cwt, clip_weight_norm=norm, clip_loss=clip_loss) if (cwt is not None or clip_loss is not None) else {}
         skey = self._sample_key() if sample else 0
         if sample and self.sampler is not None:
             # the caller draws: probabilities from the kernel (no loss pass), indices from the sampler, then forced
@@ -1435,7 +1479,7 @@ class _MarginBase(_DPMeans, nn.Module):
             loss, d_i, d_r, sel_out, probs = ops.margin_loss(
                 i_.view(B * T, C), r_.view(B * T, NR) if r_ is not None else None, *common, sel, *tail, loader_types=loader,
                 sample=1 if sample else 0, sample_seed=skey, sample_seed_dev=self._seed_dev, want_probs=bool(sample),
-                divisors=divisors, y_stride=y_stride)
+                divisors=divisors, y_stride=y_stride, **weighted)
             self.last_selected = sel_out
             if probs is not None:
                 self.last_probs = probs
@@ -1446,20 +1490,26 @@ class _MarginBase(_DPMeans, nn.Module):
 
     def _dp_local(self, args):
         B, r, NR = self._dp_args
+        if self._cw is not None and self._clip_norm() == 'sum':
+            # (weighted means: the weight sums take the counts' place -- all clips, labelled clips)
+            w = self._cw.double()
+            return [w.sum(), (w * (r.reshape(B, -1)[:, 0] != NR)).sum() if r is not None else 0]
         return [B, _count_labelled(r, NR) if r is not None else 0]
 
     def needs_before_replay(self):
-        return self._dp is not None and self._dp.world > 1 and (self.dp_valid_mean or self._dp.uneven_batches) and self._div_buf is not None
+        return self._dp_wanted() and self._div_buf is not None
 
     def before_replay(self, args):
         """lirec_amd.graph.RecordedTrainStep calls this before each replay with the batch as it is NOW: under data parallelism the
         divisors of the refilled batch go into the buffer the recorded loss launch reads (a collective: every rank's replay).  The
         labels themselves are read in place by the recorded launch."""
-        if self._dp is None or self._dp.world <= 1 or not (self.dp_valid_mean or self._dp.uneven_batches) or self._div_buf is None:
+        if not self._dp_wanted() or self._div_buf is None:
             return
         B, r, NR = self._dp_args
         if r is not None:
             self._dp_args = (len(args['rels_label']), _dev_tensor(args['rels_label'], self._div_buf.device, r.dtype), NR)
+        if self._cw is not None:
+            self._clip_weight(args, self._dp_args[0], self._div_buf.device)      # (the refilled batch's weights)
         self.dp_divisors(None, self._div_buf.device)
 
 
@@ -1475,7 +1525,7 @@ class MaxMarginCrossEntropyLoss(_MarginBase):
         B, C = inters.shape
         return self._run(inters, None, B=B, T=1, C=C, NR=0, mem=None, w=args['multilab_weights'],
                          y=args['labels'], r=None, g=None, sel=None, margin=self.m, lymbda=1.0, max_neg=False,
-                         tr_correct=False, mask_inplace=False, rels_mean_valid=False, shape1=False)
+                         tr_correct=False, mask_inplace=False, rels_mean_valid=False, shape1=False, args=args)
 
 
 class MultiTaskMaxMargin(_MarginBase):
@@ -1505,7 +1555,7 @@ class MultiTaskMaxMargin(_MarginBase):
         return self._run(inters, rels, B=B, T=1, C=C, NR=self.n_rels, mem=None, w=args['multilab_weights'], y=y,
                          r=args['rels_label'] if rels is not None else None, g=None, sel=None, margin=self.m,
                          lymbda=float(opt.lymbda), max_neg=False, tr_correct=False, mask_inplace=False,
-                         rels_mean_valid=True, shape1=True, y_stride=stride)
+                         rels_mean_valid=True, shape1=True, y_stride=stride, args=args)
 
 
 class MarginLoss(_MarginBase):
@@ -1523,7 +1573,7 @@ class MarginLoss(_MarginBase):
         return self._run(inters, None, B=B, T=T, C=C, NR=0, mem=args['mem_mask'], w=args['multilab_weights'],
                          y=args['labels'], r=None, g=args['gt_tracks'], sel=None, margin=self.m, lymbda=1.0,
                          max_neg=bool(opt.tr_max_neg and opt.tr_sum_max_flag), tr_correct=bool(opt.tr_correct),
-                         mask_inplace=True, rels_mean_valid=False, shape1=False, sample=bool(opt.tr_cat_distr))
+                         mask_inplace=True, rels_mean_valid=False, shape1=False, sample=bool(opt.tr_cat_distr), args=args)
 
 
 class MarginTrackRelsLoss(_MarginBase):
@@ -1543,7 +1593,7 @@ class MarginTrackRelsLoss(_MarginBase):
                          y=args['labels'], r=args['rels_label'], g=args['gt_tracks'], sel=None, margin=self.m,
                          lymbda=float(opt.lymbda), max_neg=bool(opt.tr_max_neg and opt.tr_sum_max_flag),
                          tr_correct=bool(opt.tr_correct), mask_inplace=True, rels_mean_valid=False, shape1=True,
-                         sample=bool(opt.tr_cat_distr))
+                         sample=bool(opt.tr_cat_distr), args=args)
 
 
 class MultiTaskCrossEntropyLoss(_DPMeans, nn.Module):
@@ -1564,12 +1614,16 @@ class MultiTaskCrossEntropyLoss(_DPMeans, nn.Module):
         y, r = self._labels32(args, dev)
         cw = _dev_tensor(self.weights, dev, torch.float32) if self.weights is not None else None
 
+        cwt = self._clip_weight(args, B, dev)
+        clip_loss = self._clip_loss_out(B, dev)
+        weighted = dict(clip_weight=cwt, clip_weight_norm=self._clip_norm(), clip_loss=clip_loss) \
+            if (cwt is not None or clip_loss is not None) else {}
         self._dp_args = (y, r, cw, B)
         divisors = self.dp_divisors(None, dev)
         res = {}
 
         def runner(i_, r_):
-            loss, d_i, d_r = ops.ce_loss(i_, r_, y, r, cw, B, C, self.n_rels, divisors=divisors)
+            loss, d_i, d_r = ops.ce_loss(i_, r_, y, r, cw, B, C, self.n_rels, divisors=divisors, **weighted)
             res['d'] = (d_i, d_r)
             return loss.view(()), d_i, d_r
         out = _LossFn.apply(runner, inters, rels)
@@ -1578,6 +1632,9 @@ class MultiTaskCrossEntropyLoss(_DPMeans, nn.Module):
     def _dp_local(self, args):
         # (F.cross_entropy(weight=w) is a WEIGHTED mean: its denominator is the sum of the targets' class weights, :372-375)
         y, r, cw, B = self._dp_args
+        if self._cw is not None and self._clip_norm() == 'sum':
+            w = self._cw.double()
+            return [(w * cw[y.long()]).sum() if cw is not None else w.sum(), (w * (r.reshape(-1) != self.n_rels)).sum()]
         return [cw[y.long()].sum() if cw is not None else B, _count_labelled(r, self.n_rels)]
 
     def _labels32(self, args, dev):
@@ -1608,6 +1665,8 @@ class MultiTaskCrossEntropyLoss(_DPMeans, nn.Module):
         y, r = self._labels32(args, dev)
         if self._dp is not None and self._dp.world > 1 and self._div_buf is not None:
             self._dp_args = (y, r, self._dp_args[2], y.numel())
+            if self._cw is not None:
+                self._clip_weight(args, y.numel(), dev)                          # (the refilled batch's weights)
             self.dp_divisors(None, dev)
 
 

@@ -13,8 +13,8 @@ import threading
 import torch
 
 from . import _lib
-from ._lib import (Dropout, FusedAdamArgs, EmbedBwdArgs, EmbedDxArgs, EmbedDxIndexedArgs, EmbedFwdArgs, EvalArgs, EvalTopkArgs, LinearBwdArgs,
-                   LinearFwdArgs, MarginLossArgs, Pieces, PredictArgs, RowSel, check, lib)
+from ._lib import (CLIP_WEIGHT_NORMS, ClipWeights, Dropout, FusedAdamArgs, EmbedBwdArgs, EmbedDxArgs, EmbedDxIndexedArgs, EmbedFwdArgs, EvalArgs,
+                   EvalTopkArgs, LinearBwdArgs, LinearFwdArgs, LirecError, MarginLossArgs, Pieces, PredictArgs, RowSel, check, lib)
 
 
 class _ThreadCell(threading.local):
@@ -617,7 +617,8 @@ def _arrive_counter(dev):
 
 def margin_loss(ints, rels, mem, w, y, r, g, sel, B, T, Cc, NR, margin, lymbda, max_neg, tr_correct,
                 mask_inplace, rels_mean_valid, loader_types=False, sample=0, sample_seed=0, sample_seed_dev=None,
-                want_probs=False, heads=None, back=None, divisors=None, y_stride=1):
+                want_probs=False, heads=None, back=None, divisors=None, y_stride=1, clip_weight=None, clip_weight_norm='sum',
+                clip_loss=None):
     """Fused loss forward+backward.  ``ints`` [B*T, C] is modified in place when
     ``mask_inplace``.  Returns (loss[1], d_ints, d_rels|None, sel_out[B], probs[B,T]|None).
     ``sample``: 1 draws the positive track in the kernel (tr_cat_distr); 2 only computes probs / the draw (no loss).
@@ -625,9 +626,13 @@ def margin_loss(ints, rels, mem, w, y, r, g, sel, B, T, Cc, NR, margin, lymbda, 
     outputs ARE ``ints`` / ``rels``, ``back`` = linear_bwd_group items with the string 'ints' / 'rels' in place of dY (the
     gradient buffers are made here); heads forward, this loss and the heads' data gradients in one library call.
     ``divisors``: the data-parallel denominators of the batch means (lirec_margin_loss_args::batch_divisor) -- a pair of numbers
-    (batch, labelled relationship rows; 0 = this batch's own) or a device float32[2] tensor the kernel reads."""
+    (batch, labelled relationship rows; 0 = this batch's own) or a device float32[2] tensor the kernel reads.
+    ``clip_weight`` / ``clip_weight_norm`` / ``clip_loss``: lirec_clip_weights -- a device [B] float32 or float64 tensor of per-clip
+    weights (taken as given: not checked for sign or finiteness), 'sum' | 'count', and a device float32 [B, 2] tensor that receives
+    the per-clip values (lymbda * li_b, lr_b); with neither, the unweighted export is called."""
     dev = ints.device
     probs_only = sample == 2
+    cw = _clip_weights(clip_weight, clip_weight_norm, clip_loss, B, dev)
     d_ints = None if probs_only else new((B * T, Cc), dtype=torch.float32, device=dev)
     d_rels = new((B * T, NR), dtype=torch.float32, device=dev) if (rels is not None and not probs_only) else None
     loss = None if probs_only else new(1, dtype=torch.float32, device=dev)
@@ -658,7 +663,10 @@ def margin_loss(ints, rels, mem, w, y, r, g, sel, B, T, Cc, NR, margin, lymbda, 
         assert all(t is None or t.dtype == torch.float32 for t in (mem, w)) and \
             all(t is None or t.dtype == torch.int32 for t in (y, r, g))
     if heads is None:
-        check(lib().lirec_margin_loss(C.byref(a), _stream()), 'lirec_margin_loss')
+        if cw is None:
+            check(lib().lirec_margin_loss(C.byref(a), _stream()), 'lirec_margin_loss')
+        else:
+            check(lib().lirec_margin_loss_weighted(C.byref(a), C.byref(cw), _stream()), 'lirec_margin_loss_weighted')
         return loss, d_ints, d_rels, sel_out, probs
     assert back is not None and len(back) == len(heads) and not probs_only
     fwd = (LinearFwdArgs * len(heads))()
@@ -671,8 +679,30 @@ def margin_loss(ints, rels, mem, w, y, r, g, sel, B, T, Cc, NR, margin, lymbda, 
         v.dW, v.db, v.dA, v.ldda, v.act, v.ldact = _p(dW), _p(db), dA, ldda, act, ldact
         v.n, v.K, v.N, v.mode, v.accumulate, v.parts = n, K, N, mode, int(accumulate), 2
         v.drop = drop
-    check(lib().lirec_heads_loss_fwd_bwd(fwd, bwd, len(heads), C.byref(a), _stream()), 'lirec_heads_loss_fwd_bwd')
+    if cw is None:
+        check(lib().lirec_heads_loss_fwd_bwd(fwd, bwd, len(heads), C.byref(a), _stream()), 'lirec_heads_loss_fwd_bwd')
+    else:
+        check(lib().lirec_heads_loss_fwd_bwd_weighted(fwd, bwd, len(heads), C.byref(a), C.byref(cw), _stream()),
+              'lirec_heads_loss_fwd_bwd_weighted')
     return loss, d_ints, d_rels, sel_out, probs
+
+
+def _clip_weights(clip_weight, norm, clip_loss, B, dev):
+    """The lirec_clip_weights of a loss call, or None when the call carries neither weights nor a per-clip output."""
+    if clip_weight is None and clip_loss is None:
+        return None
+    cw = ClipWeights()
+    if clip_weight is not None:
+        assert clip_weight.device == dev and clip_weight.dtype in (torch.float32, torch.float64) and \
+            clip_weight.numel() == B and clip_weight.is_contiguous()
+        cw.w, cw.w_f64 = _p(clip_weight), int(clip_weight.dtype == torch.float64)
+    if norm not in CLIP_WEIGHT_NORMS:
+        raise LirecError("clip_weight_norm must be 'sum' or 'count', not %r" % (norm,))
+    cw.norm = CLIP_WEIGHT_NORMS[norm]
+    if clip_loss is not None:
+        assert clip_loss.device == dev and clip_loss.dtype == torch.float32 and clip_loss.numel() == 2 * B and clip_loss.is_contiguous()
+        cw.clip_loss = _p(clip_loss)
+    return cw
 
 
 def _set_divisors(a, divisors, dev):
@@ -687,17 +717,22 @@ def _set_divisors(a, divisors, dev):
         a.batch_divisor, a.rels_divisor = float(divisors[0]), float(divisors[1])
 
 
-def ce_loss(ints, rels, y, r, class_w, B, Cc, NR, divisors=None):
-    """``divisors``: (sum of the targets' class weights, labelled relationship rows) of the GLOBAL batch, each divided by world (the
+def ce_loss(ints, rels, y, r, class_w, B, Cc, NR, divisors=None, clip_weight=None, clip_weight_norm='sum', clip_loss=None):
+    """``clip_weight`` / ``clip_weight_norm`` / ``clip_loss``: as margin_loss (the clip weight multiplies the class weight; the
+    per-clip values are (cw[y_b] * CE_b, CE_b of the relationship row)).  ``divisors``: (sum of the targets' class weights, labelled relationship rows) of the GLOBAL batch, each divided by world (the
     data-parallel form, lirec_ce_loss); a pair of numbers or a device float32[2] tensor; None: this batch's own."""
     dev = ints.device
     d_ints = new((B, Cc), dtype=torch.float32, device=dev)
     d_rels = new((B, NR), dtype=torch.float32, device=dev) if rels is not None else None
     loss = new(1, dtype=torch.float32, device=dev)
     partial = new(2 * B + 2, dtype=torch.float32, device=dev)
-    check(lib().lirec_ce_loss(_p(ints), ints.stride(0), _p(rels), rels.stride(0) if rels is not None else 0,
-                              _p(y), _p(r), _p(class_w), B, Cc, NR, _p(d_ints), Cc, _p(d_rels), NR, _p(loss),
-                              _p(partial), *_ce_divisors(divisors, dev), _stream()), 'lirec_ce_loss')
+    cw = _clip_weights(clip_weight, clip_weight_norm, clip_loss, B, dev)
+    head = (_p(ints), ints.stride(0), _p(rels), rels.stride(0) if rels is not None else 0, _p(y), _p(r), _p(class_w), B, Cc, NR,
+            _p(d_ints), Cc, _p(d_rels), NR, _p(loss), _p(partial), *_ce_divisors(divisors, dev))
+    if cw is None:
+        check(lib().lirec_ce_loss(*head, _stream()), 'lirec_ce_loss')
+    else:
+        check(lib().lirec_ce_loss_weighted(*head, C.byref(cw), _stream()), 'lirec_ce_loss_weighted')
     return loss, d_ints, d_rels
 
 

@@ -295,7 +295,9 @@ class DataParallel:
         count over world instead (``lirec_margin_loss_args::rels_divisor``), and the averaged gradient is exactly the single
         process's.  The other three losses are plain means over the batch: exact as they are with equal local batches
         (``ShardSampler``); ``uneven_batches=True`` also all-reduces the clip count, for a caller whose ranks draw batches of
-        different sizes."""
+        different sizes.  Give it too whenever the batches carry per-clip weights (``batch['clip_weight']``) under
+        ``opt.clip_weight_norm='sum'``, for any of the five losses: a weighted mean divides by the GLOBAL batch's weight sums, which
+        the ranks' own sums do not add up to even when their batches are even."""
         self.model, self.optimizer = model, optimizer
         self.group, self.uneven_batches = group, bool(uneven_batches)
         self.loss = loss

@@ -26,6 +26,17 @@ from .metrics import Precision, RelationshipsAcc
 from .util import Averaging
 
 
+def _eval_loader(dataset, batch_size, sampler=None):
+    """the loader of an evaluation pass over ``dataset``, in order"""
+    if device_collate_in_force(dataset):                               # (opt.device_collate: the batch buffer written on the device)
+        return ResidentLoader(dataset, batch_size=batch_size, shuffle=False, sampler=sampler, drop_last=False, device=opt.device)
+    if getattr(dataset, 'collate_fn', None) is not None:              # (piece tables + index, built on threads: lirec_amd/loader.py)
+        return ThreadedLoader(dataset, batch_size=batch_size, shuffle=False, sampler=sampler, num_workers=opt.num_workers,
+                              drop_last=False, collate_fn=dataset.collate_fn)
+    return torch.utils.data.DataLoader(dataset, batch_size=batch_size, shuffle=False, sampler=sampler, num_workers=opt.num_workers,
+                                       drop_last=False)
+
+
 def testing(test_dataset, model, loss, total_iter=1, mode='val', train_start_time='', verbose=True):
     # One process per GPU (lirec_amd.parallel): each rank evaluates ITS clips of the dataset (every clip on exactly one rank), the
     # counters are summed over the ranks after the loop and every rank returns -- rank 0 prints -- the whole dataset's metrics
@@ -35,14 +46,7 @@ def testing(test_dataset, model, loss, total_iter=1, mode='val', train_start_tim
     sharded = world > 1 and bool(getattr(opt, 'dp_shard_eval', True))
     sampler = parallel.ShardSampler(len(test_dataset), opt.batch_size, shuffle=False, pad=False) if sharded else None
     verbose = verbose and (rank == 0 or not sharded)
-    if device_collate_in_force(test_dataset):                          # (opt.device_collate: the batch buffer written on the device)
-        loader = ResidentLoader(test_dataset, batch_size=opt.batch_size, shuffle=False, sampler=sampler, drop_last=False, device=opt.device)
-    elif getattr(test_dataset, 'collate_fn', None) is not None:       # (piece tables + index, built on threads: lirec_amd/loader.py)
-        loader = ThreadedLoader(test_dataset, batch_size=opt.batch_size, shuffle=False, sampler=sampler, num_workers=opt.num_workers,
-                                drop_last=False, collate_fn=test_dataset.collate_fn)
-    else:
-        loader = torch.utils.data.DataLoader(test_dataset, batch_size=opt.batch_size, shuffle=False, sampler=sampler,
-                                             num_workers=opt.num_workers, drop_last=False)
+    loader = _eval_loader(test_dataset, opt.batch_size, sampler)
     losses = Averaging()
     model.eval()
     prec = Precision(inter2mgd=getattr(test_dataset, 'interidx2mgdidx', None), n_rels=opt.rels_dim, soft_gt=opt.soft_gt)
@@ -223,3 +227,32 @@ def testing(test_dataset, model, loss, total_iter=1, mode='val', train_start_tim
     if opt.tr_maximize:
         out.update({'tracks': out_tr, 'joint': out_joint})
     return out
+
+
+def clip_losses(dataset, model, loss, batch_size=None):
+    """The loss of every clip of ``dataset``: float32 numpy ``[n, 2]`` in dataset order, columns (lymbda * interaction term,
+    relationship term) -- the per-clip values of the loss kernel (``lirec_clip_weights::clip_loss``), UNWEIGHTED and undivided,
+    whatever weights the dataset carries.  What hard-example mining, label-noise triage or a curriculum rank the clips by.
+    Eval mode, no gradients, the loader selection of ``testing()``; singleton batches are NOT skipped (every clip gets its row); the
+    values stay on the device until ONE copy at the end.  The model's mode and ``loss.keep_clip_losses`` are restored."""
+    bs = int(batch_size or opt.batch_size)
+    loader = _eval_loader(dataset, bs)
+    was_training, kept = model.training, loss.keep_clip_losses
+    model.eval()
+    loss.keep_clip_losses = True
+    parts = []
+    try:
+        with torch.no_grad():
+            to_dev = getattr(dataset, 'to_device', None) if str(opt.device).startswith('cuda') else None
+            for batch in loader:
+                if to_dev is not None:
+                    batch = to_dev(batch)
+                loss(model(batch), batch)
+                parts.append(loss.last_clip_losses)
+    finally:
+        loss.keep_clip_losses = kept
+        loss.last_clip_losses = None
+        model.train(was_training)
+    if not parts:
+        return np.zeros((0, 2), dtype=np.float32)
+    return torch.cat(parts).cpu().numpy()

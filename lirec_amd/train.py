@@ -119,8 +119,20 @@ def training(train_dataset, **kwargs):
         #  a mean of per-rank means is not the global mean; attached, the loss divides by the all-reduced count)
         raise RuntimeError('training() under torch.distributed with %s: attach the loss -- DataParallel(model, optimizer, loss=loss) -- '
                            'so that its valid-row mean is the global batch\'s' % type(loss).__name__)
+    if getattr(opt, 'class_balance', ''):
+        # class-balanced training: every clip weighted by the frequency of its interaction class in the train set; the weights ride in
+        # the batch (batch['clip_weight']) and are applied inside the loss kernel
+        from .data import class_balanced_weights, interaction_labels, with_clip_weights
+        train_dataset = with_clip_weights(train_dataset, class_balanced_weights(interaction_labels(train_dataset), train_dataset.n_classes,
+                                                                                how=opt.class_balance))
+    from .features import CLIP_WEIGHT
+    weighted = CLIP_WEIGHT in (getattr(train_dataset, '_stacked', None) or ()) or getattr(train_dataset, 'carries_clip_weights', False)
+    if world > 1 and weighted and getattr(opt, 'clip_weight_norm', 'sum') == 'sum' and getattr(loss, '_dp', None) is None:
+        # (a weighted mean divides by the GLOBAL batch's weight sums: the ranks' own sums differ even with even batches)
+        raise RuntimeError('training() under torch.distributed with clip weights and clip_weight_norm=\'sum\': attach the loss -- '
+                           'DataParallel(model, optimizer, loss=loss) -- so that its weighted mean is the global batch\'s')
     batch_time, data_time, losses = Averaging(), Averaging(), Averaging()
-    guarded = lambda: bool(getattr(optimizer, 'skip_nonfinite', False))
+    guarded =lambda: bool(getattr(optimizer, 'skip_nonfinite', False))
 
     def eval_weights():
         """opt.eval_ema: the val / test evaluations see the averaged weights (FusedAdam.ema_weights: swapped in by value, the
