@@ -25,9 +25,7 @@ import torch
 
 from . import ops
 from ._lib import LirecError
-
-
-_STAGE_LANES = {}
+from .config import opt
 
 
 class _MarkingSync:
@@ -181,6 +179,7 @@ class RecordedTrainStep:
                 raise LirecError('RecordedTrainStep: the batch\'s piece tables require grad -- a recorded step computes no input '
                                  'gradient; run the eager step (model(batch) -> loss -> backward) instead')
         self.model, self.loss, self.optim, self.batch = model, loss, optimizer, batch
+        self.lanes = model.lanes       # (lirec_amd.lanes.StepLanes: the side streams and the state handed over between them)
         self.batches = [batch, next_batch] if next_batch is not None else [batch]
         self.sync = getattr(model, 'grad_sync', None)
         if next_batch is not None and self.sync is not None:
@@ -189,27 +188,19 @@ class RecordedTrainStep:
         optimizer._ensure_state()
         if hasattr(optimizer, 'fold_if_due'):
             optimizer.fold_if_due()       # (skipped steps of another frozen set, or of a guard since switched off: while the step is by value)
-        # [forward calls (the dropout key's offset), Adam step, Adam step AS THE SIDE STREAM COUNTS IT]: the first two are advanced by
-        # the step's first launch; the third by the side stream itself in front of its share of the update -- a replayed step leaves
-        # that stream un-joined (`defer`), so its Adam launch may still be running when the NEXT step's first launch advances the
-        # step: read from the shared counter, part of that launch's workgroups then took the next step's bias correction (seen as a
-        # bitwise mismatch of a whole run on some boxes of the pool and not on others)
+        # [forward calls (the dropout key's offset), Adam step, Adam step AS LANE 0 COUNTS IT]: the first two are advanced by the step's
+        # first launch; the third by lane 0's own Adam launch, which under deferral may still run when the next step begins
         self.state = torch.tensor([model._fwd_train_calls, optimizer._step, optimizer._step], dtype=torch.int64, device=dev)
         try:
             self._record(model, loss, optimizer, batch, warmup, next_batch, overwrite, dev)
         except BaseException:
-            # (a failed recording must leave the eager loop's state behind: device-side counters detached, the side stream joined
-            #  and joining again at the end of every backward -- an advisor finding of round 5: the flags used to survive the raise,
-            #  and the eager fall-back then zeroed gradients the un-joined side stream was still reading)
+            # (a failed recording leaves the eager loop's state behind: device-side counters detached, deferral off and the lane
+            #  joined -- DESIGN 4.4, "Lanes")
             self.release()
             raise
 
     def _record(self, model, loss, optimizer, batch, warmup, next_batch, overwrite, dev):
-        model._seed_dev, optimizer._step_dev = self.state[0:1], self.state[1:2]
-        optimizer._step_side_dev = self.state[2:3]
-        if hasattr(loss, '_sample_key'):
-            loss._sample_calls = model._fwd_train_calls
-            loss._seed_dev = self.state[0:1]
+        self._attach_counters()
         self.loss_out = torch.zeros(1, dtype=torch.float32, device=dev)
         self.stream = torch.cuda.current_stream()
         # The step is issued as a unit, so its weight gradients may OVERWRITE the flat gradient buffer instead of accumulating
@@ -241,8 +232,7 @@ class RecordedTrainStep:
         # folded into the launch that finishes them, which also keeps a q32b copy of the new weights for the next forward (no
         # separate Adam pass over that bucket, no staging of W1): FusedAdam.arm_first_layer_update.  Single GPU, layer 1 on the
         # q32b kernels (seen on the steps taken so far).
-        from .config import opt as _opt
-        self.fused = bool(self.sync is None and getattr(_opt, 'fuse_dw1_adam', True) and getattr(model, 'last_layer1_planes', False)
+        self.fused = bool(self.sync is None and getattr(opt, 'fuse_dw1_adam', True) and getattr(model, 'last_layer1_planes', False)
                           and getattr(model, '_has_ints', False) and getattr(model, '_has_ctx', False)
                           and hasattr(optimizer, 'arm_first_layer_update') and hasattr(model, 'refresh_w1q') and not clipping)
         if self.fused and getattr(optimizer, 'device_hyper', False):
@@ -261,33 +251,21 @@ class RecordedTrainStep:
             self.fused = model.refresh_w1q()
         # (does the recorded forward read the q32b shadow of the first-layer weights?  step() rebuilds a stale one before it replays)
         self._shadow_w1 = bool(self.fused and getattr(model, '_w1q_valid', False))
-        # The recorded forward stages the gate's weights on the side stream WITHOUT waiting for this stream when the previous step's
-        # Adam launch on that stream was their last writer (model._bucket0_on_side at recording time).  A replay inherits that:
-        # step() orders the side stream behind this one itself whenever something else has written the parameters in between.
+        # (did the recorded forward stage the gate's weights on lane 0 WITHOUT waiting for this stream -- bucket0_on_side at recording
+        #  time?  step() then orders the lane behind this stream itself whenever something else has written the parameters since)
         self._side_unordered = False
         torch.cuda.synchronize()
         self.marks = []
-        # Replays leave the weight-gradient side stream un-joined at the end of the step (model._run_backward): the heads' / gate's
-        # weight gradients, their Adam launch and the next step's staging of the gate's weights overlap the next step's head.  Needs the
-        # overwrite mode (no zeroing pass over gradients the deferred update still reads) and one GPU.
-        from .config import opt as _o
-        self.defer = bool(self.overwrite and self.sync is None and getattr(_o, 'defer_side_join', True) and not clipping)
-        model._defer_side_join = self.defer
+        # Deferral ("Lanes"): needs the overwrite mode -- no zeroing pass over gradients the deferred update still reads
+        self.defer = bool(self.overwrite and self.sync is None and getattr(opt, 'defer_side_join', True) and not clipping)
+        self.lanes.defer_join = self.defer
         if self.sync is not None:
             model.grad_sync = _MarkingSync(self.sync, self.marks)
         try:
             with ops.keep_allocations() as kept:
                 if next_batch is not None:
                     # the rows of the first batch, staged here once (eagerly); from then on every step stages the other set's
-                    # (a stream of the LOWEST priority the device offers: the pass is to fill what the step's own kernels leave)
-                    # (ONE such stream per device for the whole process, like the weight-gradient lanes: HIP deals streams onto a few
-                    #  hardware queues in creation order, and a stream made for the n-th object of a run has been seen to share a queue
-                    #  with the step's own stream -- the staging pass then runs in line with the step: 1.16 ms instead of 0.86)
-                    key = str(dev)
-                    if key not in _STAGE_LANES:
-                        lo, hi = torch.cuda.Stream.priority_range()
-                        _STAGE_LANES[key] = torch.cuda.Stream(device=dev, priority=lo)
-                    self._pre_lane = (_STAGE_LANES[key], None)
+                    self._pre_lane = self.lanes.staging(dev)
                     self.pre[0] = model.prestage(self.batches[0])
                     self.pre[1] = model.prestage(self.batches[1], advance=1)
                 if hasattr(optimizer, 'sync_hyper'):
@@ -310,8 +288,15 @@ class RecordedTrainStep:
         self.marks = [m for m in self.marks if self.sync is not None]
         self._loss_outs = getattr(self, '_loss_outs', [self.loss_out])
 
+    def _attach_counters(self):
+        """the kernels read the dropout key's offset and the Adam step (the caller's and the side stream's count) from ``state``"""
+        self.model._seed_dev, self.optim._step_dev = self.state[0:1], self.state[1:2]
+        self.lanes.step_side_dev = self.state[2:3]
+        if hasattr(self.loss, '_sample_key'):
+            self.loss._sample_calls = self.model._fwd_train_calls
+            self.loss._seed_dev = self.state[0:1]
+
     def _one_step(self, check: bool = False, k: int = 0):
-        import ctypes as C
         over = self.overwrite or check
         batch = self.batches[k]
         pipelined = len(self.batches) == 2 and self.pre[k] is not None
@@ -324,19 +309,19 @@ class RecordedTrainStep:
             # the launch that advances the dropout key: the staging pass derives this step's key from the device counter as it finds
             # it, workgroup by workgroup, and a low-priority pass that is still running when the next step begins would otherwise
             # make part of its keep bytes with the key after next (tests: ..._with_a_lagging_staging_stream_...)
-            main, s3 = ops.current_stream_handle(), C.c_void_p(self._pre_lane[0].cuda_stream)
+            main, s3 = ops.current_stream_handle(), self._pre_lane.handle
             ops.stream_wait(main, s3)
         self.optim.zero_grad(counters=(self.state, [1, 1]), zero=not over)
         if pipelined:
             # ... and the forward is told where they are
-            self.model._pre = self.pre[k]
+            self.lanes.prestaged = self.pre[k]
             # ... and the OTHER buffer set's rows -- the next step's -- are staged beside this whole step (from its start: measured
             # best; beside the gate or behind the loss were slower, HISTORY round 4)
             ops.stream_wait(s3, main)
             with ops.on_stream(s3):                 # (the staging STREAM; this thread's own library context)
                 self.pre[1 - k] = self.model.prestage(self.batches[1 - k], into=self.pre[1 - k], advance=0)
         if ops.CommandList.mark() >= 0 and k == 0:
-            self._side_unordered = bool(getattr(self.model, '_bucket0_on_side', False))
+            self._side_unordered = self.lanes.bucket0_on_side
         out = self.model(dict(batch))                # the model re-binds x['features'] (mlp/model.py:272)
         lv = self.loss(out, batch)
         # The recorder is thread-local: backward is recorded only when loss.backward() takes the direct path ON THIS THREAD
@@ -364,13 +349,12 @@ class RecordedTrainStep:
             if _overwrite_coverage(self.model, self.model.flat_grads(attach=False)):
                 # ... and no buffer was the target of two launches (the second would have wiped out the first's share)
                 self.overwrite = ops.grad_overwrite_conflicts() == 0
-        # (nothing runs between this step's backward and its update: the side stream's share of Adam need not wait for the tail of
-        #  backward on this stream -- lirec_amd/optim.py)
-        self.optim.atomic_step = not check
+        # (nothing runs between this step's backward and its update: lane 0's share of Adam need not wait for backward's tail)
+        self.lanes.atomic_step = not check
         try:
             self.optim.step()
         finally:
-            self.optim.atomic_step = False
+            self.lanes.atomic_step = False
         self.loss_out = lv.detach().reshape(-1)[:1]
         if len(self.batches) == 2 and ops.CommandList.mark() >= 0:
             self._loss_outs = (getattr(self, '_loss_outs', None) or [None, None])
@@ -439,14 +423,11 @@ class RecordedTrainStep:
         # (host flags): rebuild them from the parameters as they are now, on this stream, before the replay reads them.
         if getattr(self, 'fused', False) and self._shadow_w1 and not getattr(self.model, '_w1q_valid', False):
             self.model.refresh_w1q()
-        # (the recorded staging of the gate's weights skips its wait for this stream: legal only while the side stream's own Adam
-        #  launch is their last writer -- the model clears the flag when anything else writes the parameters)
-        if self._side_unordered and not getattr(self.model, '_bucket0_on_side', False):
+        if self._side_unordered and not self.lanes.bucket0_on_side:
             lane = self.model._wgrad_lane()
             if lane is not None:
-                import ctypes as C
-                ops.stream_wait(C.c_void_p(lane[0].cuda_stream), ops.current_stream_handle())
-            self.model._bucket0_on_side = True      # (the replayed step's own Adam launch is the last writer again)
+                ops.stream_wait(lane.handle, ops.current_stream_handle())
+            self.lanes.bucket0_on_side = True       # (the replayed step's own Adam launch is the last writer again)
         if hasattr(self.loss, 'before_replay') and self.loss.needs_before_replay():
             # (what the recorded loss launch reads from buffers of the loss's own: under data parallelism the denominators of its
             #  valid-row means, all-reduced from the labels of the batch as it is NOW -- a collective, on every rank's replay; the CE
@@ -490,7 +471,7 @@ class RecordedTrainStep:
                         sync.finish_gathers()
                 self.cmds.replay(pos, -1)
         self._advance_host()
-        self.model._side_unjoined = self.defer
+        self.lanes.unjoined = self.defer
         return self.loss_out
 
     def lag(self, command=None, ticks: int = 150000):
@@ -507,10 +488,10 @@ class RecordedTrainStep:
     def release(self):
         """Back to the eager loop: kernels take the key / step by value again."""
         self.model.join_side_streams()
-        self.model._defer_side_join = False
+        self.lanes.defer_join = False
         self.model._seed_dev = None
         self.optim._step_dev = None
-        self.optim._step_side_dev = None
+        self.lanes.step_side_dev = None
         if hasattr(self.loss, '_sample_key'):
             self.loss._seed_dev = None
         if getattr(self, 'fused', False):
@@ -524,12 +505,8 @@ class RecordedTrainStep:
         if hasattr(self.optim, 'fold_if_due'):
             self.optim.fold_if_due()      # (the eager steps in between may have changed the frozen set: before the counters attach)
         self.state.copy_(torch.tensor([self.model._fwd_train_calls, self.optim._step, self.optim._step], dtype=torch.int64), non_blocking=False)
-        self.model._seed_dev, self.optim._step_dev = self.state[0:1], self.state[1:2]
-        self.optim._step_side_dev = self.state[2:3]
-        if hasattr(self.loss, '_sample_key'):
-            self.loss._sample_calls = self.model._fwd_train_calls
-            self.loss._seed_dev = self.state[0:1]
+        self._attach_counters()
         if getattr(self, 'fused', False) and not self.model.refresh_w1q():
             raise RuntimeError('RecordedTrainStep.resume(): the q32b shadow of the first-layer weights cannot be rebuilt')
-        self.model._defer_side_join = self.defer
-        self.model._bucket0_on_side = False     # (eager steps in between: whoever wrote the parameters last, order the side stream)
+        self.lanes.defer_join = self.defer
+        self.lanes.params_written()             # (eager steps in between: whoever wrote the parameters last, order the side stream)

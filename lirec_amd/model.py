@@ -25,7 +25,6 @@ GPU raises.
 from __future__ import annotations
 
 import collections
-import ctypes as C
 
 import torch
 import torch.nn as nn
@@ -33,13 +32,11 @@ import torch.nn as nn
 from . import ops
 from ._lib import SITE_E_CTX, SITE_E_INTS, SITE_GATE, SITE_H1_CTX, SITE_H1_INTS, LirecError
 from .config import opt
+from .lanes import StepLanes
 
 __all__ = ['Modalities', 'MidFusionMultiClip', 'MidFusionMultiClipMaxTracks', 'GatingUnit',
            'MultiTaskCrossEntropyLoss', 'MultiTaskMaxMargin', 'MaxMarginCrossEntropyLoss',
            'MarginLoss', 'MarginTrackRelsLoss', 'create_model']
-
-
-_SIDE_LANES = {}          # (device, priority) -> (side stream, library context): see _HotPathModule._wgrad_lane
 
 
 def _ptr(t: torch.Tensor, col: int = 0) -> int:
@@ -239,6 +236,7 @@ class _HotPathModule(nn.Module):
             setattr(self, name + which, value)
 
     def _finish_init(self):
+        self.lanes = StepLanes()       # the side streams and what is handed over between them (a plain attribute: not in state_dict)
         self._plist = [p for _, p in self.named_parameters()]
         self._flat = self._flat_grad = None
         self._fwd_train_calls = 0
@@ -289,7 +287,7 @@ class _HotPathModule(nn.Module):
             p.grad = None
         self._offsets = offs
         self._w1q_valid = False                                 # (the q32b shadow of the first-layer weights belongs to the old buffer)
-        self._bucket0_on_side = False                           # (nobody has updated the new buffer on the side stream)
+        self.lanes.params_written()                             # (nobody has updated the new buffer on the side stream)
         self._flat, self._flat_grad = flat, None
         self._n_flat = extent                                   # flat extent (with alignment gaps)
         self._n_params = sum(k for _, k in offs.values())
@@ -297,9 +295,7 @@ class _HotPathModule(nn.Module):
     def load_state_dict(self, *a, **k):
         self.join_side_streams()
         self._w1q_valid = False         # (the parameters change under the q32b shadow of the first-layer weights)
-        # (... and on THIS stream: the next forward's staging of the gate's weights on the side stream must wait for it -- the
-        #  wait is skipped only when the optimiser's own launch on that stream was the last writer: _run_forward)
-        self._bucket0_on_side = False
+        self.lanes.params_written()     # (... and on THIS stream)
         return super().load_state_dict(*a, **k)
 
     def _apply(self, fn, *a, **k):            # .to() / .cuda() / .float(): keep the flat layout
@@ -537,7 +533,7 @@ class _HotPathModule(nn.Module):
 
     def _take_prestaged(self, X, mask, n, R):
         """the handle ``prestage`` left for exactly this forward (same buffers, same key), or None"""
-        pre, self._pre = getattr(self, '_pre', None), None
+        pre = self.lanes.take_prestaged()
         if pre is None or not self.training or (isinstance(X, ops.Q32Block) and X.planes != 2) or mask is None:
             return None
         ok = (pre['X'] == X.data_ptr() and pre['mask'] == mask.data_ptr() and pre['n'] == n and pre['R'] == R and
@@ -555,8 +551,9 @@ class _HotPathModule(nn.Module):
               'train': self.training, 'inters': None, 'rels': None}
         has_i, has_c, has_g = self._has_ints, self._has_ctx, self._has_gate
         self.last_layer1_planes = False
-        if not self.training or not getattr(self, '_defer_side_join', False):
-            self.join_side_streams()           # (a forward that is not the next replayed train step: order it behind the deferred update)
+        lanes = self.lanes
+        if not self.training or not lanes.defer_join:
+            lanes.join()                       # (a forward that is not the next replayed train step: order it behind the deferred update)
         Wi = self._segs_i.width if has_i else 0
         Wc = self._segs_c.width if has_c else 0
         # batch given as piece tables + index (lirec_amd.features): with opt.pieces_q32b (training steps) the q32b operand rows
@@ -628,34 +625,25 @@ class _HotPathModule(nn.Module):
             gws, w_side = None, None
             if self.training and getattr(opt, 'gate_q32', True) and n % 32 == 0:
                 gws = ops.new(ops.gate_ws_bytes(n, ldee, N), dtype=torch.uint8, device=dev)
-                # The weights' staging (37.7 MB read, as much written) depends on nothing in this step: it goes on the weight-
-                # gradient side stream, beside the MFMA-bound first layers, and the step's stream joins it in front of the gate.
-                # That stream is where the previous step's Adam updated these weights (lirec_amd/optim.py) -- then stream order is
-                # all the ordering it needs (`_bucket0_on_side`: set by that step(), cleared by anything else that may write the
-                # parameters: load_state_dict, _flatten; a caller that writes them by hand calls mark_params_written());
-                # otherwise it is first put behind this stream (one event record).
+                # The weights' staging (37.7 MB read, as much written) depends on nothing in this step: it goes on lane 0, beside the
+                # MFMA-bound first layers -- behind this stream first unless lane 0's own Adam launch wrote them last
                 lane = self._wgrad_lane()
                 if lane is not None and getattr(opt, 'gate_stage_on_side', True):
-                    side_h, main = C.c_void_p(lane[0].cuda_stream), ops.current_stream_handle()
-                    if not getattr(self, '_bucket0_on_side', False):
+                    side_h, main = lane.handle, ops.current_stream_handle()
+                    if not lanes.take_bucket0_on_side():
                         ops.stream_wait(side_h, main)
-                    self._bucket0_on_side = False           # (one-shot: armed again by the next FusedAdam.step)
                     # (the side STREAM, this thread's own library context: the same GEMM core decides here and in gate_fwd)
                     with ops.on_stream(side_h):
                         if ops.gate_stage_weights(Wg, n, ldee, N, gws):
                             w_side = (main, side_h)
             st['gate_ws'] = gws
             st['w_side_staged'] = w_side is not None
-        # A replayed train step leaves the weight-gradient side stream un-joined (`_defer_side_join`, _run_backward); the forward of
-        # the NEXT step is where the step's stream joins it -- in front of its second layers, which overwrite what that stream may
-        # still be reading (EE).  With the gate's weights staged on the side stream that is the `w_side` wait; WITHOUT (the staging
-        # declined, or is switched off) the same wait is issued on its own: every training forward under `_defer_side_join` joins, so that a
-        # backward may defer whenever the flag is set (an advisor finding of round 5: the deferral rested on `w_side` alone).
+        # (every training forward under deferral joins lane 0: the `w_side` wait, or the same wait on its own -- DESIGN 4.4, "Lanes")
         deferred_join = None
-        if self.training and getattr(self, '_defer_side_join', False) and has_g and w_side is None:
+        if self.training and lanes.defer_join and has_g and w_side is None:
             lane0 = self._wgrad_lane()
             if lane0 is not None:
-                deferred_join = (ops.current_stream_handle(), C.c_void_p(lane0[0].cuda_stream))
+                deferred_join = (ops.current_stream_handle(), lane0.handle)
         # (waiter, signaller) of the wait in front of the second layers: the staging's pair, else the deferred pair, else none
         join = w_side if (has_g and w_side is not None) else deferred_join
         st['pieces'] = pieces if pq is None else None          # (q32b rows staged from the pieces: backward is the dense path's)
@@ -673,14 +661,8 @@ class _HotPathModule(nn.Module):
                 ops.stream_wait(*join)              # (in front of the second layers: see the dense path below)
             ops.embed_fwd_heads([args_i, args_c], 3)
         elif join is not None:
-            # The step's stream joins the side stream IN FRONT OF THE SECOND LAYERS, not just in front of the gate: a replayed
-            # step leaves that stream un-joined (`_defer_side_join`), and what it may still be running from the previous step
-            # reads the heads' inputs -- EE, which the second layers are about to overwrite (the context / relationship heads'
-            # weight gradients), and the gate's staged rows.  Behind layer 1 and the pooling pass (~250 us into the step) the
-            # join waits for nothing in practice; in front of them it would give the deferral's overlap away.  Same launches in
-            # the same order: layer 1 + pooling (parts = 1), then the second layers (parts = 2).
-            # (the deferred join without the staging of the gate's weights on the side stream -- strict-f32 core, shapes the
-            #  q32b gate does not take, opt.gate_stage_on_side off: the same join at the same place, unconditionally)
+            # The step's stream joins lane 0 IN FRONT OF THE SECOND LAYERS (they overwrite EE, which an un-joined lane may still be
+            # reading), behind layer 1 + pooling (parts = 1), where the wait costs nothing: DESIGN 4.4, "Lanes", invariant 1
             ops.embed_fwd_heads([args_i, args_c], 1)
             ops.stream_wait(*join)
             ops.embed_fwd_heads([args_i, args_c], 2)
@@ -713,31 +695,9 @@ class _HotPathModule(nn.Module):
 
     # ---- backward ----------------------------------------------------------
     def _wgrad_lane(self, which: int = 0):
-        """(side stream, library context) for the weight-gradient GEMMs, or None.  ``which`` = 1: a second such lane, for the
-        second layers' weight gradients (see _run_backward).  The data-gradient GEMMs form the
-        critical chain of backward (head dA -> gate dEE -> hidden-layer gradient -> un-pool -> dW1) and most of them
-        fill a fraction of the chip; the weight gradients of the heads, the gate and the second layers only hang off
-        that chain, so they are enqueued on a second stream -- with its own context, hence its own split-K scratch --
-        and run beside it (opt.wgrad_side_stream)."""
-        if not getattr(opt, 'wgrad_side_stream', True):
-            return None
-        if getattr(self, '_sides', None) is None:
-            self._sides = {}
-        if which not in self._sides:
-            # (priority 0, the default stream's own: a lower-priority side stream was measured no better -- HISTORY round 4 -- and
-            #  the flag that selected it is gone, round 6)
-            prio = 0
-            # ONE lane per (device, priority) for the whole process, not one per model: HIP deals streams onto a few hardware
-            # queues round-robin, and the stream a fourth model of a process drew shared a queue with the step's own stream --
-            # every launch of its step then waited for the "concurrent" one (measured: 1.43 -> 2.10 ms/step, tools/mode3_sites.py)
-            key = (str(self._flat.device), prio, which)
-            if key not in _SIDE_LANES:
-                lane = (torch.cuda.Stream(device=self._flat.device, priority=prio), ops.Context())
-                with lane[1]:
-                    ops.ensure_scratch(self._flat.device, (128 if which == 0 else 64) << 20)
-                _SIDE_LANES[key] = lane
-            self._sides[which] = _SIDE_LANES[key]
-        return self._sides[which]
+        """The ``lanes.Lane`` for the weight-gradient GEMMs (``which`` = 1: the second layers'), or None: they only hang off the
+        critical chain of backward (head dA -> gate dEE -> hidden-layer gradient -> un-pool -> dW1) and run beside it."""
+        return self.lanes.wgrad(self._flat.device, which)
 
     def _run_backward(self, st, d_inters, d_rels, want_dx=False, want_dp=(False, False)):
         """The hand-written backward; returns (dX, dClip, dTrack): d loss / d X (the staged (n, R+1, D) block, X's dtype) when
@@ -756,48 +716,33 @@ class _HotPathModule(nn.Module):
         need = self.trainable_plan().need(want_dx or want_dp)
         if pieces is not None and ('tail_i' in need or 'tail_c' in need):
             need = need | {'tail_i', 'tail_c'}
+        lanes = self.lanes
         lane = self._wgrad_lane()
         main = ops.current_stream_handle() if lane is not None else None
-        side_h = C.c_void_p(lane[0].cuda_stream) if lane is not None else None
-        # A lane of their own for the second layers' weight gradients (dW2, db2).  On the first side stream they queue behind the
-        # gate's weight gradient, which ends just as the persistent first-layer weight-gradient kernel takes every CU: they then
-        # run AFTER it (40 us of GEMM + reduce), and the side stream's share of Adam after them -- the tail of the step.  On a third
-        # stream they run beside the gate's weight gradient and the hidden-layer gradient, long before that kernel starts.
+        side_h = lane.handle if lane is not None else None
+        # A lane of their own for the second layers' weight gradients (dW2, db2).  On lane 0 they queue behind the gate's weight
+        # gradient, which ends just as the persistent first-layer weight-gradient kernel takes every CU: they then run AFTER it
+        # (40 us), and lane 0's share of Adam after them -- the tail of the step.  On lane 1 they run long before that kernel starts.
         lane2 = self._wgrad_lane(1) if lane is not None else None
-        side2_h = C.c_void_p(lane2[0].cuda_stream) if lane2 is not None else None
+        side2_h = lane2.handle if lane2 is not None else None
 
         # (a side lane has a library context of its own -- its own split-K scratch -- and with it its own GEMM core selection,
         #  fixed when the lane was made: the launches it is handed take THIS context's core, whatever ran in the process before)
         core = ops.get_gemm_mode()
 
-        def on_side2(fn):
-            # (the FIRST side stream is put behind the same point of the main stream: the first bucket's Adam update runs on it
-            #  (lirec_amd/optim.py) and must come after the gate's data gradient -- enqueued on the main stream after that stream's
-            #  only fork -- has read the gate's weights.  One event record for both waiters.)
-            ops.stream_wait_many([side2_h, side_h], main)
-            with ops.on_stream(side2_h), lane2[1]:
+        def on_side(fn, to=None):
+            """run fn (a weight-gradient launch) on lane 0 -- ``to``: on that lane -- behind everything enqueued on main so far.  (Lane
+            1's fork puts lane 0 there too, one event record: bucket 0's update must follow the gate's data gradient on main.)"""
+            if to is None:
+                ops.stream_wait(side_h, main)
+            else:
+                ops.stream_wait_many([to.handle, side_h], main)
+            with ops.on_stream((to or lane).handle), (to or lane).ctx:
                 ops.set_gemm_mode(core)
                 fn()
 
-        def on_side(fn):
-            """run fn (a weight-gradient launch) on the side stream, after everything enqueued on the main one so far"""
-            ops.stream_wait(side_h, main)
-            with ops.on_stream(side_h), lane[1]:
-                ops.set_gemm_mode(core)
-                fn()
-
-        # A caller that issues the step as a unit and replays it (lirec_amd.graph.RecordedTrainStep, single GPU, gradients in overwrite
-        # mode) leaves the FIRST side stream un-joined at the end of backward: the heads' and the gate's weight gradients -- and,
-        # behind them on that stream, their Adam launch and the next step's staging of the gate's weights -- then run on into the
-        # next step's head (its staging pass is HBM-bound, the weight gradient MFMA-bound) instead of the main chain waiting for
-        # them at the end of this one.  What the next step reads of them it reads behind the wait in front of its gate forward
-        # (`w_side`, _run_forward); join_side_streams() is the explicit join (eval forwards, state_dict, release()).
-        # (... and only while the side stream also carries the first bucket's update -- opt.adam_on_side_stream: an update issued on
-        #  THIS stream would read gradients the un-joined stream is still writing -- and the forward of this step was a training
-        #  forward under the same flag, i.e. the next replay's forward joins: _run_forward, `deferred_join`)
-        defer = bool(getattr(self, '_defer_side_join', False)) and lane is not None and self._has_gate and self._has_ints \
-            and self.grad_sync is None and st.get('train', False) and bool(getattr(opt, 'adam_on_side_stream', True)) \
-            and bool(getattr(opt, 'wgrad_side_stream', True))
+        # (a replayed step leaves lane 0 un-joined: its weight gradients and their Adam launch run on into the next step's head)
+        defer = lanes.may_defer(lane, self._has_gate, self._has_ints, self.grad_sync is not None, st.get('train', False))
 
         def join_side():
             if lane is not None and not defer:
@@ -898,11 +843,9 @@ class _HotPathModule(nn.Module):
         args_i = args_c = None
         # the first-layer parameters' update folded into the launch that finishes their gradients (armed by the optimiser for a
         # step issued as a unit: FusedAdam.arm_first_layer_update): both heads' tails must be the ONE gemm_p2 launch
-        adam = self.__dict__.pop('_dw1_adam', None)
-        # (... reading its hyper-parameters from this device row -- FusedAdam with device_hyper -- or, None, carrying them by value)
-        hyper_row = self.__dict__.pop('_dw1_hyper_row', None)
-        # (... or one row per first-layer parameter: (table, [(offset, length, group)]) -- the first layers span several groups)
-        hyper_map = self.__dict__.pop('_dw1_hyper_map', None)
+        # (... reading its hyper-parameters from a device row -- FusedAdam with device_hyper --, from one row per first-layer
+        #  parameter: (table, [(offset, length, group)]) -- the first layers span several groups --, or carrying them by value)
+        adam, hyper_row, hyper_map = lanes.take_fold()
         if want_dx:
             adam = None          # (the features' gradient reads the first-layer weights after the tail: no update folded into it)
         if adam is not None and not (has_i and has_c and pieces is None and st.get('planes_i') is not None
@@ -910,7 +853,7 @@ class _HotPathModule(nn.Module):
             adam = None
         if adam is not None and not ('tail_i' in need and 'tail_c' in need):
             adam = None          # (a frozen first layer: the optimiser does not arm the fused update then -- belt and braces)
-        self._dw1_adam_applied = adam is not None
+        lanes.fold_applied = adam is not None
         work_i = has_i and ('dW2_i' in need or 'tail_i' in need)
         work_c = has_c and ('dW2_c' in need or 'tail_c' in need)
         def head_args(head, H1, planes, **kw):
@@ -939,11 +882,11 @@ class _HotPathModule(nn.Module):
         forked2 = False
         if not ('dW2_i' in need or 'dW2_c' in need):
             # (both second layers frozen: their lane is not forked.  The first side stream is still put behind this point of the
-            #  main one -- the wait on_side2 makes for it: the first bucket's update runs there, after the gate's data gradient)
+            #  main one -- the wait lane 1's fork makes for it: the first bucket's update runs there, after the gate's data gradient)
             if lane2 is not None and (heads_w or 'gate_dW' in need):
                 ops.stream_wait(side_h, main)
         elif lane2 is not None:
-            on_side2(lambda: ops.embed_bwd_heads(heads_w2, 1))         # second-layer weight gradients beside the rest of the chain, on their own stream
+            on_side(lambda: ops.embed_bwd_heads(heads_w2, 1), lane2)         # second-layer weight gradients beside the rest of the chain, on their own stream
             forked2 = True
         elif lane is not None:
             on_side(lambda: ops.embed_bwd_heads(heads_w2, 1))
@@ -990,9 +933,8 @@ class _HotPathModule(nn.Module):
         join_side()
         if self.grad_sync is not None:
             self.grad_sync.bucket_ready(2)
-        # (for the optimiser: this backward left the side stream ordered behind every reader of the first bucket's parameters)
-        self._side_after_backward = (side_h, main) if (lane is not None and has_g and has_i) else None
-        self._side_unjoined = defer
+        lanes.after_backward = (side_h, main) if (lane is not None and has_g and has_i) else None
+        lanes.unjoined = defer
         return dX, dClip, dTrack
 
     # ---- first-layer weights kept in the q32b form (lirec_embed_fwd_args::W1q) -------------------------------------------------
@@ -1040,11 +982,8 @@ class _HotPathModule(nn.Module):
         self._w1q_valid = False
 
     def join_side_streams(self):
-        """The current stream waits for the weight-gradient side stream (the first bucket's Adam launch may still be running there
-        when a replayed step returns: _run_backward).  Called wherever the parameters are read outside a training step."""
-        if getattr(self, '_side_unjoined', False) and getattr(self, '_sides', None) and 0 in self._sides:
-            ops.stream_wait(ops.current_stream_handle(), C.c_void_p(self._sides[0][0].cuda_stream))
-        self._side_unjoined = False
+        """The current stream waits for what a replayed step left running on lane 0: wherever parameters are read outside a step."""
+        self.lanes.join()
 
     def state_dict(self, *a, **k):
         self.join_side_streams()
@@ -1052,10 +991,9 @@ class _HotPathModule(nn.Module):
 
     def named_parameters(self, *a, **k):
         """(``parameters()`` goes through here too.)  A replayed train step returns with the first bucket's update possibly still
-        running on the side stream (`_side_unjoined`): whoever asks for the parameters is about to read them -- or their ``.grad`` --
-        with ordinary torch ops on the current stream (the reference's own create_model prints ``param.norm()``, mlp/model.py:603-608;
-        gradient clipping; an EMA), so the current stream joins first.  One flag test when nothing is pending.  Parameter objects a
-        caller kept from BEFORE the replays are not covered: ``RecordedTrainStep.flush()`` is the explicit join."""
+        running on lane 0: whoever asks for the parameters is about to read them -- or their ``.grad`` -- with ordinary torch ops on
+        the current stream (the reference's own create_model prints ``param.norm()``, mlp/model.py:603-608), so it joins first.  One
+        flag test when nothing is pending.  Parameter objects kept from BEFORE the replays: ``RecordedTrainStep.flush()``."""
         self.join_side_streams()
         return super().named_parameters(*a, **k)
 
@@ -1063,7 +1001,7 @@ class _HotPathModule(nn.Module):
         """For a caller that writes parameters by hand (an EMA swap, weight clipping) on the current stream: the q32b shadow of the
         first-layer weights is stale, and the next forward's staging of the gate's weights must be ordered behind this stream."""
         self._w1q_valid = False
-        self._bucket0_on_side = False
+        self.lanes.params_written()
 
     def _w1q_of(self, mods, planes):
         if getattr(self, '_w1q_valid', False) and getattr(self, '_w1q_mode', None) != ops.get_gemm_mode():
@@ -1071,21 +1009,6 @@ class _HotPathModule(nn.Module):
         if not (getattr(self, '_w1q_valid', False) and self.training and planes is not None):
             return None
         return [self._w1q[a + '.weight'] for a, _ in mods]
-
-    def _take_side_after_backward(self):
-        """(side stream handle, end of the first gradient bucket) when the backward that just ran put the heads' and the gate's
-        weight gradients on the side stream and the caller is on the stream that backward ran on; None otherwise.  One-shot."""
-        tag, self._side_after_backward = getattr(self, '_side_after_backward', None), None
-        if tag is None or not getattr(opt, 'wgrad_side_stream', True) or not getattr(opt, 'adam_on_side_stream', True):
-            return None
-        side_h, main = tag
-        if ops.current_stream_handle().value != main.value:
-            return None
-        from .parallel import bucket_ranges
-        if getattr(self, '_bucket0_end', None) is None:
-            ranges, stages = bucket_ranges(self._offsets)
-            self._bucket0_end = ranges[0][1] if (stages and stages[0] == 0 and len(ranges) > 1) else 0
-        return (side_h, self._bucket0_end) if self._bucket0_end > 0 else None
 
     def _call_hot_path(self, X, mask, n, R, clamp, tables=(None, None)):
         self._begin_forward()

@@ -105,6 +105,7 @@ class FusedAdam(torch.optim.Optimizer):
     def __init__(self, model, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5, max_grad_norm=None, param_groups=None,
                  device_hyper=None, amsgrad=False, decoupled_weight_decay=False, skip_nonfinite=False, ema_decay=None):
         self.model = model
+        self.lanes = getattr(model, 'lanes', None)       # (lirec_amd.lanes.StepLanes; None: every update on the caller's stream)
         params = list(model.parameters())
         self._names = [n for n, _ in model.named_parameters()]        # (in the order of model._plist)
         if amsgrad:
@@ -139,7 +140,6 @@ class FusedAdam(torch.optim.Optimizer):
         self._step = 0
         self.grad_scale = 1.0          # 1/world_size after a summing all-reduce
         self._step_dev = None          # device int64[1]: the step kept on the GPU (lirec_amd.graph)
-        self._step_side_dev = None     # device int64[1]: the same as the weight-gradient side stream counts it (step(): side update)
         self._lag = {}                 # parameter name -> updates it sat out frozen (missing = 0): state[p]['step'] = _step - lag
         self.max_grad_norm = max_grad_norm      # None / 0: no clipping; settable between steps (a recorded step is recorded again)
         self._clip_out = None          # device float32[4]: (clip coefficient, gradient norm, skipped?, -) of the last clipped / guarded step
@@ -185,8 +185,7 @@ class FusedAdam(torch.optim.Optimizer):
             return
         if ops.CommandList.mark() >= 0:
             raise RuntimeError('FusedAdam: the EMA shadow cannot be made while a step is being recorded; set ema_decay before')
-        if hasattr(self.model, 'join_side_streams'):
-            self.model.join_side_streams()
+        self._join_side()
         old = getattr(self, '_ema_views', None) if self._ema is not None else None
         self._ema = flat.clone()
         self._ema_views = {}
@@ -224,8 +223,7 @@ class FusedAdam(torch.optim.Optimizer):
         self._ema_not_recording('ema_reset()')
         self._ensure_state()
         self._ensure_ema(self.model.flat_params(), force=True)
-        if hasattr(self.model, 'join_side_streams'):
-            self.model.join_side_streams()
+        self._join_side()
         self._ema.copy_(self.model.flat_params())
         self._ema_done, self._ema_calls, self._ema_skip_base = 0, 0, self.skipped_total()
 
@@ -262,8 +260,7 @@ class FusedAdam(torch.optim.Optimizer):
         missing = [n for n in self.model._offsets if n not in sd]
         if missing:
             raise KeyError('FusedAdam.load_ema_state_dict: missing %s' % ', '.join(missing))
-        if hasattr(self.model, 'join_side_streams'):
-            self.model.join_side_streams()
+        self._join_side()
         for n, (off, k) in self.model._offsets.items():
             t = torch.as_tensor(sd[n])
             if t.numel() != k:
@@ -288,10 +285,10 @@ class FusedAdam(torch.optim.Optimizer):
                           'call optimizer.consolidate_state() on EVERY rank first (a collective)', RuntimeWarning, stacklevel=3)
 
         def about_to_write():
-            if hasattr(self.model, 'join_side_streams'):
-                self.model.join_side_streams()
+            self._join_side()
             self.model._w1q_valid = False
-            self.model._bucket0_on_side = False
+            if self.lanes is not None:
+                self.lanes.params_written()
         with torch.no_grad():
             about_to_write()
             backup = flat.clone()
@@ -302,6 +299,10 @@ class FusedAdam(torch.optim.Optimizer):
             with torch.no_grad():
                 about_to_write()
                 flat.copy_(backup)
+
+    def _join_side(self):
+        if self.lanes is not None:
+            self.lanes.join()
 
     def _lerp(self, flat, a, b):
         """the average of stretch [a, b) follows the stretch's update, on the stream current here; guarded on the guarded route"""
@@ -384,14 +385,13 @@ class FusedAdam(torch.optim.Optimizer):
         """the streams that issue Adam launches, as {role: raw handle or None (= the current one)}"""
         m = self.model
         roles = {'main': None}
-        # (the side stream only where step() can put an update on it -- opt.adam_on_side_stream, model._take_side_after_backward --:
-        #  no lane is made, and no table written, for a run that never updates there)
+        # (the side stream only where step() can put an update on it: no lane made, no table written, for a run that never does)
         lane = None
-        if hasattr(m, '_wgrad_lane') and m.flat_params().is_cuda and getattr(opt, 'adam_on_side_stream', True) \
+        if self.lanes is not None and m.flat_params().is_cuda and getattr(opt, 'adam_on_side_stream', True) \
                 and getattr(getattr(m, 'grad_sync', None), 'world', 1) <= 1:
-            lane = m._wgrad_lane()
+            lane = self.lanes.wgrad(m.flat_params().device)
         if lane is not None:
-            roles['side'] = C.c_void_p(lane[0].cuda_stream)
+            roles['side'] = lane.handle
         early = getattr(getattr(m, 'grad_sync', None), '_launch_stream', None)
         if early is not None:
             roles['early'] = C.c_void_p(early.cuda_stream)
@@ -441,7 +441,8 @@ class FusedAdam(torch.optim.Optimizer):
             old = {id(p): self.state.get(p) for p in self.model.parameters()}
             self._m = torch.zeros_like(flat)
             self._v = torch.zeros_like(flat)
-            self._side_ticket = torch.zeros(1, dtype=torch.int32, device=flat.device)      # (lirec_adam_step_counted's arrival counter)
+            if self.lanes is not None:
+                self.lanes.side_ticket = torch.zeros(1, dtype=torch.int32, device=flat.device)      # (lirec_adam_step_counted's arrival counter)
             if self._guard_flags is not None:
                 self._fold_skipped()   # (the count of skipped steps does not outlive its buffer)
             self._clip_out = None
@@ -607,7 +608,7 @@ class FusedAdam(torch.optim.Optimizer):
         m = self.model
         if self._step_dev is None:
             self.fold_if_due()
-        if getattr(m, 'grad_sync', None) is not None or not hasattr(m, 'first_layer_range'):
+        if getattr(m, 'grad_sync', None) is not None or self.lanes is None or not hasattr(m, 'first_layer_range'):
             return False
         if self._clip_max() is not None or self.skip_nonfinite:
             return False          # (the norm needs the finished first-layer gradients: they are updated with the rest, clipped)
@@ -636,16 +637,10 @@ class FusedAdam(torch.optim.Optimizer):
                  grp['weight_decay'], self.grad_scale, self._step_dev)
         lo, hi, n_params = m.first_layer_range()
         valid = bool(getattr(m, '_w1q_valid', False)) and getattr(m, '_w1q_mode', None) == ops.get_gemm_mode()
-        m._dw1_adam = ops.fused_adam_args(flat, g, self._m, self._v, n_params, *hyper,
-                                          wq=m._w1q_buf if valid else None, wq_first=m._w1q_first if valid else 0)
-        if row is not None:
-            m._dw1_hyper_row = row          # (the five values above are then ignored: lirec_set_adam_hyper_row)
-        else:
-            m.__dict__.pop('_dw1_hyper_row', None)
-        if hmap is not None:
-            m._dw1_hyper_map = hmap         # (... and each parameter reads the row of its group: lirec_set_adam_hyper_map)
-        else:
-            m.__dict__.pop('_dw1_hyper_map', None)
+        # (with ``row`` the five values above are ignored: lirec_set_adam_hyper_row; with ``hmap`` each parameter reads the row of its
+        #  group: lirec_set_adam_hyper_map)
+        self.lanes.fold = (ops.fused_adam_args(flat, g, self._m, self._v, n_params, *hyper, wq=m._w1q_buf if valid else None,
+                                               wq_first=m._w1q_first if valid else 0), row, hmap)
         return True
 
     def first_layer_fold_ranges(self):
@@ -801,7 +796,7 @@ class FusedAdam(torch.optim.Optimizer):
         args = (max(self._step, 1), grp['lr'], grp['betas'][0], grp['betas'][1], grp['eps'], grp['weight_decay'],
                 self.grad_scale, self._step_dev)
         flat = self.model.flat_params()
-        sync = self.model.grad_sync
+        sync, lanes = self.model.grad_sync, self.lanes
         self._clip_now = self._clip_max()
         # (skip_nonfinite: the clipped route, whether or not a bound is set -- `clip` from here on means "that route")
         self._guard_now = guard = bool(self.skip_nonfinite)
@@ -815,7 +810,8 @@ class FusedAdam(torch.optim.Optimizer):
         if sync is not None and sync.world > 1:
             if getattr(opt, 'strict', False) and hasattr(sync, 'check_frozen_set'):
                 sync.check_frozen_set(self._flags(), self.group_membership() if len(self.param_groups) > 1 else ())
-            self.model._bucket0_on_side = False
+            if lanes is not None:
+                lanes.bucket0_on_side = False
             if clip:
                 self._step_parallel_clipped(sync, flat, g, args)
                 if self._step_dev is None:
@@ -851,7 +847,7 @@ class FusedAdam(torch.optim.Optimizer):
             # (the first layers' bucket was updated by the backward itself -- arm_first_layer_update -- or: an update from here
             #  does not write the q32b shadow of the first-layer weights, which is stale from now on)
             skip = []
-            if self.model.__dict__.pop('_dw1_adam_applied', False):
+            if lanes is not None and lanes.take_fold_applied():
                 skip.append((self.model.first_layer_range()[0], flat.numel()))
                 # (the backward's fold ran on this stream before step() was entered: the range's average follows it here)
                 self._lerp(flat, *skip[0])
@@ -863,40 +859,34 @@ class FusedAdam(torch.optim.Optimizer):
             def update(lo, hi, role='main'):
                 for a, b in self._minus(lo, hi, skip):
                     self._update(flat, g, a, b, args, role=role)
-            side = self.model._take_side_after_backward() if hasattr(self.model, '_take_side_after_backward') else None
+            side = lanes.take_after_backward(self.model._offsets) if lanes is not None else None
             if clip:
                 # Clipped: the coefficient needs EVERY gradient finished, so nothing is updated beside the tail of backward -- the side
                 # streams are joined (below: the no-side branch), the norm is taken over the trainable ranges (frozen slices of the
                 # buffer hold whatever a shared launch left there) and the whole update follows on this stream, clipped
                 side = None
-            # (for the next forward: were the heads' / the gate's weights updated on the weight-gradient side stream?)
-            self.model._bucket0_on_side = side is not None
+            if lanes is not None:
+                lanes.bucket0_on_side = side is not None
             if side is not None:
-                # Single GPU with the weight-gradient side stream: the heads' and the gate's gradients (the first bucket of the
-                # flat buffer, 53 % of the parameters) were finished on the side stream long before the main stream is through
-                # with the layer-1 weight gradients, and that stream is ordered behind every main-stream kernel that reads
-                # these parameters (model._run_backward forks it after the gate's data gradient).  Their update runs there,
-                # beside the MFMA-bound tail of backward; only the embedding buckets are updated at the end of the chain.
+                # Single GPU with lane 0: the heads' and the gate's gradients (bucket 0, 53 % of the parameters) were finished there
+                # long before the main stream is through with the layer-1 weight gradients, and the lane is ordered behind every
+                # main-stream reader of these parameters.  Their update runs there, beside the MFMA-bound tail of backward.
                 side_h, hi0 = side
-                # (ordered behind everything enqueued on this stream so far: a caller that touches the gradients between
-                #  backward() and step() -- clipping, inspection -- must not race with the update; one event, ~6 us.  That also
-                #  puts the update behind this stream's own tail of backward -- the first-layer weight gradients, 0.19 ms that have
-                #  nothing to do with this bucket -- so a caller that issues the step as a unit (lirec_amd.graph, `atomic_step`) skips it)
-                if not getattr(self, 'atomic_step', False):
+                # (behind everything enqueued on this stream so far -- a caller may touch the gradients between backward() and step();
+                #  one event, ~6 us -- unless the step is issued as a unit: the wait would also put the update behind 0.19 ms of tail)
+                if not lanes.atomic_step:
                     ops.stream_wait(side_h, ops.current_stream_handle())
                 with ops.on_stream(side_h):
-                    if self._step_dev is not None and self._step_side_dev is not None:
-                        # the step as THIS stream counts it: the shared counter may be advanced by the next step's first launch
-                        # while this update is still running (lirec_amd.graph, `defer`).  The counter holds the steps this stream
-                        # has COMPLETED; the update launch reads it (+ 1) and its last workgroup advances it (round 6: the
-                        # one-thread counter launch that used to stand in front of it waited 43 us on average for a CU)
-                        # (stretches with nothing trainable issue no launch; the counter is advanced all the same)
+                    if self._step_dev is not None and lanes.step_side_dev is not None:
+                        # the step as THIS lane counts it ("Lanes": step_side_dev): the update launch reads the completed
+                        # steps (+ 1), its last workgroup advances them; stretches with nothing trainable issue no launch, the
+                        # counter is advanced all the same
                         stretches = self._minus(0, hi0, skip)
                         rs = [(a, b) for a, b in stretches if self._all_live or self.trainable_ranges(a, b)]
                         if not rs:
-                            ops.counter_add(self._step_side_dev, [1])
+                            ops.counter_add(lanes.step_side_dev, [1])
                         for i, (a, b) in enumerate(rs):
-                            self._update(flat, g, a, b, args, counted=(self._step_side_dev, self._side_ticket), last=(i == len(rs) - 1),
+                            self._update(flat, g, a, b, args, counted=(lanes.step_side_dev, lanes.side_ticket), last=(i == len(rs) - 1),
                                          role='side')
                         for a, b in stretches:            # (nothing trainable, no launch above: the average moves all the same)
                             if (a, b) not in rs:
@@ -904,17 +894,14 @@ class FusedAdam(torch.optim.Optimizer):
                     else:
                         update(0, hi0, 'side')
                 update(hi0, flat.numel())
-                # (the step ends when the side stream's share has -- unless the caller replays the step and leaves that stream to run
-                #  on into the next one: model._run_backward, `_side_unjoined`)
-                if not getattr(self.model, '_side_unjoined', False):
+                # (the step ends when lane 0's share has -- unless a replayed step leaves it un-joined: StepLanes.may_defer)
+                if not lanes.unjoined:
                     ops.stream_wait(ops.current_stream_handle(), side_h)
             else:
-                # (no update on the side stream after all -- another caller stream, opt.adam_on_side_stream off: whatever a backward
-                #  left running there writes the gradients this update reads; join first.  A no-op unless a step was left un-joined.)
-                if hasattr(self.model, 'join_side_streams'):
-                    self.model.join_side_streams()
-                if self._step_dev is not None and self._step_side_dev is not None:
-                    ops.counter_add(self._step_side_dev, [1])      # (kept in step with the shared counter whichever path a step takes)
+                # (no update on lane 0 after all: whatever a backward left running there writes the gradients this update reads)
+                self._join_side()
+                if self._step_dev is not None and lanes is not None and lanes.step_side_dev is not None:
+                    ops.counter_add(lanes.step_side_dev, [1])      # (kept in step with the shared counter whichever path a step takes)
                 if clip:
                     if skip:
                         # (max_grad_norm was set between arm_first_layer_update() and this step: the backward has already applied
@@ -1011,8 +998,7 @@ class FusedAdam(torch.optim.Optimizer):
 
     def state_dict(self):
         self._ensure_state()
-        if hasattr(self.model, 'join_side_streams'):
-            self.model.join_side_streams()       # (a replayed step may have left the first bucket's update running on the side stream)
+        self._join_side()       # (a replayed step may have left the first bucket's update running on the side stream)
         self._sync_state_steps()
         sync = getattr(self.model, 'grad_sync', None)
         if sync is not None and sync.sharded and sync.real_world > 1 and getattr(self, '_consolidated_at', None) != self._step:

@@ -377,7 +377,7 @@ def test_two_groups_with_a_parameter_frozen_for_a_step(flagged, route):
             optim.step()
             torch.cuda.synchronize()
             after = [_np(t) for t in TG._snap(model, optim)]
-            assert bool(model._bucket0_on_side) == (route == 'side'), 'the step took another route'
+            assert bool(model.lanes.bucket0_on_side) == (route == 'side'), 'the step took another route'
             _check_step(model, optim, before, grad, after, s, 'frozen-' + route, rs=rs)
             for fo, fk in where:
                 if s == 2:

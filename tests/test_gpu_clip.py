@@ -369,7 +369,7 @@ def test_fused_adam_clips_end_to_end(freeze):
             for a, b, what in zip(after, before, 'pmv'):
                 assert torch.equal(a[~live], b[~live]), (what, 'written outside the trainable elements')
             clipped.append(float(got_coef) < 1.0)
-            assert not model._bucket0_on_side
+            assert not model.lanes.bucket0_on_side
         assert clipped[0] and not clipped[2] and float(optim.clip_coef) == 1.0, clipped
     finally:
         config.reset()

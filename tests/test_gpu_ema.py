@@ -269,7 +269,7 @@ def _recorded(ema, swap_after=None, keyword=True):
             out['others'] = sum(1 for s, k in cmds if k != 0)
             lanes = {}
             out['commands'] = [(lanes.setdefault(s, len(lanes)), k) for s, k in cmds]
-            out['layout'] = (model._bucket0_end, model.first_layer_range()[0], model.flat_params().numel())
+            out['layout'] = (model.lanes.bucket0_end, model.first_layer_range()[0], model.flat_params().numel())
 
             def snap():
                 torch.cuda.synchronize()

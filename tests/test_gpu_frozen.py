@@ -345,7 +345,7 @@ def test_persistent_path_with_the_context_first_layer_frozen_is_a_one_head_launc
     torch.cuda.synchronize()
     g_ref = {n: p.grad.detach().clone() for n, p in ref_m.named_parameters()}
     model, loss, optim, batch = _persistent('L1_c')
-    assert optim.arm_first_layer_update() is False and getattr(model, '_dw1_adam', None) is None
+    assert optim.arm_first_layer_update() is False and model.lanes.fold is None
     flat0 = model.flat_params().detach().clone()
     ops.profile_enable(True)
     try:
@@ -355,7 +355,7 @@ def test_persistent_path_with_the_context_first_layer_frozen_is_a_one_head_launc
     finally:
         ops.profile_enable(False)
     assert model.last_layer1_planes and 'embed_dW1' in sites and 'embed_dW1_reduce' in sites and 'pool_bwd' not in sites, sorted(sites)
-    assert sites['embed_dW1']['launches'] == 1 and not getattr(model, '_dw1_adam_applied', False)
+    assert sites['embed_dW1']['launches'] == 1 and not model.lanes.fold_applied
     for n, p in model.named_parameters():
         o, k = model._offsets[n]
         if model.param_group_of(n) == 'L1_c':

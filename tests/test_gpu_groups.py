@@ -14,6 +14,8 @@ three step forms -- by value, step_dev, and counted on a side stream the stand-i
 
 The recorded command lists are compared as (stream, command kind) sequences: lirec_cmdlist_command gives no kernel symbol, so "the
 same kernels" is shown by the same bits on every step together with the same sequence, as tests/test_gpu_clip.py does it."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -23,6 +25,7 @@ import clip_cases as CC
 import group_cases as GC
 from lirec_amd import _lib, config, ops
 from lirec_amd.config import opt
+from lirec_amd.lanes import Lane, StepLanes
 from lirec_amd.optim import FusedAdam
 
 pytestmark = pytest.mark.gpu
@@ -262,7 +265,7 @@ def _route(route, make, steps=STEPS, check=True, between=None):
                 rows = GC.rows_of(optim)
                 optim.step()
                 torch.cuda.synchronize()
-                assert bool(model._bucket0_on_side) == (route == 'side'), 'the step took another route'
+                assert bool(model.lanes.bucket0_on_side) == (route == 'side'), 'the step took another route'
                 out[s] = _snap(model, optim)
                 if check:
                     _check_step(model, optim, before, grad, out[s], s, route, rows=rows)
@@ -345,19 +348,15 @@ def test_three_groups_differ_from_one_group():
 # ---------------------------------------------------------------------------------------------------------------------------
 class ManyParams:
     """a stand-in for the model: 140 parameters of 5 .. 9 elements in one flat buffer, each on a multiple of 4 (what FusedAdam
-    reads of a model on its single-GPU routes, and nothing else).  `_side`: (raw stream handle, end of the stretch) -- what a
-    backward that left its first bucket to the side stream would hand step(), here the whole buffer."""
+    reads of a model on its single-GPU routes, and nothing else).  `lanes`: a real StepLanes around a lane of the stand-in's own;
+    `side_after_backward()` leaves what a backward that left its first bucket to the side stream would hand step(), here the
+    whole buffer."""
     grad_sync = None
-    _side = None
     _lane = None
 
-    def _take_side_after_backward(self):
-        return self._side
-
-    def _wgrad_lane(self, which=0):
-        if ManyParams._lane is None:
-            ManyParams._lane = (torch.cuda.Stream(), None)
-        return ManyParams._lane
+    def side_after_backward(self):
+        self.lanes.bucket0_end = self._n_flat
+        self.lanes.after_backward = (self.lanes.sides[0].handle, ops.current_stream_handle())
 
     def __init__(self, n=140):
         r = np.random.default_rng(2)
@@ -373,7 +372,10 @@ class ManyParams:
         self._flat = torch.from_numpy(vals).to(DEV)
         self._flat_grad = torch.zeros_like(self._flat)
         self._plist = [torch.nn.Parameter(self._flat[o:o + k]) for o, k in self._offsets.values()]
-        self._bucket0_on_side = False
+        if ManyParams._lane is None:
+            stream = torch.cuda.Stream()
+            ManyParams._lane = Lane(stream, None, ctypes.c_void_p(stream.cuda_stream))
+        self.lanes = StepLanes({0: ManyParams._lane})
 
     def parameters(self):
         return iter(self._plist)
@@ -390,7 +392,6 @@ class ManyParams:
 
 @pytest.mark.parametrize('form', ['by_value', 'step_dev', 'counted'])
 def test_more_than_64_ranges_take_two_calls(form):
-    import ctypes
     opt.adam_on_side_stream = True
     model = ManyParams()
     names = list(model._offsets)
@@ -410,8 +411,7 @@ def test_more_than_64_ranges_take_two_calls(form):
         if form == 'counted':
             # (the side route of step(): the update on the side stream, the step from that stream's own counter of completed steps,
             #  advanced by the LAST of the two calls only)
-            optim._step_side_dev = torch.zeros(1, dtype=torch.int64, device=DEV)
-            model._side = (ctypes.c_void_p(model._wgrad_lane()[0].cuda_stream), model._n_flat)
+            model.lanes.step_side_dev = torch.zeros(1, dtype=torch.int64, device=DEV)
         for step in (1, 2):
             model._flat_grad.copy_(torch.from_numpy(r.standard_normal(model._n_flat).astype(np.float32)))
             optim._ensure_state()
@@ -419,13 +419,15 @@ def test_more_than_64_ranges_take_two_calls(form):
             if form != 'by_value':
                 optim._step_dev.fill_(step)
             torch.cuda.synchronize()
+            if form == 'counted':
+                model.side_after_backward()
             optim.step()
             torch.cuda.synchronize()
             if form != 'by_value':
                 optim._step += 1
                 optim._advance_lags()
             if form == 'counted':
-                assert int(optim._step_side_dev) == step and int(optim._side_ticket) == 0 and model._bucket0_on_side
+                assert int(model.lanes.step_side_dev) == step and int(model.lanes.side_ticket) == 0 and model.lanes.bucket0_on_side
                 assert sorted(optim._tables) == ['main', 'side']
             after = _snap(model, optim)
             full = [(o, k, lag, grp) for o, k, lag, grp in GC.model_ranges(model, optim)]
@@ -672,7 +674,7 @@ def test_groups_with_max_grad_norm_1():
             _check_step(model, optim, before, grad, after, s, 'clipped', coef=got_coef)
             assert _same(_np(model.flat_grads(attach=False)), grad)
             clipped.append(got_coef < 1.0)
-            assert not model._bucket0_on_side              # (a clipped update runs whole on the caller's stream)
+            assert not model.lanes.bucket0_on_side        # (a clipped update runs whole on the caller's stream)
         assert any(clipped), 'max_grad_norm = 1 never clipped: the test shows nothing'
     finally:
         config.reset()
@@ -731,7 +733,7 @@ def test_folded_update_with_a_by_value_step_reads_the_row():
                 if arm:
                     assert optim.arm_first_layer_update() and optim._step_dev is None
                 lv.backward()
-                applied.append(bool(model.__dict__.get('_dw1_adam_applied', False)))
+                applied.append(bool(model.lanes.fold_applied))
                 optim.step()
                 torch.cuda.synchronize()
             return _snap(model, optim), applied

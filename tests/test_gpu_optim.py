@@ -371,7 +371,7 @@ def _run_route_once(route):
                 grad = model.flat_grads(attach=False).clone()
                 optim.step()
                 torch.cuda.synchronize()
-                assert bool(model._bucket0_on_side) == (route == 'side'), 'the step took another route'
+                assert bool(model.lanes.bucket0_on_side) == (route == 'side'), 'the step took another route'
                 assert optim._step == s
                 after = tuple(t.clone() for t in (model.flat_params(), optim._m, optim._v))
                 _check_step(route, s, before, grad, after, hyper)
@@ -381,7 +381,7 @@ def _run_route_once(route):
             # (did the backward of each step taken while recording fold the armed first-layer update in?  The flag is consumed by
             #  optim.step(): read it in front of it)
             applied, step0 = [], optim.step
-            optim.step = lambda *a, **k: (applied.append(bool(model.__dict__.get('_dw1_adam_applied', False))), step0(*a, **k))[1]
+            optim.step = lambda *a, **k: (applied.append(bool(model.lanes.fold_applied)), step0(*a, **k))[1]
             try:
                 g = RecordedTrainStep(model, loss, optim, batch, warmup=WARMUP)
             finally:
@@ -397,7 +397,7 @@ def _run_route_once(route):
                 # is updated by the launch that reduces its gradient (lirec_fused_adam, reading the step from the device), and
                 # the first bucket by the counted launch on the side stream
                 assert g.overwrite and g.fused and g.defer, (g.overwrite, g.fused, g.defer)
-                assert optim._step_dev is not None and optim._step_side_dev is not None and model._bucket0_on_side
+                assert optim._step_dev is not None and model.lanes.step_side_dev is not None and model.lanes.bucket0_on_side
                 assert optim._step == WARMUP + 1
                 out[optim._step] = tuple(t.clone() for t in (model.flat_params(), optim._m, optim._v))
                 for _ in range(REPLAYS):
@@ -408,7 +408,7 @@ def _run_route_once(route):
                     # the shared step counter and the side stream's own both stand at this step: the counted launch advanced its
                     # counter exactly once
                     assert g.state.tolist() == [model._fwd_train_calls, s, s], (g.state.tolist(), s)
-                    assert int(optim._side_ticket) == 0
+                    assert int(model.lanes.side_ticket) == 0
                     _shadow_is_current(model)      # (written by this replay's fused reduce from the weights it has just updated)
                     grad = model.flat_grads(attach=False).clone()       # (the fused reduce still stores the gradient)
                     after = tuple(t.clone() for t in (model.flat_params(), optim._m, optim._v))

@@ -3,7 +3,7 @@
 bench.py times `lirec_amd.graph.RecordedTrainStep` at B=64 clips x T=16 candidate pairs x (1+18) clips x 6912-d, dropout 0.3:
 the recorded command list, weight gradients OVERWRITING the flat gradient buffer (no zeroing pass; `lirec_set_grad_overwrite`:
 beta = 0, `dbias_set`, whole stream-K tiles stored), Adam's first bucket on the side stream without the tail wait
-(`FusedAdam.atomic_step`), three streams.  The other bench-shape tests run the eager loop (zeroed buffer, accumulate).  Here
+(`StepLanes.atomic_step`), three streams.  The other bench-shape tests run the eager loop (zeroed buffer, accumulate).  Here
 the replayed step itself is compared
 
   * with the eager loop at the same step: the flat gradient buffer and the parameters, BIT FOR BIT;
@@ -353,7 +353,7 @@ def test_parameters_loaded_between_replays():
     g.step()
     assert g._side_unordered, 'the recorded staging of Wg was expected to rely on the side stream\'s own order'
     m2.load_state_dict(sd)
-    assert not m2._bucket0_on_side and not m2._w1q_valid
+    assert not m2.lanes.bucket0_on_side and not m2._w1q_valid
     for _ in range(2):
         g.step()
     torch.cuda.synchronize()
@@ -497,9 +497,9 @@ def test_parameters_read_right_after_a_replay():
         assert g.defer
         while m2._fwd_train_calls < NSTEP:
             g.step()
-        assert m2._side_unjoined
+        assert m2.lanes.unjoined
         got = torch.stack([p.detach().norm() for p in m2.parameters()] + [p.grad.norm() for p in m2.parameters()])
-        assert not m2._side_unjoined
+        assert not m2.lanes.unjoined
         torch.cuda.synchronize()
     finally:
         with lane[1]:

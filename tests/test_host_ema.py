@@ -308,13 +308,13 @@ def test_swaps_and_resets_are_refused_inside_a_recording():
         optim.load_ema_state_dict({k: v * 2 + 1 for k, v in optim.ema_state_dict().items()})
         flat = model.flat_params()
         before, addr = flat.clone(), flat.data_ptr()
-        model._w1q_valid, model._bucket0_on_side = True, True
+        model._w1q_valid, model.lanes.bucket0_on_side = True, True
         with optim.ema_weights():
             assert torch.equal(flat, optim.ema) and not torch.equal(flat, before)
-            assert model._w1q_valid is False and model._bucket0_on_side is False
-            model._w1q_valid, model._bucket0_on_side = True, True
+            assert model._w1q_valid is False and model.lanes.bucket0_on_side is False
+            model._w1q_valid, model.lanes.bucket0_on_side = True, True
         assert torch.equal(flat.view(torch.int32), before.view(torch.int32)) and model.flat_params().data_ptr() == addr
-        assert model._w1q_valid is False and model._bucket0_on_side is False
+        assert model._w1q_valid is False and model.lanes.bucket0_on_side is False
         assert math.isfinite(float(flat.sum()))
     finally:
         config.reset()
