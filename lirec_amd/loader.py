@@ -85,6 +85,19 @@ def device_collate_in_force(dataset, device=None) -> bool:
         bool(getattr(opt, 'pieces_gather', True)) and bool(getattr(opt, 'pieces_q32b', False)) and bool(getattr(opt, 'layer1_planes', False))
 
 
+def make_loader(dataset, batch_size, shuffle=False, sampler=None):
+    """What ``training()``, ``testing()`` and ``predict()`` draw ``dataset`` with: ``ResidentLoader`` where ``device_collate_in_force``
+    (the batch buffer written on the device), ``ThreadedLoader`` for a dataset that brings its own ``collate_fn`` (PiecesDataset: piece
+    tables + index, built on ``opt.num_workers`` threads), else the stock ``DataLoader`` (mlp/train.py:33-37, mlp/test.py:18-22)."""
+    from .config import opt
+    kw = dict(batch_size=batch_size, shuffle=shuffle, sampler=sampler, drop_last=False)
+    if device_collate_in_force(dataset):
+        return ResidentLoader(dataset, device=opt.device, **kw)
+    if getattr(dataset, 'collate_fn', None) is not None:
+        return ThreadedLoader(dataset, num_workers=opt.num_workers, collate_fn=dataset.collate_fn, **kw)
+    return torch.utils.data.DataLoader(dataset, num_workers=opt.num_workers, **kw)
+
+
 class ResidentLoader:
     """Batches of a ``PiecesDataset(resident=True, emit='pieces')`` collated ON THE DEVICE: the stacked sample tables are uploaded
     once (``PiecesDataset.device_tables``), an epoch's sample ids go up in one copy, and every ``next()`` is one

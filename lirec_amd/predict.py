@@ -24,7 +24,7 @@ from scipy.special import expit
 
 from . import ops
 from .config import opt
-from .loader import ResidentLoader, ThreadedLoader, device_collate_in_force
+from .loader import make_loader
 
 
 class Predictions:
@@ -56,14 +56,7 @@ def pair_scores(rel_logits, hashes):
 
 def predict(dataset, model, top_k=5, batch_size=None):
     batch_size = opt.batch_size if batch_size is None else batch_size
-    if device_collate_in_force(dataset):                              # (opt.device_collate: the batch buffer written on the device)
-        loader = ResidentLoader(dataset, batch_size=batch_size, shuffle=False, drop_last=False, device=opt.device)
-    elif getattr(dataset, 'collate_fn', None) is not None:            # (piece tables + index, built on threads: lirec_amd/loader.py)
-        loader = ThreadedLoader(dataset, batch_size=batch_size, shuffle=False, num_workers=opt.num_workers, drop_last=False,
-                                collate_fn=dataset.collate_fn)
-    else:
-        loader = torch.utils.data.DataLoader(dataset, batch_size=batch_size, shuffle=False, num_workers=opt.num_workers,
-                                             drop_last=False)
+    loader = make_loader(dataset, batch_size)
     if opt.ints != 1:
         raise ValueError('predict() needs the interaction head (opt.ints == 1)')
     was_training = model.training

@@ -21,20 +21,9 @@ import torch
 
 from . import ops
 from .config import opt
-from .loader import ResidentLoader, ThreadedLoader, device_collate_in_force
+from .loader import make_loader
 from .metrics import Precision, RelationshipsAcc
 from .util import Averaging
-
-
-def _eval_loader(dataset, batch_size, sampler=None):
-    """the loader of an evaluation pass over ``dataset``, in order"""
-    if device_collate_in_force(dataset):                               # (opt.device_collate: the batch buffer written on the device)
-        return ResidentLoader(dataset, batch_size=batch_size, shuffle=False, sampler=sampler, drop_last=False, device=opt.device)
-    if getattr(dataset, 'collate_fn', None) is not None:              # (piece tables + index, built on threads: lirec_amd/loader.py)
-        return ThreadedLoader(dataset, batch_size=batch_size, shuffle=False, sampler=sampler, num_workers=opt.num_workers,
-                              drop_last=False, collate_fn=dataset.collate_fn)
-    return torch.utils.data.DataLoader(dataset, batch_size=batch_size, shuffle=False, sampler=sampler, num_workers=opt.num_workers,
-                                       drop_last=False)
 
 
 def testing(test_dataset, model, loss, total_iter=1, mode='val', train_start_time='', verbose=True):
@@ -46,7 +35,7 @@ def testing(test_dataset, model, loss, total_iter=1, mode='val', train_start_tim
     sharded = world > 1 and bool(getattr(opt, 'dp_shard_eval', True))
     sampler = parallel.ShardSampler(len(test_dataset), opt.batch_size, shuffle=False, pad=False) if sharded else None
     verbose = verbose and (rank == 0 or not sharded)
-    loader = _eval_loader(test_dataset, opt.batch_size, sampler)
+    loader = make_loader(test_dataset, opt.batch_size, sampler=sampler)
     losses = Averaging()
     model.eval()
     prec = Precision(inter2mgd=getattr(test_dataset, 'interidx2mgdidx', None), n_rels=opt.rels_dim, soft_gt=opt.soft_gt)
@@ -236,7 +225,7 @@ def clip_losses(dataset, model, loss, batch_size=None):
     Eval mode, no gradients, the loader selection of ``testing()``; singleton batches are NOT skipped (every clip gets its row); the
     values stay on the device until ONE copy at the end.  The model's mode and ``loss.keep_clip_losses`` are restored."""
     bs = int(batch_size or opt.batch_size)
-    loader = _eval_loader(dataset, bs)
+    loader = make_loader(dataset, bs)
     was_training, kept = model.training, loss.keep_clip_losses
     model.eval()
     loss.keep_clip_losses = True

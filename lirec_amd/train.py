@@ -12,6 +12,7 @@ evaluation is sharded and reduced (``lirec_amd.test.testing``), every rank takes
 """
 from __future__ import annotations
 
+import contextlib
 import copy
 import os
 import math
@@ -20,8 +21,10 @@ from datetime import datetime
 
 import torch
 
+from . import parallel
 from .config import opt
-from .loader import ResidentLoader, ThreadedLoader, device_collate_in_force
+from .features import CLIP_WEIGHT, PinnedPool
+from .loader import ResidentLoader, make_loader
 from .test import testing
 from .util import Averaging, ModelSaver, ema_entry, save_checkpoint
 
@@ -48,11 +51,8 @@ def _flush_losses(pending, losses, wait=True, finite_only=False):
             return
     take = pending[:k]
     dev = take[0][0].device
-    if dev.type == 'cuda' and not wait:
-        cs = _COPY_STREAMS.setdefault(dev, torch.cuda.Stream(device=dev))
-        with torch.cuda.stream(cs):
-            vals = torch.cat([v for v, _, _ in take]).cpu().tolist()
-    else:
+    on_side = dev.type == 'cuda' and not wait
+    with torch.cuda.stream(_COPY_STREAMS.setdefault(dev, torch.cuda.Stream(device=dev))) if on_side else contextlib.nullcontext():
         vals = torch.cat([v for v, _, _ in take]).cpu().tolist()
     for v, (_, n, _) in zip(vals, take):
         if finite_only and not math.isfinite(v):
@@ -93,23 +93,141 @@ def _all_ranks(flag: bool, world: int) -> bool:
     return bool(int(t.item()))
 
 
-def training(train_dataset, **kwargs):
-    from . import parallel
-    rank, world = parallel.world_info()
-    print = _print if rank == 0 else (lambda *a, **k: None)        # (one log, rank 0's)
-    start = datetime.now().strftime('%Y%m%d-%H%M%S')
-    print('set parameters and model, train start time: %s' % start)
-    model, loss, optimizer = kwargs['model'], kwargs['loss'], kwargs['optimizer']
-    val_dataset = kwargs.get('val_dataset', kwargs.get('test_dataset'))
-    test_dataset = kwargs.get('test_dataset') if 'val_dataset' in kwargs else None
-    sampler = kwargs.get('sampler')
-    # scheduler= any object with .step() (torch.optim.lr_scheduler.*), called after every optimiser step -- eager or replayed --
-    # (scheduler_every='step') or after every epoch ('epoch').  With FusedAdam(device_hyper=True) the recorded step follows it
-    # without being recorded again (FusedAdam.sync_hyper); by value every change of the learning rate records anew.
-    scheduler, scheduler_every = kwargs.get('scheduler'), kwargs.get('scheduler_every', 'step')
-    if scheduler_every not in ('step', 'epoch'):
-        raise ValueError('training(): scheduler_every must be \'step\' or \'epoch\', not %r' % (scheduler_every,))
-    sched_step = scheduler.step if (scheduler is not None and scheduler_every == 'step') else (lambda: None)
+class _Stepper:
+    """The optimiser step on every batch of one ``training()`` call, and what decides how it is taken.  A loader batch whose small
+    tensors all live in ONE buffer of a layout that repeats from batch to batch (a resident piece store: lirec_amd.features.collate,
+    static_layout) is stepped on by a RECORDED train step (lirec_amd.graph): the step's launches re-issued from C for ~0.1 ms of
+    host time instead of ~0.6 ms of Python -- the loop is host-bound otherwise.  Recorded once, on the fourth such batch in a row
+    (that batch's own, single step); a batch of another layout (the last, short one of an epoch) takes the eager step.
+    State: ``recorded`` (None: no step is) with its ``layout``, ``blob`` (input buffer), ``flags`` (the ``_flag_key`` it has baked
+    in) and ``released``; ``run`` batches in a row had ``last_layout``; ``run_barred``: a recording failed in this run, none is tried
+    before the layout changes; ``overwrite_ok``: the coverage check's verdicts by (layout, flag key) -- a flag flip (:49-51) may
+    route a parameter's gradient differently; ``dp_gave_up``: the ranks did not all record, and do not ask again."""
+
+    def __init__(self, model, loss, optimizer, world, loader, stats, to_device=None, say=_print):
+        self.model, self.loss, self.optimizer, self.world, self.loader, self.stats = model, loss, optimizer, world, loader, stats
+        self.to_device, self.say, self.binds = to_device, say, isinstance(loader, ResidentLoader)
+        self.recorded = self.layout = self.blob = self.flags = self.last_layout = None
+        self.released = self.run_barred = self.dp_gave_up = False
+        self.run, self.overwrite_ok = 0, {}
+
+    def _forget(self):                    # (a recipe flag or a hyper-parameter the step has baked in changed: eager until recorded again)
+        self.recorded.release()
+        self.recorded, self.run, self.run_barred = None, 0, False
+
+    def begin_epoch(self):
+        if self.recorded is not None and self.flags != _flag_key(self.optimizer):      # (a recipe flag changed, :49-51)
+            self._forget()
+
+    def before_draw(self):
+        """a device-collating loader is told before every draw where the recorded step's inputs are, so that a batch of that
+        layout is written there -- behind the previous replay on this stream -- and nowhere else"""
+        if self.binds and self.recorded is not None:
+            self.loader.bind(self.layout, self.blob)
+        elif self.binds:
+            self.loader.unbind()
+
+    def close(self):
+        if self.recorded is not None:
+            self.recorded.release()       # (back to the eager loop's way of passing the dropout key and Adam's step)
+
+    def step(self, i, batch):
+        """this batch's step: (loss value -- one element, on the device, not read --, labels); None: a one-label batch, skipped (:55-56)"""
+        lay = tuple(batch.get('_layout', ())) if isinstance(batch, dict) else ()
+        if self.recorded is not None and self.recorded.hyper_key(self.optimizer) != self.recorded._hyper:
+            self._forget()                # (the learning rate changed inside the epoch)
+        if self.recorded is not None and lay == self.layout:
+            return self._replay(batch), len(batch['labels'])
+        if self.to_device is not None:
+            batch = self.to_device(batch)     # (every small tensor of the batch in ONE host-to-device copy: features.collate)
+        n = len(batch['labels'])
+        if n == 1:
+            return None
+        if self.recorded is not None and not self.released:
+            self.recorded.release()       # an eager step in between: dropout key and Adam's step by value again
+            self.released = True
+        lval = self._record(batch, lay) if self.recorded is None and self._record_now(i, batch, lay) else None
+        if lval is None:
+            if lay and lay == self.last_layout:
+                self.run += 1
+            else:
+                self.run, self.run_barred = (1 if lay else 0), False
+            self.last_layout = lay
+            if self.recorded is None and lay and self.run == 3 and not self.run_barred and \
+                    (lay, _flag_key(self.optimizer)) not in self.overwrite_ok and _recordable(self.model, batch):
+                lval = self._checked(batch, lay)
+            else:
+                lval = self._eager(batch)
+        return lval, n
+
+    def _record_now(self, i, batch, lay) -> bool:
+        """the fourth batch in a row of its layout?  Data parallel: the ranks step in lock-step (ShardSampler: the same number of
+        batches of the same sizes), so iteration i is the same point of the program everywhere -- the decision is taken there, by all
+        ranks together, a few iterations per epoch at most (one tiny all-reduce each) until the step is recorded or given up"""
+        want = bool(lay and _recordable(self.model, batch) and self.run >= 3 and not self.run_barred and lay == self.last_layout)
+        if self.world > 1:
+            if self.dp_gave_up or not 3 <= i < 3 + _DP_RECORD_TRIES:
+                return False
+            want = _all_ranks(want, self.world)
+            if not want and i == 3 + _DP_RECORD_TRIES - 1:
+                self.dp_gave_up = True
+        return want
+
+    def _record(self, batch, lay):
+        """this batch's step, recorded: its loss value -- None when it could not be (RecordedTrainStep undoes its own state: device
+        counters detached, side stream joined; the eager step gives the same numbers).  Data parallel: a rank that recorded while another
+        could not releases its step -- replaying alone, its collectives would come from other positions -- the step taken all the same."""
+        from .graph import RecordedTrainStep
+        lval = None
+        try:
+            g = RecordedTrainStep(self.model, self.loss, self.optimizer, batch, warmup=0,
+                                  overwrite=self.overwrite_ok.get((lay, _flag_key(self.optimizer))))
+            self.recorded, self.layout, self.blob, self.flags, self.released = g, lay, batch['_dev_blob'], _flag_key(self.optimizer), False
+            lval = g.loss_out.clone()
+        except Exception as e:
+            self.say('recorded train step not used: %s' % str(e)[:160])
+            self.recorded, self.run_barred = None, True
+        if self.world > 1 and not _all_ranks(self.recorded is not None, self.world):
+            if self.recorded is not None:
+                self.recorded.release()
+            self.recorded, self.run_barred, self.dp_gave_up = None, True, True
+        return lval
+
+    def _replay(self, batch):
+        if self.released:
+            self.recorded.resume()
+            self.released = False
+        if batch.get('_dev_blob') is not self.blob:       # (else ResidentLoader wrote the batch into the step's inputs: nothing to copy)
+            self.blob.copy_(batch['_blob'], non_blocking=True)
+            PinnedPool.copied(batch.get('_slots'))
+            self.stats['input_copies'] += 1
+        self.stats['replays'] += 1
+        return self.recorded.step().clone()
+
+    def _checked(self, batch, lay):
+        """the step before the recorded one: this batch's own, with the gradient-overwrite coverage check on it -- the recorded step
+        may then skip the 76 MB zeroing pass and leave the side stream un-joined, like the benchmark's; same bits as the plain step"""
+        from .graph import checked_overwrite_step
+        ok, lv = checked_overwrite_step(self.model, self.loss, self.optimizer, batch)
+        self.overwrite_ok[(lay, _flag_key(self.optimizer))] = ok
+        return lv.detach().reshape(-1)[:1]
+
+    def _eager(self, batch):
+        out = self.model(batch)
+        if self.to_device is None and isinstance(batch, dict) and batch.get('_slots'):
+            PinnedPool.copied(batch['_slots'])       # (the model moved the pooled tables itself: hand the buffers back)
+        lv = self.loss(out, batch)
+        # the reference reads the loss back every iteration (``.item()``, :59): one host sync per step.  Here
+        # the values are kept on the device and read back where they are printed (every 10th iteration, epoch end).
+        lval = lv.detach().reshape(-1)[:1]
+        self.optimizer.zero_grad()
+        lv.backward()                     # a 0-d or one-element tensor, as mlp/train.py:62
+        self.optimizer.step()
+        return lval
+
+
+def _check_distributed(train_dataset, model, loss, sampler, world):
+    """(train_dataset, sampler) as the loop draws them -- this rank's shard sampler, class-balance weights --, or why the ranks do not add up"""
     if world > 1 and sampler is None:
         if getattr(model, 'grad_sync', None) is None:
             raise RuntimeError('training() under torch.distributed: wrap model / optimizer with lirec_amd.parallel.DataParallel first')
@@ -125,43 +243,83 @@ def training(train_dataset, **kwargs):
         from .data import class_balanced_weights, interaction_labels, with_clip_weights
         train_dataset = with_clip_weights(train_dataset, class_balanced_weights(interaction_labels(train_dataset), train_dataset.n_classes,
                                                                                 how=opt.class_balance))
-    from .features import CLIP_WEIGHT
     weighted = CLIP_WEIGHT in (getattr(train_dataset, '_stacked', None) or ()) or getattr(train_dataset, 'carries_clip_weights', False)
     if world > 1 and weighted and getattr(opt, 'clip_weight_norm', 'sum') == 'sum' and getattr(loss, '_dp', None) is None:
         # (a weighted mean divides by the GLOBAL batch's weight sums: the ranks' own sums differ even with even batches)
         raise RuntimeError('training() under torch.distributed with clip weights and clip_weight_norm=\'sum\': attach the loss -- '
                            'DataParallel(model, optimizer, loss=loss) -- so that its weighted mean is the global batch\'s')
-    batch_time, data_time, losses = Averaging(), Averaging(), Averaging()
-    guarded =lambda: bool(getattr(optimizer, 'skip_nonfinite', False))
+    return train_dataset, sampler
 
-    def eval_weights():
-        """opt.eval_ema: the val / test evaluations see the averaged weights (FusedAdam.ema_weights: swapped in by value, the
-        training weights restored bit for bit); otherwise nothing"""
-        if getattr(opt, 'eval_ema', False) and getattr(optimizer, 'ema_decay', None) is not None:
-            return optimizer.ema_weights()
-        import contextlib
-        return contextlib.nullcontext()
-    # (a dataset may bring its own collate_fn / pin_memory -- lirec_amd.features.PiecesDataset does: de-duplicated piece
-    #  tables + index instead of the tiled float64 block, built by `num_workers` THREADS (lirec_amd/loader.py says why);
-    #  the protocol of mlp/train.py:33-37 is otherwise unchanged)
-    # (opt.device_collate over a resident store: the batch buffer is written on the device from the sample ids -- lirec_amd/loader.py,
-    #  ResidentLoader -- and, once a step is recorded, straight into that step's input buffer)
-    on_device_loader = device_collate_in_force(train_dataset)
-    if on_device_loader:
-        loader = ResidentLoader(train_dataset, batch_size=opt.batch_size, shuffle=sampler is None, sampler=sampler, drop_last=False,
-                                device=opt.device)
-    elif getattr(train_dataset, 'collate_fn', None) is not None:
-        loader = ThreadedLoader(train_dataset, batch_size=opt.batch_size, shuffle=sampler is None, sampler=sampler,
-                                num_workers=opt.num_workers, drop_last=False, collate_fn=train_dataset.collate_fn)
-    else:
-        loader = torch.utils.data.DataLoader(train_dataset, batch_size=opt.batch_size, shuffle=sampler is None,
-                                             sampler=sampler, num_workers=opt.num_workers, drop_last=False)
+
+def _evaluate_and_keep(epoch, start, train_dataset, val_dataset, test_dataset, model, loss, optimizer, saver, rank, world):
+    """the periodic evaluation: the train set, then -- opt.test -- the validation set, whose metrics decide whether this epoch's
+    checkpoint is kept (and the test set evaluated).  COLLECTIVE under torch.distributed: every rank takes the same path."""
+    testing(train_dataset, model, loss, total_iter=epoch, mode='train', train_start_time=start)
+    if not (opt.test and val_dataset is not None):
+        return
+    # (opt.eval_ema: val / test see the averaged weights -- FusedAdam.ema_weights: swapped in by value, the live ones restored bit for bit)
+    averaged = getattr(opt, 'eval_ema', False) and getattr(optimizer, 'ema_decay', None) is not None
+    eval_weights = optimizer.ema_weights if averaged else contextlib.nullcontext
+    # (sharded + reduced under data parallelism: the same dict on every rank)
+    if getattr(opt, 'eval_ema', False) and hasattr(optimizer, 'consolidate_state') and world > 1:
+        optimizer.consolidate_state()         # (a collective: the shadow outside a rank's slices is stale otherwise)
+    with eval_weights():
+        check_val = testing(val_dataset, model, loss, total_iter=epoch, train_start_time=start, mode='val')
+    keep = saver.check(check_val) if rank == 0 else False
+    if world > 1:                             # rank 0 keeps the history the decision is taken against: its verdict, everywhere
+        keep = bool(parallel.all_reduce_counters({'keep': int(keep)})['keep'])
+    if not keep:
+        return
+    if hasattr(optimizer, 'consolidate_state'):
+        optimizer.consolidate_state()         # (a collective: every rank is here)
+    if rank == 0:
+        kept = {'epoch': epoch, 'state_dict': copy.deepcopy(model.state_dict()), 'optimizer': copy.deepcopy(optimizer.state_dict())}
+        ema = ema_entry(optimizer)
+        if ema is not None:
+            kept['ema'] = copy.deepcopy(ema)
+        saver.update(check_val, kept, epoch)
+    if test_dataset is not None:
+        with eval_weights():
+            testing(test_dataset, model, loss, total_iter=epoch, train_start_time=start, mode='test')
+
+
+def training(train_dataset, **kwargs):
+    rank, world = parallel.world_info()
+    print = _print if rank == 0 else (lambda *a, **k: None)        # (one log, rank 0's)
+    start = datetime.now().strftime('%Y%m%d-%H%M%S')
+    print('set parameters and model, train start time: %s' % start)
+    model, loss, optimizer = kwargs['model'], kwargs['loss'], kwargs['optimizer']
+    val_dataset = kwargs.get('val_dataset', kwargs.get('test_dataset'))
+    test_dataset = kwargs.get('test_dataset') if 'val_dataset' in kwargs else None
+    # scheduler= any object with .step() (torch.optim.lr_scheduler.*), called after every optimiser step -- eager or replayed --
+    # (scheduler_every='step') or after every epoch ('epoch').  With FusedAdam(device_hyper=True) the recorded step follows it
+    # without being recorded again (FusedAdam.sync_hyper); by value every change of the learning rate records anew.
+    scheduler, scheduler_every = kwargs.get('scheduler'), kwargs.get('scheduler_every', 'step')
+    if scheduler_every not in ('step', 'epoch'):
+        raise ValueError('training(): scheduler_every must be \'step\' or \'epoch\', not %r' % (scheduler_every,))
+    sched_step = scheduler.step if (scheduler is not None and scheduler_every == 'step') else (lambda: None)
+    train_dataset, sampler = _check_distributed(train_dataset, model, loss, kwargs.get('sampler'), world)
+    batch_time, data_time, losses = Averaging(), Averaging(), Averaging()
+    guarded = lambda: bool(getattr(optimizer, 'skip_nonfinite', False))
+    # (a dataset may bring its own collate_fn -- lirec_amd.features.PiecesDataset does --; with opt.device_collate over a resident store
+    #  the batch buffer is written on the device from the sample ids and, once a step is recorded, straight into that step's inputs)
+    loader = make_loader(train_dataset, opt.batch_size, shuffle=sampler is None, sampler=sampler)
     print('epochs: %s' % opt.epochs)
     saver = ModelSaver(path=opt.store_root) if rank == 0 else None      # (the kept checkpoints live on rank 0)
     epoch = -1
-    rec, last_layout, same_layout, ow_ok, dp_gave_up = None, None, 0, {}, False
     # (what the last call did with its recorded step: replays, host- or device-side copies into its input buffer, and the loader)
     stats = training.last = {'replays': 0, 'input_copies': 0, 'loader': loader}
+    to_dev = getattr(train_dataset, 'to_device', None) if str(opt.device).startswith('cuda') else None
+    stepper = _Stepper(model, loss, optimizer, world, loader, stats, to_device=to_dev, say=print)
+
+    def batches():
+        it = iter(loader)
+        while True:
+            stepper.before_draw()
+            try:
+                yield next(it)
+            except StopIteration:
+                return
     for epoch in range(opt.epochs):
         model.train()
         train_dataset.epoch = epoch
@@ -172,152 +330,22 @@ def training(train_dataset, **kwargs):
             opt.tr_sum_max_flag = True
         seen, end, t_epoch = 0, time.time(), time.time()
         pending = []
-        to_dev = getattr(train_dataset, 'to_device', None) if str(opt.device).startswith('cuda') else None
-        if rec is not None and rec['flags'] != _flag_key(optimizer):       # a recipe flag changed (:49-51): the recorded step is stale
-            rec['step'].release()
-            rec, same_layout = None, 0
-        def batches():
-            """the loader's batches; a device-collating loader is told before every draw where the recorded step's inputs are, so
-            that a batch of that layout is written there -- behind the previous replay on this stream -- and nowhere else"""
-            it = iter(loader)
-            while True:
-                if on_device_loader:
-                    if rec is not None:
-                        loader.bind(rec['layout'], rec['blob'])
-                    else:
-                        loader.unbind()
-                try:
-                    nxt = next(it)
-                except StopIteration:
-                    return
-                yield nxt
+        stepper.begin_epoch()
         for i, batch in enumerate(batches()):
             data_time.update(time.time() - end)
-            # A loader batch whose small tensors all live in ONE buffer of a layout that repeats from batch to batch (a resident
-            # piece store: lirec_amd.features.collate, static_layout) is stepped on by a RECORDED train step (lirec_amd.graph):
-            # the step's launches re-issued from C for ~0.1 ms of host time instead of ~0.6 ms of Python -- the loop is host-
-            # bound otherwise.  Recorded once, on the fourth such batch (that batch's own, single step); a batch of another
-            # layout (the last, short one of an epoch) takes the eager path below.
-            lay = tuple(batch.get('_layout', ())) if isinstance(batch, dict) else ()
-            if rec is not None and rec['step'].hyper_key(optimizer) != rec['step']._hyper:
-                rec['step'].release()             # (the learning rate changed inside the epoch: eager until the step is recorded again)
-                rec, same_layout = None, 0
-            if rec is not None and lay == rec['layout']:
-                from .features import PinnedPool
-                if rec.get('released'):
-                    rec['step'].resume()
-                    rec['released'] = False
-                if batch.get('_dev_blob') is rec['blob']:
-                    pass                          # (ResidentLoader wrote the batch into the step's inputs: nothing to copy)
-                else:
-                    rec['blob'].copy_(batch['_blob'], non_blocking=True)
-                    PinnedPool.copied(batch.get('_slots'))
-                    stats['input_copies'] += 1
-                stats['replays'] += 1
-                nlab = len(batch['labels'])
-                lval = rec['step'].step().clone()
-                sched_step()
-                ev = torch.cuda.Event()
-                ev.record()
-                pending.append((lval, nlab, ev))
-                batch_time.update(time.time() - end)
-                end = time.time()
-                seen += nlab
-                if i % 10 == 0 and i:
-                    _flush_losses(pending, losses, wait=False, finite_only=guarded())
-                    print('Epoch: [{0}][{1}/{2}]\tTime {bt.val:.3f} ({bt.avg:.3f})\tData {dt.val:.3f} ({dt.avg:.3f})\t'
-                          'Loss {ls.val:.4f} ({ls.avg:.4f})\t'.format(epoch, i, len(loader), bt=batch_time, dt=data_time, ls=losses))
+            took = stepper.step(i, batch)
+            if took is None:
                 continue
-            if to_dev is not None:
-                batch = to_dev(batch)             # (every small tensor of the batch in ONE host-to-device copy: features.collate)
-            labels = batch['labels']
-            if len(labels) == 1:                      # :55-56
-                continue
-            if rec is not None and not rec.get('released'):
-                rec['step'].release()             # an eager step in between: dropout key and Adam's step by value again
-                rec['released'] = True
-            want = bool(rec is None and lay and _recordable(model, batch) and same_layout >= 3 and lay == last_layout)
-            if world > 1 and rec is None and not dp_gave_up and 3 <= i < 3 + _DP_RECORD_TRIES:
-                # data parallel: the ranks step in lock-step (ShardSampler: the same number of batches of the same sizes), so
-                # iteration i is the same point of the program everywhere -- the decision is taken there, by all ranks together,
-                # a few iterations per epoch at most (one tiny all-reduce each) until the step is recorded or given up
-                want = _all_ranks(want, world)
-                if not want and i == 3 + _DP_RECORD_TRIES - 1:
-                    dp_gave_up = True
-            elif world > 1:
-                want = False
-            if want:
-                from .graph import RecordedTrainStep
-                g = None
-                try:
-                    g = RecordedTrainStep(model, loss, optimizer, batch, warmup=0, overwrite=ow_ok.get((lay, _flag_key(optimizer))))     # this batch's step, recorded
-                    rec = {'step': g, 'layout': lay, 'blob': batch['_dev_blob'], 'flags': _flag_key(optimizer)}
-                    lval = g.loss_out.clone()
-                except Exception as e:                # (a step that cannot be recorded stays eager: same numbers)
-                    # (RecordedTrainStep undoes its own state on a failed recording: device counters detached, side stream joined)
-                    print('recorded train step not used: %s' % str(e)[:160])
-                    rec, same_layout = None, -10 ** 9
-                if world > 1 and not _all_ranks(rec is not None, world):
-                    # (a rank could not record: every rank goes back to the eager loop -- a rank replaying alone would issue its
-                    #  collectives from other positions than the eager ranks)
-                    if rec is not None:
-                        rec['step'].release()
-                    rec, same_layout, dp_gave_up = None, -10 ** 9, True
-                    if g is not None:
-                        sched_step()              # (the step was taken all the same)
-                        ev = torch.cuda.Event()
-                        ev.record()
-                        pending.append((lval, len(labels), ev))
-                        seen += len(labels)
-                        continue
-                if rec is not None:
-                    sched_step()                  # (the recording took this batch's step)
-                    ev = torch.cuda.Event()
-                    ev.record()
-                    pending.append((lval, len(labels), ev))
-                    batch_time.update(time.time() - end)
-                    end = time.time()
-                    seen += len(labels)
-                    continue
-            same_layout = same_layout + 1 if (lay and lay == last_layout) else (1 if lay else 0)
-            last_layout = lay
-            if rec is None and lay and same_layout == 3 and (lay, _flag_key(optimizer)) not in ow_ok and _recordable(model, batch):
-                # the step before the one that gets recorded: this batch's own step, with the gradient-overwrite coverage check on
-                # it (graph.checked_overwrite_step) -- the recorded step may then skip the 76 MB zeroing pass and leave the side
-                # stream un-joined, like the benchmark's; same bits as the plain step
-                # (the verdict belongs to the layout AND the recipe flags / hyper-parameters it was taken under: a flag flip -- :49-51 --
-                #  may route a parameter's gradient differently)
-                from .graph import checked_overwrite_step
-                ow_ok[(lay, _flag_key(optimizer))], lv = checked_overwrite_step(model, loss, optimizer, batch)
-                lval = lv.detach().reshape(-1)[:1]
-                sched_step()
-                ev = torch.cuda.Event()
-                ev.record()
-                pending.append((lval, len(labels), ev))
-                batch_time.update(time.time() - end)
-                end = time.time()
-                seen += len(labels)
-                continue
-            out = model(batch)
-            if to_dev is None and isinstance(batch, dict) and batch.get('_slots'):
-                from .features import PinnedPool
-                PinnedPool.copied(batch['_slots'])       # (the model moved the pooled tables itself: hand the buffers back)
-            lv = loss(out, batch)
-            # the reference reads the loss back every iteration (``.item()``, :59): one host sync per step.  Here
-            # the values are kept on the device and read back where they are printed (every 10th iteration, epoch end).
-            lval = lv.detach().reshape(-1)[:1]
-            optimizer.zero_grad()
-            lv.backward()                 # a 0-d or one-element tensor, as mlp/train.py:62
-            optimizer.step()
+            lval, n = took
             sched_step()
             ev = None
             if lval.is_cuda:
                 ev = torch.cuda.Event()
                 ev.record()
-            pending.append((lval, len(labels), ev))
+            pending.append((lval, n, ev))
             batch_time.update(time.time() - end)
             end = time.time()
-            seen += len(labels)
+            seen += n
             if i % 10 == 0 and i:
                 _flush_losses(pending, losses, wait=False, finite_only=guarded())
                 print('Epoch: [{0}][{1}/{2}]\tTime {bt.val:.3f} ({bt.avg:.3f})\tData {dt.val:.3f} ({dt.avg:.3f})\t'
@@ -332,34 +360,11 @@ def training(train_dataset, **kwargs):
             print('skipped steps: %d' % optimizer.skipped_total())        # (one read per epoch)
         losses.reset()
         if epoch % opt.test_fr == 0:
-            testing(train_dataset, model, loss, total_iter=epoch, mode='train', train_start_time=start)
-            if opt.test and val_dataset is not None:
-                # (sharded + reduced under data parallelism: the same dict on every rank)
-                if getattr(opt, 'eval_ema', False) and hasattr(optimizer, 'consolidate_state') and world > 1:
-                    optimizer.consolidate_state()         # (a collective: the shadow outside a rank's slices is stale otherwise)
-                with eval_weights():
-                    check_val = testing(val_dataset, model, loss, total_iter=epoch, train_start_time=start, mode='val')
-                keep = saver.check(check_val) if rank == 0 else False
-                if world > 1:                         # rank 0 keeps the history the decision is taken against: its verdict, everywhere
-                    keep = bool(parallel.all_reduce_counters({'keep': int(keep)})['keep'])
-                if keep:
-                    if hasattr(optimizer, 'consolidate_state'):
-                        optimizer.consolidate_state()     # (a collective: every rank is here)
-                    if rank == 0:
-                        kept = {'epoch': epoch, 'state_dict': copy.deepcopy(model.state_dict()),
-                                'optimizer': copy.deepcopy(optimizer.state_dict())}
-                        ema = ema_entry(optimizer)
-                        if ema is not None:
-                            kept['ema'] = copy.deepcopy(ema)
-                        saver.update(check_val, kept, epoch)
-                    if test_dataset is not None:
-                        with eval_weights():
-                            testing(test_dataset, model, loss, total_iter=epoch, train_start_time=start, mode='test')
+            _evaluate_and_keep(epoch, start, train_dataset, val_dataset, test_dataset, model, loss, optimizer, saver, rank, world)
             print(getattr(opt, 'log_prefix', ''))
         if opt.save_model and opt.save_model_often and epoch % 30 == 0 and rank == 0:
             saver.save()
-    if rec is not None:
-        rec['step'].release()             # (back to the eager loop's way of passing the dropout key and Adam's step)
+    stepper.close()
     opt.resume_str = os.path.join(opt.store_root, '%d.pth.tar' % epoch)
     if opt.save_model:
         save_checkpoint(opt.resume_str, epoch, model, optimizer)
