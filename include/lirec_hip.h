@@ -174,6 +174,37 @@ int lirec_embed_fwd(const lirec_embed_fwd_args* a, lirec_stream_t stream);
  * heads -- small GEMMs on the candidate rows -- share one grouped launch. */
 int lirec_embed_fwd2(const lirec_embed_fwd_args* a, const lirec_embed_fwd_args* b, lirec_stream_t stream);
 
+/* Rows of a RESIDENT BLOCK STORE (added to ABI 124 without a new number: new exports and a new struct, index 21 of
+ * lirec_abi_sizeof).  A tiled dataset's feature rows are kept once on the device as ONE q32b matrix -- sample s owns storage rows
+ * [s * rows_per_clip, (s + 1) * rows_per_clip) -- and a batch is a list of sample ids.  With the setter armed, the X of the next
+ * call (x_q32 = 1) is that whole matrix and the call's block is "these n_clips samples of it": batch-local physical row p -- what
+ * the lirec_rowsel arithmetic yields -- names
+ *   storage row  (int64) clip_ids[p / rows_per_clip] * rows_per_clip + p % rows_per_clip.
+ * The staging launch writes that into the row lists layer 1 and its weight gradient gather through (nothing else changes: the
+ * backward reads the lists from `planes` and takes no setter; dropout counters keep the BATCH-LOCAL row id, as they do under row
+ * compaction, so a mask does not depend on where a sample is stored).  clip_ids is DEVICE memory, read by the kernel through the
+ * pointer each time it runs: a recorded launch sees the ids that are there when it is replayed.  TRUSTED, not checked on the
+ * device: every id in [0, store_rows / rows_per_clip); duplicates are fine.
+ * READ BY: lirec_embed_fwd and lirec_embed_fwd2, parts 0, 1 and 4 (with rows_staged the lists are in `planes` already: the value
+ * is checked and otherwise unused).  CONSUMED by the first such call the thread makes after the setter, whether it succeeds or
+ * not -- a forgotten one cannot leak into another model's forward; NULL switches it off.  Per calling thread.
+ * While armed the call returns LIREC_EINVAL, before any device call and also under the host-side dry run, when: clip_ids is NULL
+ * or misaligned, n_clips or rows_per_clip < 1; a head has x_q32 != 1, x_bf16 or `pieces`; the call would not take the gathered
+ * q32b path (shapes, planes, GEMM mode); parts is 2 or 3 or a head is empty; a head's `rows` is not a multiple of its per-sample
+ * row count (rows_per_clip without a selector; rows_per_clip / group_stride * group with one, rows_per_clip % group_stride == 0);
+ * n_clips * rows_per_clip differs from the physical rows of the call (rows, or rows / group * group_stride);
+ * store_rows > LIREC_FEATURE_ROWS_MAX.
+ * LIMIT: row lists are int32, so a store holds at most LIREC_FEATURE_ROWS_MAX = 2^31 - 32 rows (59 TB at 27 648 B a row: the
+ * card's memory is the bound that bites); every byte offset formed from a list entry is 64-bit (gemm_p2.hpp: p2_row_off and the
+ * per-lane / scalar addresses built on it), a store may pass 4 GiB. */
+#define LIREC_FEATURE_ROWS_MAX 2147483616LL
+typedef struct {
+  const int32_t* clip_ids;                /* device, [n_clips] */
+  int32_t n_clips, rows_per_clip;
+  int64_t store_rows;                     /* rows of the q32b matrix at X (multiple of 32) */
+} lirec_feature_rows;
+int lirec_set_feature_rows(const lirec_feature_rows* rows);
+
 /* Layer 1 on the UNIQUE feature pieces (second half).  A row of the loader's (B, T, R+1, D) block is
  * [clip piece (text | clip-visual) | track-1 piece | track-2 piece] and every piece is shared by many rows
  * (mixed_utils/classification_dataloader.py:336-349, :477-478, :531-533); the first Linear of a modality branch
@@ -200,6 +231,14 @@ typedef struct lirec_pieces_s {
  * lirec_q32b_bytes(rows, cols) bytes at dst (256-byte aligned). */
 int64_t lirec_q32b_bytes(int64_t rows, int64_t cols);
 int lirec_to_q32b(const float* src, int64_t ld_src, int64_t rows, int64_t cols, void* dst, lirec_stream_t stream);
+/* `rows` rows of src -> storage rows [dst_row0, dst_row0 + rows) of an EXISTING q32b matrix of dst_rows (a multiple of 32, at most
+ * LIREC_FEATURE_ROWS_MAX) x cols at dst: how a resident block store is filled in chunks and updated in place.  The same hi / lo
+ * halves lirec_to_q32b writes for those values, at any row offset (a row's 128-byte lines are independent: no read-modify-write,
+ * no other row is touched -- the caller zeroes a store's tail rows once).  src_f64 = 0: fp32 source; 1: float64, every value
+ * converted through fp32 exactly as lirec_cast_f64_f32 + lirec_to_q32b would.  ld_src in elements.  LIREC_EINVAL for NULL or
+ * misaligned pointers (dst 256 bytes, src its element size), cols % 32 != 0, ld_src < cols, a row range outside the matrix. */
+int lirec_q32b_write_rows(const void* src, int32_t src_f64, int64_t ld_src, int64_t rows, int64_t cols, void* dst, int64_t dst_row0,
+                          int64_t dst_rows, lirec_stream_t stream);
 /* The same to q16b (ABI 119): every value rounded to bf16 (nearest even), 32 x 32 blocks of 2 KiB, row r of a block = 64 B;
  * lirec_q16b_bytes(rows, cols) bytes at dst (256-byte aligned).  What lirec_embed_fwd_args::x_q32 = 2 reads. */
 int64_t lirec_q16b_bytes(int64_t rows, int64_t cols);
@@ -956,6 +995,13 @@ typedef struct {
 /* (pure host arithmetic; -1 for a negative count) */
 int64_t lirec_collate_workspace_bytes(int64_t n_clip_all, int64_t n_track_all);
 int lirec_collate_resident(const lirec_collate_args* a, lirec_stream_t stream);
+/* The field-row copy of lirec_collate_resident on its own (resident block store; index 23 of lirec_abi_sizeof = the field struct):
+ * for every field f < nf, dst row b = src row ids[b], b < B, byte for byte with the same 16 / 8 / 4 / 1-byte moves.  ONE launch.
+ * The batch's own id list is one more field (src = the table 0, 1, 2, ... as int32, row_bytes 4): it then sits at a fixed address
+ * of the batch buffer, where lirec_feature_rows::clip_ids of a recorded step reads it.  ids are trusted as above.  LIREC_EINVAL
+ * (also under the dry run) for B or nf negative, nf over LIREC_COLLATE_MAX_FIELDS, NULL fields with nf > 0, a row_bytes < 1, a
+ * misaligned ids; with B > 0: NULL ids, a field with a NULL src or dst.  B == 0 (or nf == 0): no launch, LIREC_OK. */
+int lirec_collate_fields(const int32_t* ids, int32_t B, const lirec_collate_field* fields, int32_t nf, lirec_stream_t stream);
 
 /* ---- feature assembly ---------------------------------------------
  * The reference's loader tiles every row of the (B, T, R+1, D) feature block on the host as
@@ -1001,7 +1047,7 @@ int lirec_dropout_mask(uint8_t* keep, int32_t rows, int32_t cols, const lirec_dr
 int lirec_version(void);
 /* sizeof() of ABI struct `which` (5 = eval; 0 embed_fwd, 1 embed_bwd, 2 margin_loss, 3 dropout,
  * 4 rowsel, 6 linear_fwd, 7 linear_bwd, 8 embed_dx, 9 embed_dx_indexed, 10 adam_range, 11 adam_hyper, 12 adam_group_range,
- * 13 eval_topk, 15 predict, 17 collate, 19 clip_weights; 14, 16 and 18 are not assigned) so a binding can verify its mirror;
+ * 13 eval_topk, 15 predict, 17 collate, 19 clip_weights, 21 feature_rows, 23 collate_field; 14, 16, 18, 20 and 22 are not assigned) so a binding can verify its mirror;
  * -1 if unknown */
 int lirec_abi_sizeof(int which);
 /* GEMM core: 0 exact f32-input MFMA   1 one-thread-per-output HIP GEMM (bring-up cross-check)

@@ -180,6 +180,14 @@ class CollateArgs(C.Structure):
                 ('fields', CollateField * COLLATE_MAX_FIELDS)]
 
 
+class FeatureRows(C.Structure):
+    """lirec_feature_rows: the batch's sample ids into a resident block store (lirec_set_feature_rows)"""
+    _fields_ = [('clip_ids', _vp), ('n_clips', _i32), ('rows_per_clip', _i32), ('store_rows', _i64)]
+
+
+FEATURE_ROWS_MAX = 2147483616  # LIREC_FEATURE_ROWS_MAX: the most rows a q32b store may hold (int32 row lists)
+
+
 class LirecError(RuntimeError):
     pass
 
@@ -220,6 +228,8 @@ _PROTOS = {
     'lirec_q16b_bytes': (_i64, [_i64, _i64]),
     'lirec_to_q16b': (_i32, [_vp, _i64, _i64, _i64, _vp, _vp]),
     'lirec_to_q16c': (_i32, [_vp, _i64, _i64, _i64, _vp, _vp]),
+    'lirec_q32b_write_rows': (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _vp]),
+    'lirec_set_feature_rows': (_i32, [C.POINTER(FeatureRows)]),
     'lirec_embed_fwd': (_i32, [C.POINTER(EmbedFwdArgs), _vp]),
     'lirec_embed_bwd': (_i32, [C.POINTER(EmbedBwdArgs), _vp]),
     'lirec_embed_fwd2': (_i32, [C.POINTER(EmbedFwdArgs), C.POINTER(EmbedFwdArgs), _vp]),
@@ -276,6 +286,7 @@ _PROTOS = {
     'lirec_predict_clips': (_i32, [C.POINTER(PredictArgs), _vp]),
     'lirec_collate_workspace_bytes': (_i64, [_i64, _i64]),
     'lirec_collate_resident': (_i32, [C.POINTER(CollateArgs), _vp]),
+    'lirec_collate_fields': (_i32, [_vp, _i32, C.POINTER(CollateField), _i32, _vp]),
     'lirec_cast_f64_f32': (_i32, [_vp, _vp, _i64, _vp]),
     'lirec_grid_pool': (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i64, _vp]),
     'lirec_rows_max': (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _vp]),
@@ -326,7 +337,8 @@ def lib():
                                                                                                       (10, AdamRange), (11, AdamHyper),
                                                                                                       (12, AdamGroupRange), (13, EvalTopkArgs),
                                                                                                       (15, PredictArgs), (17, CollateArgs),
-                                                                                                      (19, ClipWeights)]:
+                                                                                                      (19, ClipWeights), (21, FeatureRows),
+                                                                                                      (23, CollateField)]:
         if L.lirec_abi_sizeof(which) != C.sizeof(st):
             raise LirecError('ABI mismatch for %s: library %d bytes, binding %d bytes'
                              % (st.__name__, L.lirec_abi_sizeof(which), C.sizeof(st)))

@@ -724,6 +724,10 @@ struct StageSrc {
   int* srow[3]; const int* clip_rows; const int* track_rows; int zero_clip, zero_track;
   int x16;      // the block at X is bf16 (row-major, ldx in elements): its rows are staged as q16b -- ONE plane, 64-byte rows -- and
                 // srow[0] gets the identity list the one-plane kernels read them through; 2 = staged as q16c (single-pass mode)
+  // rows of a q32b block that holds a whole DATASET (lirec_set_feature_rows): the block's rows are those of the batch's samples,
+  // physical row p = row p % rpc of sample clip_ids[p / rpc] -> storage row clip_ids[p / rpc] * rpc + p % rpc.  The ids are read
+  // here, through the pointer, every time the pass runs.  nullptr = the block is the batch.
+  const int* clip_ids; int rpc;
 };
 // (block = this role's workgroup index, nblocks = how many workgroups the role has: the roles of several row sets and of the
 //  weight split share ONE launch, stage_fused_kernel below)
@@ -799,6 +803,9 @@ __device__ __forceinline__ void stage_rows_q32b(const float* __restrict__ X, lon
           const int v = src.index[3 * prow + part];
           const int* lst = part == 0 ? src.clip_rows : src.track_rows;
           out = v < 0 ? (part == 0 ? src.zero_clip : src.zero_track) : (lst ? lst[v] : v);
+        } else if (src.clip_ids) {
+          const long c = prow / src.rpc;
+          out = (int)((long)src.clip_ids[c] * src.rpc + (prow - c * src.rpc));     // (< 2^31: checked on the host)
         } else {
           out = (int)prow;
         }
@@ -864,6 +871,23 @@ __global__ __launch_bounds__(256) void to_q32b_kernel(const float* __restrict__ 
     f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = a;
     if (row < rows) { const float* q = src + row * ld + 8 * c8; a = *reinterpret_cast<const f32x4*>(q); b = *reinterpret_cast<const f32x4*>(q + 4); }
     p2_store_q32b(dst, row, c8, c8n >> 2, a, b);
+  }
+}
+// `rows` rows of an fp32 or float64 source -> rows [row0, row0 + rows) of an EXISTING q32b matrix (lirec_q32b_write_rows): the
+// halves to_q32b_kernel writes for the same values (a float64 value goes through fp32 first, as cast_f64_f32_kernel rounds it).  A
+// thread owns 32 bytes of one row's 128-byte line of a block: nothing outside the written rows is touched, nothing is read back.
+template <typename T>
+__global__ __launch_bounds__(256) void q32b_write_rows_kernel(const T* __restrict__ src, long ld, long rows, long row0, int c8n,
+                                                              unsigned char* __restrict__ dst) {
+  const long total = rows * c8n;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long row = i / c8n;
+    const int c8 = (int)(i - row * c8n);
+    const T* q = src + row * ld + 8 * c8;
+    f32x4 a, b;
+    a.x = (float)q[0]; a.y = (float)q[1]; a.z = (float)q[2]; a.w = (float)q[3];
+    b.x = (float)q[4]; b.y = (float)q[5]; b.z = (float)q[6]; b.w = (float)q[7];
+    p2_store_q32b(dst, row0 + row, c8, c8n >> 2, a, b);
   }
 }
 // fp32 [rows][cols] -> q16b (bf16 round-to-nearest-even of every value, blocked: gemm_bf16x3.hpp), rows padded to rows32 by zeros
@@ -2582,6 +2606,17 @@ __global__ __launch_bounds__(256) void collate_emit_kernel(const lirec_collate_a
   int out = -1;
   if (v >= 0 && (int64_t)v < (t ? a.n_track_all : a.n_clip_all)) out = ((const int*)((const unsigned char*)a.workspace + ws.rank[t]))[v];
   a.feature_index[i] = out;
+}
+
+// lirec_collate_fields: the field-row copy alone, blockIdx.y = the field
+struct CollateFields { const int* ids; int B, nf; lirec_collate_field fields[LIREC_COLLATE_MAX_FIELDS]; };
+__global__ __launch_bounds__(256) void collate_fields_kernel(const CollateFields a) {
+  const lirec_collate_field& f = a.fields[blockIdx.y];
+  const uintptr_t al = (uintptr_t)f.src | (uintptr_t)f.dst | (uintptr_t)f.row_bytes;
+  if ((al & 15) == 0) collate_copy_rows<uint4>(f, a.ids, a.B);
+  else if ((al & 7) == 0) collate_copy_rows<uint2>(f, a.ids, a.B);
+  else if ((al & 3) == 0) collate_copy_rows<unsigned>(f, a.ids, a.B);
+  else collate_copy_rows<unsigned char>(f, a.ids, a.B);
 }
 
 __global__ void dropout_mask_kernel(uint8_t* __restrict__ keep, int rows, int cols, unsigned seed_lo, unsigned seed_hi,

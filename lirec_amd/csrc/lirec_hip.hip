@@ -153,6 +153,10 @@ struct AdamThreadState {
   AdamHyperMap map;                      //   of the flat layout with their groups; count 0 = off
 };
 static thread_local AdamThreadState t_adam = {};
+// What lirec_set_feature_rows left for the NEXT lirec_embed_fwd / lirec_embed_fwd2 of this host thread (taken -- and cleared -- at
+// the entry of that call, whatever the call then does with it).
+static thread_local lirec_feature_rows t_frows = {};
+static thread_local bool t_frows_on = false;
 // While the mode is on, every weight / bias gradient target that is handed to a launch is noted: a parameter written by TWO
 // launches of one step (a tied module, a gradient cut over several launches) would silently lose the first contribution -- the
 // caller that switches the mode on asks for the count of such targets afterwards (lirec_grad_overwrite_conflicts) and keeps
@@ -606,7 +610,7 @@ static int launch_stage(const Args* a, const PlaneLayout& L, hipStream_t s, cons
 
 // the same as a role of the fused staging launch (stage_fused_kernel)
 template <class Args>
-static void stage_head_fill(StageHead& h, const Args* a, const PlaneLayout& L) {
+static void stage_head_fill(StageHead& h, const Args* a, const PlaneLayout& L, const lirec_feature_rows* fr = nullptr) {
   memset(&h, 0, sizeof(h));
   h.X = a->X ? (L.staged16 ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(a->X) + 2L * L.c0) : a->X + L.c0) : nullptr;
   h.ldx = (long)a->ldx; h.gs = a->sel.group; h.gstride = a->sel.group_stride; h.goff = a->sel.group_off;
@@ -622,6 +626,8 @@ static void stage_head_fill(StageHead& h, const Args* a, const PlaneLayout& L) {
     if (const lirec_pieces* pc = pieces_of(a)) {
       h.src.index = pc->index; h.src.clip_rows = pc->clip_rows; h.src.track_rows = pc->track_rows;
       h.src.zero_clip = pc->n_clip; h.src.zero_track = pc->n_track;
+    } else if (fr) {
+      h.src.clip_ids = fr->clip_ids; h.src.rpc = fr->rows_per_clip;     // (the block at X holds the whole dataset)
     }
   }
   const lirec_dropout* drop = &a->drop;
@@ -1139,6 +1145,8 @@ int lirec_abi_sizeof(int which) {
     case 15: return (int)sizeof(lirec_predict_args);         // (14 stays unassigned)
     case 17: return (int)sizeof(lirec_collate_args);         // (16 stays unassigned)
     case 19: return (int)sizeof(lirec_clip_weights);         // (18 stays unassigned)
+    case 21: return (int)sizeof(lirec_feature_rows);         // (20 stays unassigned)
+    case 23: return (int)sizeof(lirec_collate_field);        // (22 stays unassigned)
     default: return -1;
   }
 }
@@ -1233,6 +1241,26 @@ int lirec_to_q32b(const float* src, int64_t ld_src, int64_t rows, int64_t cols, 
   if (blocks > 8192) blocks = 8192;
   lirec::launch(to_q32b_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, (long)ld_src, (long)rows, rows32, (int)(cols / 8),
                 reinterpret_cast<unsigned char*>(dst));
+  LIREC_CHECK_LAUNCH();
+  return LIREC_OK;
+}
+
+int lirec_q32b_write_rows(const void* src, int32_t src_f64, int64_t ld_src, int64_t rows, int64_t cols, void* dst, int64_t dst_row0,
+                          int64_t dst_rows, lirec_stream_t stream) {
+  if (!src || !dst || (src_f64 != 0 && src_f64 != 1) || rows < 0 || cols < 32 || (cols & 31) != 0 || ld_src < cols || dst_row0 < 0 ||
+      dst_rows < 32 || (dst_rows & 31) != 0 || dst_rows > LIREC_FEATURE_ROWS_MAX || rows > dst_rows - dst_row0 ||
+      (reinterpret_cast<uintptr_t>(src) & (src_f64 ? 7 : 3)) != 0 || (reinterpret_cast<uintptr_t>(dst) & 255) != 0)
+    return LIREC_EINVAL;
+  if (rows == 0) return LIREC_OK;
+  const long total = rows * (cols / 8);
+  long blocks = (total + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  if (src_f64)
+    lirec::launch(q32b_write_rows_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const double*)src, (long)ld_src,
+                  (long)rows, (long)dst_row0, (int)(cols / 8), reinterpret_cast<unsigned char*>(dst));
+  else
+    lirec::launch(q32b_write_rows_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)src, (long)ld_src,
+                  (long)rows, (long)dst_row0, (int)(cols / 8), reinterpret_cast<unsigned char*>(dst));
   LIREC_CHECK_LAUNCH();
   return LIREC_OK;
 }
@@ -1380,11 +1408,13 @@ static int launch_gemm_heads(int layout, GemmGroup* gs, int n, hipStream_t s, in
 // stage_mode: 0 = stage everything, then the GEMM; 1 = stage the ROWS only (feature rows / row lists, dropout keep bytes, the
 // partition bound) and return -- parts = 4, what a caller runs for the NEXT batch beside this batch's backward; 2 = the rows are
 // in `planes` already (such a call was made): stage the weights only, then the GEMM.
-static int embed_fwd_layer1_heads(const lirec_embed_fwd_args* const* hs, GemmGroup* g1, int nh, hipStream_t s, int stage_mode = 0) {
+static int embed_fwd_layer1_heads(const lirec_embed_fwd_args* const* hs, GemmGroup* g1, int nh, hipStream_t s, int stage_mode = 0,
+                                  const lirec_feature_rows* fr = nullptr) {
   PlaneLayout L[2];
   int rc = LIREC_OK;
   bool planes = planes_for_heads(hs, nh, L);
   if (stage_mode != 0 && !planes) return LIREC_EINVAL;          // (rows staged ahead: the q32b kernels only)
+  if (fr && !planes) return LIREC_EINVAL;                       // (rows of a resident store: the gathered q32b path only)
   for (int h = 0; h < nh; ++h)
     if ((hs[h]->pieces || hs[h]->x_q32) && !planes) return LIREC_EINVAL;   // rows given as pieces / stored as q32b: the q32b kernels only
   SplitQ32b q;
@@ -1439,7 +1469,7 @@ static int embed_fwd_layer1_heads(const lirec_embed_fwd_args* const* hs, GemmGro
       double bytes = 0.0;
       for (int k = 0; k < nh && stage_mode != 2; ++k) {
         const int h = (k == 0) ? first : 1 - first;
-        stage_head_fill(f.h[k], hs[h], L[h]);
+        stage_head_fill(f.h[k], hs[h], L[h], fr);
         if (L[h].staged16) bytes += 4.0 * (double)hs[h]->rows * L[h].dsum;
         else if (!L[h].gather) bytes += 8.0 * (double)hs[h]->rows * L[h].dsum;
       }
@@ -1479,7 +1509,24 @@ static int embed_fwd_layer1_heads(const lirec_embed_fwd_args* const* hs, GemmGro
 
 // The forward of one head (lirec_embed_fwd) or two (lirec_embed_fwd2).  Every head is validated first, head 0 before head 1.  A
 // head without rows: the one-head call is done (before `parts` is looked at); the two-head call becomes the one-head calls, in order.
-static int embed_fwd_heads(const lirec_embed_fwd_args* const* hs, int nh, hipStream_t s) {
+// The checks of a call made under lirec_set_feature_rows (include/lirec_hip.h), all on the host: what a head of the call must be
+// for its block rows to be rows of the batch's samples in a q32b store.  (That the call takes the gathered q32b path is checked
+// where the path is chosen: embed_fwd_layer1_heads.)
+static bool feature_rows_ok(const lirec_feature_rows* fr, const lirec_embed_fwd_args* a) {
+  if (!fr->clip_ids || (reinterpret_cast<uintptr_t>(fr->clip_ids) & 3) != 0 || fr->n_clips < 1 || fr->rows_per_clip < 1) return false;
+  if (fr->store_rows < 1 || fr->store_rows > LIREC_FEATURE_ROWS_MAX) return false;
+  if (a->x_q32 != 1 || a->pieces != nullptr || a->x_bf16 != 0) return false;
+  const int64_t rpc = fr->rows_per_clip, phys = (int64_t)fr->n_clips * rpc;
+  if (phys > LIREC_FEATURE_ROWS_MAX) return false;
+  const lirec_rowsel& sel = a->sel;
+  if (sel.group == 0) return a->rows % rpc == 0 && (int64_t)a->rows == phys;
+  if (sel.group < 0 || sel.group_stride < 1 || sel.group_off < 0 || sel.group_off + sel.group > sel.group_stride) return false;
+  if (rpc % sel.group_stride != 0) return false;
+  const int64_t per_clip = rpc / sel.group_stride * sel.group;       // logical rows of this head per sample
+  return a->rows % per_clip == 0 && (int64_t)a->rows / sel.group * sel.group_stride == phys;
+}
+
+static int embed_fwd_heads(const lirec_embed_fwd_args* const* hs, int nh, hipStream_t s, const lirec_feature_rows* fr = nullptr) {
   GemmGroup g1[2], g2[2];
   int rc = LIREC_OK;
   bool empty = false;
@@ -1487,6 +1534,12 @@ static int embed_fwd_heads(const lirec_embed_fwd_args* const* hs, int nh, hipStr
     rc = embed_fwd_build(hs[h], g1[h], g2[h]);
     if (rc) return rc;
     empty = empty || hs[h]->rows == 0;
+  }
+  if (fr) {
+    // (an empty head, or a part of the call that reads no rows, under the setter: a caller's mistake, not a no-op)
+    if (empty || (hs[0]->parts != 0 && hs[0]->parts != 1 && hs[0]->parts != 4)) return LIREC_EINVAL;
+    for (int h = 0; h < nh; ++h)
+      if (!feature_rows_ok(fr, hs[h])) return LIREC_EINVAL;
   }
   if (empty) {
     for (int h = 0; nh > 1 && !rc && h < nh; ++h) rc = embed_fwd_heads(&hs[h], 1, s);
@@ -1496,19 +1549,35 @@ static int embed_fwd_heads(const lirec_embed_fwd_args* const* hs, int nh, hipStr
   if (parts < 0 || parts > 4) return LIREC_EINVAL;
   for (int h = 1; h < nh; ++h)
     if (hs[h]->parts != parts || (hs[h]->rows_staged != 0) != (hs[0]->rows_staged != 0)) return LIREC_EINVAL;
-  if (parts == 4) return embed_fwd_layer1_heads(hs, g1, nh, s, 1);
+  if (parts == 4) return embed_fwd_layer1_heads(hs, g1, nh, s, 1, fr);
   if (parts == 3) { for (int h = 0; !rc && h < nh; ++h) rc = embed_fwd_pool_only(hs[h], s); }
-  else if (parts != 2) rc = embed_fwd_layer1_heads(hs, g1, nh, s, hs[0]->rows_staged ? 2 : 0);
+  else if (parts != 2) rc = embed_fwd_layer1_heads(hs, g1, nh, s, hs[0]->rows_staged ? 2 : 0, fr);
   if (rc || parts == 1) return rc;
   // the second layers of both heads run on the (pooled) candidate rows: one grouped launch
   return launch_gemm_heads(L_NT, g2, nh, s, PS_EMBED_L2_FWD);
 }
 
-int lirec_embed_fwd(const lirec_embed_fwd_args* a, lirec_stream_t stream) { return embed_fwd_heads(&a, 1, (hipStream_t)stream); }
+int lirec_set_feature_rows(const lirec_feature_rows* rows) {
+  t_frows_on = rows != nullptr;
+  if (rows) t_frows = *rows;
+  return LIREC_OK;
+}
+// (taken at the entry of the two calls that read it: consumed whether the call succeeds or not)
+struct FeatureRowsTaken {
+  lirec_feature_rows v; bool on;
+  FeatureRowsTaken() : v(t_frows), on(t_frows_on) { t_frows_on = false; }
+  const lirec_feature_rows* get() const { return on ? &v : nullptr; }
+};
+
+int lirec_embed_fwd(const lirec_embed_fwd_args* a, lirec_stream_t stream) {
+  const FeatureRowsTaken fr;
+  return embed_fwd_heads(&a, 1, (hipStream_t)stream, fr.get());
+}
 
 int lirec_embed_fwd2(const lirec_embed_fwd_args* a, const lirec_embed_fwd_args* b, lirec_stream_t stream) {
+  const FeatureRowsTaken fr;
   const lirec_embed_fwd_args* hs[2] = {a, b};
-  return embed_fwd_heads(hs, 2, (hipStream_t)stream);
+  return embed_fwd_heads(hs, 2, (hipStream_t)stream, fr.get());
 }
 
 // Layer 1 of `nh` heads on the unique feature pieces (kernels.hpp, gather_act_kernel): the pre-activations of every piece
@@ -2796,6 +2865,30 @@ int lirec_collate_resident(const lirec_collate_args* a, lirec_stream_t stream) {
   lirec::launch(collate_mark_kernel, dim3(blocks), dim3(256), 0, s, *a);
   lirec::launch(collate_rank_kernel, dim3(2), dim3(COLLATE_SCAN_THREADS), 0, s, *a);
   lirec::launch(collate_emit_kernel, dim3(blocks, 1 + a->nf), dim3(256), 0, s, *a);
+  LIREC_CHECK_LAUNCH();
+  return LIREC_OK;
+}
+
+int lirec_collate_fields(const int32_t* ids, int32_t B, const lirec_collate_field* fields, int32_t nf, lirec_stream_t stream) {
+  if (B < 0 || nf < 0 || nf > LIREC_COLLATE_MAX_FIELDS || (nf > 0 && !fields) || (reinterpret_cast<uintptr_t>(ids) & 3) != 0) return LIREC_EINVAL;
+  for (int f = 0; f < nf; ++f)
+    if (fields[f].row_bytes < 1) return LIREC_EINVAL;
+  if (B > 0) {
+    if (!ids) return LIREC_EINVAL;
+    for (int f = 0; f < nf; ++f)
+      if (!fields[f].src || !fields[f].dst) return LIREC_EINVAL;
+  }
+  if (B == 0 || nf == 0) return LIREC_OK;
+  CollateFields a;
+  memset(&a, 0, sizeof(a));
+  a.ids = ids; a.B = B; a.nf = nf;
+  int64_t most = 0;
+  for (int f = 0; f < nf; ++f) { a.fields[f] = fields[f]; most = fields[f].row_bytes > most ? fields[f].row_bytes : most; }
+  // (sized for the widest field in 16-byte moves; every field's loop strides over the grid)
+  long blocks = ((long)B * ((most + 15) / 16) + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  if (blocks < 1) blocks = 1;
+  lirec::launch(collate_fields_kernel, dim3((unsigned)blocks, (unsigned)nf), dim3(256), 0, (hipStream_t)stream, a);
   LIREC_CHECK_LAUNCH();
   return LIREC_OK;
 }

@@ -85,12 +85,33 @@ def device_collate_in_force(dataset, device=None) -> bool:
         bool(getattr(opt, 'pieces_gather', True)) and bool(getattr(opt, 'pieces_q32b', False)) and bool(getattr(opt, 'layer1_planes', False))
 
 
+def block_store_in_force(dataset, device=None) -> bool:
+    """``BlockLoader`` draws ``dataset`` when it keeps its samples in a resident block store (lirec_amd.blockstore) and the device is
+    a GPU.  (Nothing else is asked: a model that cannot read such batches -- ``opt.layer1_planes`` off, another GEMM core -- says so
+    itself, there is no other path to fall back to.)  A wrapper that adds per-clip weights AROUND the store would lose them --
+    the store's batches carry the store's fields -- and is refused."""
+    from .config import opt
+    from .features import CLIP_WEIGHT
+    from ._lib import LirecError
+    store = getattr(dataset, 'block_store', None)
+    device = opt.device if device is None else device
+    if store is None or store.tables is None or not str(device).startswith('cuda'):
+        return False
+    if getattr(dataset, 'carries_clip_weights', False) and CLIP_WEIGHT not in store.keys:
+        raise LirecError('per-clip weights wrapped around a resident block store do not reach its batches: give them to the store '
+                         '(ResidentBlockDataset.set_clip_weights / data.with_clip_weights) or wrap the dataset before it is made resident')
+    return True
+
+
 def make_loader(dataset, batch_size, shuffle=False, sampler=None):
     """What ``training()``, ``testing()`` and ``predict()`` draw ``dataset`` with: ``ResidentLoader`` where ``device_collate_in_force``
-    (the batch buffer written on the device), ``ThreadedLoader`` for a dataset that brings its own ``collate_fn`` (PiecesDataset: piece
-    tables + index, built on ``opt.num_workers`` threads), else the stock ``DataLoader`` (mlp/train.py:33-37, mlp/test.py:18-22)."""
+    (the batch buffer written on the device), ``BlockLoader`` for a tiled dataset resident in a block store (``block_store_in_force``),
+    ``ThreadedLoader`` for a dataset that brings its own ``collate_fn`` (PiecesDataset: piece tables + index, built on
+    ``opt.num_workers`` threads), else the stock ``DataLoader`` (mlp/train.py:33-37, mlp/test.py:18-22)."""
     from .config import opt
     kw = dict(batch_size=batch_size, shuffle=shuffle, sampler=sampler, drop_last=False)
+    if block_store_in_force(dataset):
+        return BlockLoader(dataset, device=opt.device, **kw)
     if device_collate_in_force(dataset):
         return ResidentLoader(dataset, device=opt.device, **kw)
     if getattr(dataset, 'collate_fn', None) is not None:
@@ -175,6 +196,83 @@ class ResidentLoader:
         flat = np.fromiter((i for idx in todo for i in idx), dtype=np.int64)
         if flat.size and (int(flat.min()) < 0 or int(flat.max()) >= len(self.dataset)):
             raise IndexError('ResidentLoader: the sampler drew a sample id outside [0, %d)' % len(self.dataset))
+        ids = torch.from_numpy(flat.astype(np.int32)).to(self.device)         # the epoch's order: one host-to-device copy
+        at = 0
+        for idx in todo:
+            B = len(idx)
+            yield self.collate_ids(ids[at:at + B], B)
+            at += B
+
+
+class BlockLoader:
+    """Batches of a dataset resident in a block store (``lirec_amd.blockstore.ResidentBlockDataset``), made ON THE DEVICE from
+    sample ids -- ``ResidentLoader``'s contract for tiled datasets.  The batch sampler is drawn on the caller's thread, all at once
+    (the same torch seed gives the same batches as the stock ``DataLoader``); the epoch's ids go up in one copy and are validated on
+    the host; every ``next()`` is ONE ``ops.collate_fields`` launch on the current stream into one buffer of a static layout.  A
+    batch is ``to_device_batch(default_collate([dataset[i] for i in ids]), feature_dtype='q32')`` key for key, dtype for dtype,
+    value for value -- ``features`` a ``Q32Block`` over the whole store that names the batch's samples, no row copied -- plus
+    ``_layout`` and ``_dev_blob``.  Duplicate ids (a sampler that draws with replacement) are fine.
+    ``bind`` / ``unbind`` / ``n_collate`` / ``n_in_place`` as ``ResidentLoader``."""
+
+    def __init__(self, dataset, batch_size=1, shuffle=False, sampler=None, drop_last=False, device='cuda'):
+        if getattr(dataset, 'block_store', None) is None:
+            raise ValueError('BlockLoader needs a dataset with a block_store (lirec_amd.blockstore.ResidentBlockDataset)')
+        self.dataset, self.device, self.store = dataset, torch.device(device), dataset.block_store
+        if sampler is None:
+            sampler = torch.utils.data.RandomSampler(dataset) if shuffle else torch.utils.data.SequentialSampler(dataset)
+        self.batch_sampler = torch.utils.data.BatchSampler(sampler, batch_size, drop_last)
+        self.n_collate = self.n_in_place = 0
+        self._bound = None                  # (layout, blob)
+        self._layouts = {}                  # batch size -> (layout, nbytes)
+
+    def __len__(self):
+        return len(self.batch_sampler)
+
+    def bind(self, layout, blob):
+        self._bound = (tuple(layout), blob)
+
+    def unbind(self):
+        self._bound = None
+
+    def layout(self, B):
+        """(layout, bytes) of a batch of ``B`` samples: ``blockstore.batch_layout`` of the store's fields"""
+        if B not in self._layouts:
+            from .blockstore import batch_layout
+            self._layouts[B] = batch_layout(self.store.fields, B)
+        return self._layouts[B]
+
+    def epoch_ids(self):
+        return [list(idx) for idx in self.batch_sampler]
+
+    def collate_ids(self, ids, B):
+        """one batch from ``B`` sample ids on the device (int32; validated by the caller)"""
+        from . import ops
+        from ._lib import COLLATE_MAX_FIELDS
+        from .blockstore import IDS_KEY
+        from .features import layout_views
+        store = self.store
+        layout, nbytes = self.layout(B)
+        in_place = self._bound is not None and self._bound[0] == tuple(layout)
+        blob = self._bound[1] if in_place else torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        views = layout_views(blob, layout)
+        pairs = [(store.tables[k], views[k]) for k, _, _, _, _ in layout]
+        for at in range(0, len(pairs), COLLATE_MAX_FIELDS):            # (one launch for up to sixteen fields: every recipe's)
+            ops.collate_fields(ids, pairs[at:at + COLLATE_MAX_FIELDS])
+        self.n_collate += 1
+        self.n_in_place += int(in_place)
+        clip_ids = views.pop(IDS_KEY)
+        out = {}
+        for k in store.keys:
+            out[k] = store.features_of(clip_ids, B) if k == store.feature_key else views[k]
+        out['_layout'], out['_dev_blob'] = layout, blob
+        return out
+
+    def __iter__(self):
+        import numpy as np
+        todo = self.epoch_ids()
+        flat = np.fromiter((i for idx in todo for i in idx), dtype=np.int64)
+        if flat.size and (int(flat.min()) < 0 or int(flat.max()) >= self.store.n):
+            raise IndexError('BlockLoader: the sampler drew a sample id outside [0, %d)' % self.store.n)
         ids = torch.from_numpy(flat.astype(np.int32)).to(self.device)         # the epoch's order: one host-to-device copy
         at = 0
         for idx in todo:

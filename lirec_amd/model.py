@@ -407,6 +407,11 @@ class _HotPathModule(nn.Module):
                 raise LirecError('q32 feature storage must live on the model\'s device')
             if not getattr(opt, 'layer1_planes', False):
                 raise LirecError('q32 feature storage is read by the q32b layer-1 kernels (opt.layer1_planes) only')
+            if f.clip_ids is not None and (f.planes != 2 or ops.get_gemm_mode() != 2):
+                # a batch of a resident block store (lirec_amd.blockstore): its rows exist in the store only -- no other layer-1
+                # path can read them, and none is tried
+                raise LirecError('a block-store batch is read by the gathered q32b layer-1 kernels only: the split-precision core '
+                                 '(gemm mode 2), not mode %d' % ops.get_gemm_mode())
             return f
         if f.device != dev:
             f = f.to(dev, non_blocking=True)
@@ -528,15 +533,22 @@ class _HotPathModule(nn.Module):
                                            pool=(None, R, clamp, d, d, cmp) if head.pooled else None,
                                            planes=pl_c if head.pooled else pl_i))
         ops.embed_fwd_heads(args, 4)
-        return {'X': X.data_ptr(), 'mask': mask.data_ptr(), 'n': n, 'R': R, 'seed': fwd_seed, 'seed_dev': self._seed_dev is not None,
+        return {'X': X.data_ptr(), 'ids': self._ids_key(X), 'mask': mask.data_ptr(), 'n': n, 'R': R, 'seed': fwd_seed, 'seed_dev': self._seed_dev is not None,
                 'cmp': cmp, 'planes_i': pl_i, 'planes_c': pl_c, 'dummy': d, '_keep': (X, mask)}
+
+    @staticmethod
+    def _ids_key(X):
+        """which samples of a resident block store ``X`` is made of (every batch of a store has the store's address): the address of
+        its id list -- None for a block that is its own storage"""
+        ids = getattr(X, 'clip_ids', None)
+        return None if ids is None else ids.data_ptr()
 
     def _take_prestaged(self, X, mask, n, R):
         """the handle ``prestage`` left for exactly this forward (same buffers, same key), or None"""
         pre = self.lanes.take_prestaged()
         if pre is None or not self.training or (isinstance(X, ops.Q32Block) and X.planes != 2) or mask is None:
             return None
-        ok = (pre['X'] == X.data_ptr() and pre['mask'] == mask.data_ptr() and pre['n'] == n and pre['R'] == R and
+        ok = (pre['X'] == X.data_ptr() and pre.get('ids') == self._ids_key(X) and pre['mask'] == mask.data_ptr() and pre['n'] == n and pre['R'] == R and
               pre['seed'] == self._cur_seed and pre['seed_dev'] == (self._seed_dev is not None))
         return pre if ok else None
 

@@ -183,16 +183,32 @@ def _f32c(t):
 class Q32Block:
     """A feature matrix stored as q32b on the device (include/lirec_hip.h: blocked bf16 hi / lo, the fp32 footprint) -- the storage
     layer 1 reads without a staging pass.  ``shape`` is the logical fp32 shape ((..., D), the leading dims flattened to rows),
-    ``data`` the uint8 buffer."""
+    ``data`` the uint8 buffer.
+
+    A batch of a RESIDENT BLOCK STORE (lirec_amd.blockstore) is such a block with ``clip_ids``: ``data`` is then the whole store
+    (``store_rows`` rows, ``rows_per_clip`` consecutive ones per sample), ``shape`` the BATCH's ((B, ..., D)) and ``clip_ids`` the
+    int32 device tensor [B] of the samples the batch is made of -- carried through ``view()``, handed to the library by the forward
+    call (lirec_set_feature_rows); no row is copied."""
     dtype = 'q32'
 
-    def __init__(self, data, shape, planes=2, k64=False):
+    def __init__(self, data, shape, planes=2, k64=False, clip_ids=None, rows_per_clip=0, store_rows=0):
         """``planes`` = 1: q16b -- the values rounded to bf16, one plane, half the footprint (``to_q16b``; dtype 'q16');
         ``k64``: the same values as q16c (64-column blocks: ``to_q16c``) -- the storage of the single-pass mode (gemm mode 3)"""
         self.data, self.shape, self.device, self.planes, self.k64 = data, tuple(shape), data.device, int(planes), bool(k64)
         assert not self.k64 or self.planes == 1
         if self.planes == 1:
             self.dtype = 'q16'
+        self.clip_ids, self.rows_per_clip, self.store_rows = clip_ids, int(rows_per_clip), int(store_rows)
+        if clip_ids is not None:
+            assert self.planes == 2 and clip_ids.dtype == torch.int32 and clip_ids.is_cuda and clip_ids.is_contiguous()
+
+    def feature_rows(self):
+        """the lirec_feature_rows of a block-store batch (None for a block that is its own storage)"""
+        if self.clip_ids is None:
+            return None
+        fr = _lib.FeatureRows(self.clip_ids.data_ptr(), self.clip_ids.numel(), self.rows_per_clip, self.store_rows)
+        fr._refs = (self.clip_ids, self.data)
+        return fr
 
     @property
     def x_q32(self):
@@ -210,7 +226,7 @@ class Q32Block:
             for d in shape:
                 k *= d if d != -1 else 1
             shape[shape.index(-1)] = n // k
-        return Q32Block(self.data, shape, self.planes, self.k64)
+        return Q32Block(self.data, shape, self.planes, self.k64, self.clip_ids, self.rows_per_clip, self.store_rows)
 
     def data_ptr(self):
         return self.data.data_ptr()
@@ -235,6 +251,21 @@ def to_q32b(t, out=None):
     assert out.dtype == torch.uint8 and out.is_cuda and out.numel() >= need and out.data_ptr() % 256 == 0
     check(lib().lirec_to_q32b(_p(t), D, rows, D, _p(out), _stream()), 'lirec_to_q32b')
     return Q32Block(out, t.shape)
+
+
+def q32b_write_rows(src, dst, row0, dst_rows):
+    """Rows of ``src`` (fp32 or float64 device tensor (..., D), contiguous) -> storage rows [row0, row0 + rows) of the q32b matrix of
+    ``dst_rows`` x D in the uint8 buffer ``dst`` (lirec_q32b_write_rows): the halves ``to_q32b`` writes for the same values -- a
+    float64 value through fp32 first --, no other row touched."""
+    assert src.is_cuda and src.dtype in (torch.float32, torch.float64) and src.is_contiguous()
+    assert dst.dtype == torch.uint8 and dst.is_cuda and dst.is_contiguous()
+    D = src.shape[-1]
+    rows = src.numel() // D if D else 0
+    assert dst.numel() >= int(dst_rows) * D * 4, (dst.numel(), dst_rows, D)
+    if rows == 0:
+        return
+    check(lib().lirec_q32b_write_rows(_p(src), int(src.dtype == torch.float64), D, rows, D, _p(dst), int(row0), int(dst_rows), _stream()),
+          'lirec_q32b_write_rows')
 
 
 def to_q16b(t, out=None, k64=False):
@@ -330,19 +361,33 @@ def _fill_head_common(a, X, ldx, sel, rows, J, segs, drop, pool, planes, pieces,
     a.X, a.ldx = _p(X), ldx
     a.x_bf16 = int(X.dtype == torch.bfloat16)
     a.x_q32 = X.x_q32 if isinstance(X, Q32Block) else 0
+    a._frows = X.feature_rows() if isinstance(X, Q32Block) else None     # (a block-store batch: armed by the forward call)
     _fill(a.in_off, segs.in_off); _fill(a.in_dim, segs.in_dim); _fill(a.out_dim, segs.out_dim)
     a.rows, a.nseg, a.J = rows, segs.n, J
     a.sel = RowSel(*sel)
     a.drop = drop
 
 
+def _arm_feature_rows(*heads):
+    """lirec_set_feature_rows for the forward call about to be made, when its heads read a block-store batch: the parts of the
+    call that turn block rows into storage rows (0, 1, 4) -- parts 2 and 3 read no rows and take no setter.  The library consumes
+    it in that call."""
+    fr = getattr(heads[0], '_frows', None)
+    if len({getattr(h, '_frows', None) is None for h in heads}) > 1:
+        raise LirecError('the heads of one forward call must read the same feature block')
+    if fr is not None and heads[0].parts in (0, 1, 4):
+        check(lib().lirec_set_feature_rows(C.byref(fr)), 'lirec_set_feature_rows')
+
+
 def embed_fwd(*args, **kw):
     a = kw['args'] if 'args' in kw else embed_fwd_args(*args, **kw)
+    _arm_feature_rows(a)
     check(lib().lirec_embed_fwd(C.byref(a), _stream()), 'lirec_embed_fwd')
 
 
 def embed_fwd2(a, b):
     """Both heads in one call (``a``, ``b`` from embed_fwd_args): their second layers share a grouped launch."""
+    _arm_feature_rows(a, b)
     check(lib().lirec_embed_fwd2(C.byref(a), C.byref(b), _stream()), 'lirec_embed_fwd2')
 
 
@@ -441,6 +486,7 @@ def with_parts(a, parts):
     b._refs = getattr(a, '_refs', None)
     b._pieces_ref = getattr(a, '_pieces_ref', None)
     b._adam_ref = getattr(a, '_adam_ref', None)
+    b._frows = getattr(a, '_frows', None)
     return b
 
 
@@ -1184,6 +1230,21 @@ def predict_clips(ints, rels=None, mem=None, B=None, T=1, K=5, loader_types=Fals
     a.loader_types = int(bool(loader_types))
     check(lib().lirec_predict_clips(C.byref(a), _stream()), 'lirec_predict_clips')
     return out
+
+
+def collate_fields(ids, fields):
+    """dst row b = src row ids[b] for every (src [N, ...], dst [B, ...]) pair of contiguous device tensors, byte for byte, in one
+    launch on the current stream (lirec_collate_fields).  ``ids``: int32 [B], trusted (the caller validated them)."""
+    B = ids.numel()
+    assert ids.dtype == torch.int32 and ids.is_contiguous() and len(fields) <= _lib.COLLATE_MAX_FIELDS, len(fields)
+    if B == 0 or not fields:
+        return
+    arr = (_lib.CollateField * len(fields))()
+    for f, (src, dst) in enumerate(fields):
+        rb = src[0].numel() * src.element_size()
+        assert src.is_contiguous() and dst.is_contiguous() and dst.numel() * dst.element_size() == B * rb, (f, tuple(src.shape), tuple(dst.shape))
+        arr[f].src, arr[f].row_bytes, arr[f].dst = _p(src), rb, _p(dst)
+    check(lib().lirec_collate_fields(_p(ids), B, arr, len(fields), _stream()), 'lirec_collate_fields')
 
 
 def collate_workspace(n_clip_all, n_track_all, device):

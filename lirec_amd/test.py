@@ -47,7 +47,7 @@ def testing(test_dataset, model, loss, total_iter=1, mode='val', train_start_tim
     # the recipes without a maximum over tracks: clip-level counters by lirec_eval_clip_topk
     on_device_topk = (bool(getattr(opt, 'device_metrics', True)) and str(opt.device).startswith('cuda') and opt.ints == 1
                       and not opt.tr_maximize)
-    dev_counters = dev_loss = dev_conf = dev_rels = None
+    dev_counters = dev_loss = dev_conf = dev_rels = dev_tracks = None
     n_batches = n_out = rels_at = 0
     rels_parts = []                                   # (offset, rows, labelled rows, their labels, their pair hashes) per batch
     with torch.no_grad():
@@ -110,12 +110,18 @@ def testing(test_dataset, model, loss, total_iter=1, mode='val', train_start_tim
                         if rels_at + bs > dev_rels.shape[0]:          # (a dataset that yields more clips than its length)
                             dev_rels = torch.cat([dev_rels, torch.empty_like(dev_rels)])
                         dev_rels[rels_at:rels_at + bs].copy_(rl)
-                        sel = torch.nonzero(batch['rels_label'] - n_rels + 1)         # the loader's host tensors
-                        if sel.shape[0]:
-                            rels_parts.append((rels_at, bs, sel, batch['rels_label'][sel].squeeze(1), batch['hash_rel'][sel].squeeze(1)))
+                        if batch['rels_label'].is_cuda:
+                            # (a batch made on the device -- lirec_amd.loader.BlockLoader: its labels wait there like the logits)
+                            rels_parts.append((rels_at, bs, None, batch['rels_label'], batch['hash_rel']))
+                        else:
+                            sel = torch.nonzero(batch['rels_label'] - n_rels + 1)         # the loader's host tensors
+                            if sel.shape[0]:
+                                rels_parts.append((rels_at, bs, sel, batch['rels_label'][sel].squeeze(1), batch['hash_rel'][sel].squeeze(1)))
                         rels_at += bs
                 else:
-                    if opt.tracks:
+                    if opt.tracks and batch['just_zeros'].is_cuda:
+                        dev_tracks = batch['just_zeros'].sum() + (dev_tracks if dev_tracks is not None else 0)   # (read after the loop)
+                    elif opt.tracks:
                         total_tracks += int(np.sum(batch['just_zeros'].cpu().numpy()))       # (a host tensor of the loader)
                     ops.eval_clip_topk(ints, dv(labels.long()).reshape(-1), dev_counters, conf=dev_conf, loader_types=True)
                 continue
@@ -159,9 +165,17 @@ def testing(test_dataset, model, loss, total_iter=1, mode='val', train_start_tim
         losses.val = float(dev_loss) / n_batches
         losses.sum, losses.count = float(dev_loss) * n_out, n_out * n_batches
         losses.avg = losses.sum / losses.count
+        if dev_tracks is not None:
+            total_tracks += int(dev_tracks)
         if rels_parts:
             rels_host = dev_rels[:rels_at].cpu()
             for at, bs, sel, gt_rel, hashes in rels_parts:            # batch by batch, in order: the host path's sums
+                if sel is None:                                       # (device batches: selected here, as the host batches were in the loop)
+                    gt_all, hash_all = gt_rel.cpu(), hashes.cpu()
+                    sel = torch.nonzero(gt_all - n_rels + 1)
+                    if not sel.shape[0]:
+                        continue
+                    gt_rel, hashes = gt_all[sel].squeeze(1), hash_all[sel].squeeze(1)
                 prec_rels.update(rels_host[at:at + bs][sel].squeeze(1), gt_rel, hashes)
     if sharded:
         # the ranks' sums become the dataset's: Precision's counters, the loss average's numerator and denominator, the clip
