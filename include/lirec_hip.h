@@ -1002,6 +1002,17 @@ int lirec_collate_resident(const lirec_collate_args* a, lirec_stream_t stream);
  * (also under the dry run) for B or nf negative, nf over LIREC_COLLATE_MAX_FIELDS, NULL fields with nf > 0, a row_bytes < 1, a
  * misaligned ids; with B > 0: NULL ids, a field with a NULL src or dst.  B == 0 (or nf == 0): no launch, LIREC_OK. */
 int lirec_collate_fields(const int32_t* ids, int32_t B, const lirec_collate_field* fields, int32_t nf, lirec_stream_t stream);
+/* lirec_collate_fields with the batch's ids read THROUGH A DEVICE WORD: ids = ids_base + *cursor, the cursor read by the kernel (once
+ * per workgroup) when it runs -- so the launch, recorded into a command list, draws another batch at every replay: the batch the
+ * cursor names then.  ids_base: the epoch's sample ids (int32, a stable address); cursor: an int64 device word, an offset in ids.
+ * The same one launch, moves and blockIdx.y = field; no id outside [*cursor, *cursor + B) is read.  The launch does NOT move the
+ * cursor: lirec_counter_add(cursor, {B}, 1, stream) directly behind it does (a launch of its own: every workgroup of this one
+ * reads the word).  TRUSTED: 0 <= *cursor, *cursor + B <= the ids behind ids_base, every id a row of every field's source (the host
+ * sets the cursor and validated the ids).  LIREC_EINVAL (also under the dry run) for a NULL or misaligned ids_base (4 bytes) or
+ * cursor (8 bytes), B < 1, nf negative or over LIREC_COLLATE_MAX_FIELDS, NULL fields with nf > 0, a row_bytes < 1, a field with a
+ * NULL src or dst.  nf == 0: no launch, LIREC_OK.  (Added to ABI 124 without a new number: one new export, no struct changes.) */
+int lirec_collate_fields_at(const int32_t* ids_base, const int64_t* cursor, int32_t B, const lirec_collate_field* fields, int32_t nf,
+                            lirec_stream_t stream);
 
 /* ---- feature assembly ---------------------------------------------
  * The reference's loader tiles every row of the (B, T, R+1, D) feature block on the host as

@@ -287,6 +287,7 @@ _PROTOS = {
     'lirec_collate_workspace_bytes': (_i64, [_i64, _i64]),
     'lirec_collate_resident': (_i32, [C.POINTER(CollateArgs), _vp]),
     'lirec_collate_fields': (_i32, [_vp, _i32, C.POINTER(CollateField), _i32, _vp]),
+    'lirec_collate_fields_at': (_i32, [_vp, _vp, _i32, C.POINTER(CollateField), _i32, _vp]),
     'lirec_cast_f64_f32': (_i32, [_vp, _vp, _i64, _vp]),
     'lirec_grid_pool': (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i64, _vp]),
     'lirec_rows_max': (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _vp]),

@@ -65,6 +65,10 @@ def defaults() -> dict:
         # training() / testing() / predict() over such a store, gathered q32b path on a CUDA device: the batch buffer is written ON THE
         # DEVICE from the sample ids (lirec_amd.loader.ResidentLoader, lirec_collate_resident) instead of collated by loader threads
         device_collate=False,
+        # training() over a resident BLOCK store (lirec_amd.blockstore), single GPU: '' -- every batch steps eagerly; 'bind' -- the
+        # recorded train step over its batches, each written into the step's inputs by the loader's collate call; 'list' -- the
+        # batch is drawn INSIDE the recorded list (lirec_collate_fields_at at a device cursor): one replay call per iteration
+        record_block_store='',
         # a recorded train step (single GPU) folds the first-layer parameters' Adam update into the launch that finishes their
         # gradients, which also keeps the q32b form of the new weights for the next forward (lirec_amd/optim.py:arm_first_layer_update)
         fuse_dw1_adam=True,

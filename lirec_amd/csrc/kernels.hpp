@@ -2619,6 +2619,19 @@ __global__ __launch_bounds__(256) void collate_fields_kernel(const CollateFields
   else collate_copy_rows<unsigned char>(f, a.ids, a.B);
 }
 
+// lirec_collate_fields_at: the same copy with the batch's ids at ids_base + *cursor -- a device word every workgroup reads once, so a
+// launch replayed from a command list draws the batch the cursor names at replay time.  No id outside [*cursor, *cursor + B) is read.
+struct CollateFieldsAt { const int* ids_base; const long long* cursor; int B, nf; lirec_collate_field fields[LIREC_COLLATE_MAX_FIELDS]; };
+__global__ __launch_bounds__(256) void collate_fields_at_kernel(const CollateFieldsAt a) {
+  const int* ids = a.ids_base + *a.cursor;
+  const lirec_collate_field& f = a.fields[blockIdx.y];
+  const uintptr_t al = (uintptr_t)f.src | (uintptr_t)f.dst | (uintptr_t)f.row_bytes;
+  if ((al & 15) == 0) collate_copy_rows<uint4>(f, ids, a.B);
+  else if ((al & 7) == 0) collate_copy_rows<uint2>(f, ids, a.B);
+  else if ((al & 3) == 0) collate_copy_rows<unsigned>(f, ids, a.B);
+  else collate_copy_rows<unsigned char>(f, ids, a.B);
+}
+
 __global__ void dropout_mask_kernel(uint8_t* __restrict__ keep, int rows, int cols, unsigned seed_lo, unsigned seed_hi,
                                     const unsigned long long* __restrict__ seed_dev, unsigned site, unsigned thresh) {
   apply_seed_offset(seed_lo, seed_hi, seed_dev);

@@ -2893,6 +2893,28 @@ int lirec_collate_fields(const int32_t* ids, int32_t B, const lirec_collate_fiel
   return LIREC_OK;
 }
 
+int lirec_collate_fields_at(const int32_t* ids_base, const int64_t* cursor, int32_t B, const lirec_collate_field* fields, int32_t nf,
+                            lirec_stream_t stream) {
+  if (!ids_base || !cursor || (reinterpret_cast<uintptr_t>(ids_base) & 3) != 0 || (reinterpret_cast<uintptr_t>(cursor) & 7) != 0)
+    return LIREC_EINVAL;
+  if (B < 1 || nf < 0 || nf > LIREC_COLLATE_MAX_FIELDS || (nf > 0 && !fields)) return LIREC_EINVAL;
+  for (int f = 0; f < nf; ++f)
+    if (fields[f].row_bytes < 1 || !fields[f].src || !fields[f].dst) return LIREC_EINVAL;
+  if (nf == 0) return LIREC_OK;
+  CollateFieldsAt a;
+  memset(&a, 0, sizeof(a));
+  a.ids_base = ids_base; a.cursor = (const long long*)cursor; a.B = B; a.nf = nf;
+  int64_t most = 0;
+  for (int f = 0; f < nf; ++f) { a.fields[f] = fields[f]; most = fields[f].row_bytes > most ? fields[f].row_bytes : most; }
+  // (the grid of lirec_collate_fields: sized for the widest field in 16-byte moves; every field's loop strides over it)
+  long blocks = ((long)B * ((most + 15) / 16) + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  if (blocks < 1) blocks = 1;
+  lirec::launch(collate_fields_at_kernel, dim3((unsigned)blocks, (unsigned)nf), dim3(256), 0, (hipStream_t)stream, a);
+  LIREC_CHECK_LAUNCH();
+  return LIREC_OK;
+}
+
 int lirec_counter_add(int64_t* ctr, const int64_t* inc_host, int32_t n, lirec_stream_t stream) {
   if (!ctr || !inc_host || n < 1 || n > 4) return LIREC_EINVAL;
   long long inc[4] = {0, 0, 0, 0};

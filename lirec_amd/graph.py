@@ -158,13 +158,17 @@ class RecordedTrainStep:
     is a real step (every rank must construct this object at the same point of its program).
     """
 
-    def __init__(self, model, loss, optimizer, batch, warmup: int = 2, next_batch=None, overwrite=None):
+    def __init__(self, model, loss, optimizer, batch, warmup: int = 2, next_batch=None, overwrite=None, draw=None):
         """``next_batch`` (a SECOND set of device buffers, single GPU, resident fp32 features): the input pipeline form.  Steps
         alternate between the two buffer sets, and each step stages the layer-1 operand rows of the OTHER set -- the batch the
         next step runs on -- on a stream of its own beside its backward (``model.prestage``): the rows do not depend on the
         weights, and the backward is MFMA-bound while the staging pass is HBM-bound.  Refill the set a step has just run on
         before the next call (it is the one the call after next reads); the set the next call steps on must already be
-        filled -- its rows are staged DURING the current call.  Same numbers as the plain form, bit for bit."""
+        filled -- its rows are staged DURING the current call.  Same numbers as the plain form, bit for bit.
+        ``draw`` (a callable; plain single-GPU form): library launches that FILL ``batch``'s buffers, issued -- and recorded -- at the
+        head of the list, in front of the step's first launch: every replay then draws its own batch (a resident block store:
+        ``BlockLoader.collate_at``, lirec_collate_fields_at at a device cursor) and the host calls ``step()`` and nothing else.  The
+        recording step runs them too: they must write the recording batch's own values."""
         if not model.training:
             raise ValueError('RecordedTrainStep records a TRAIN step: call model.train() first')
         for b in (batch, next_batch):
@@ -178,7 +182,26 @@ class RecordedTrainStep:
                 # (likewise for piece tables that require grad: a replay would drop their gradient)
                 raise LirecError('RecordedTrainStep: the batch\'s piece tables require grad -- a recorded step computes no input '
                                  'gradient; run the eager step (model(batch) -> loss -> backward) instead')
-        self.model, self.loss, self.optim, self.batch = model, loss, optimizer, batch
+            ids = getattr(f, 'clip_ids', None)
+            if ids is not None and next_batch is not None:
+                # (two buffers would be two id slots, but the form's bit-identity test over such batches did not pass: DESIGN 4.n)
+                raise LirecError('RecordedTrainStep(next_batch=...): the input-pipeline form is not built over block-store batches -- '
+                                 'record the plain form')
+            if ids is not None:
+                # (a batch of a resident block store: the recorded launches read its sample ids through their ADDRESS -- a refill of the
+                #  batch's buffer reaches them only when the list lives inside that buffer; anywhere else every replay would read
+                #  the recording batch's ids again)
+                blob = b.get('_dev_blob')
+                lo = blob.data_ptr() if torch.is_tensor(blob) else None
+                if lo is None or not lo <= ids.data_ptr() <= lo + blob.numel() * blob.element_size() - ids.numel() * 4:
+                    raise LirecError('RecordedTrainStep: the block-store batch\'s clip_ids do not lie inside the batch\'s own buffer '
+                                     '(_dev_blob): a replay would keep reading the ids of the recording batch -- take the batch '
+                                     'from BlockLoader, or run the eager step')
+        if draw is not None and (next_batch is not None or getattr(model, 'grad_sync', None) is not None):
+            raise ValueError('RecordedTrainStep(draw=...): the plain single-GPU form')
+        self.draw, self.loss = draw, loss
+        self._check_draw()
+        self.model, self.loss, self.optim, self.batch, self.draw = model, loss, optimizer, batch, draw
         self.lanes = model.lanes       # (lirec_amd.lanes.StepLanes: the side streams and the state handed over between them)
         self.batches = [batch, next_batch] if next_batch is not None else [batch]
         self.sync = getattr(model, 'grad_sync', None)
@@ -272,6 +295,10 @@ class RecordedTrainStep:
                     optimizer.sync_hyper()          # (a command list never contains a write to the hyper-parameter tables)
                 ops.CommandList.begin()
                 try:
+                    if self.draw is not None:
+                        self.draw()
+                        if ops.CommandList.mark() < 1:
+                            raise RuntimeError('RecordedTrainStep(draw=...): the callable issued no library launch')
                     self._one_step(k=0)
                     if next_batch is not None:
                         self._advance_host()
@@ -405,9 +432,23 @@ class RecordedTrainStep:
                                'the other core\'s kernels and read its operand forms (the shadow of the first-layer weights is q16c in the '
                                'single-pass mode, q32b otherwise): set the mode back, or release() and record again'
                                % (self._gemm_mode, ops.get_gemm_mode()))
+        f = self.batch.get('features') if isinstance(self.batch, dict) else None
+        if getattr(f, 'clip_ids', None) is not None and not getattr(opt, 'layer1_planes', False):
+            # (the model refuses such a batch without the flag; a replay never asks the model)
+            raise LirecError('RecordedTrainStep: recorded on a block-store batch, which the gathered q32b layer-1 kernels alone read '
+                             '(opt.layer1_planes) -- the flag is off now: set it back, or release()')
+
+    def _check_draw(self):
+        """A list that draws its own batch leaves the host nothing to read of that batch in front of the replay: a loss with such
+        work (``before_replay``: the cross-entropy loss's int32 label copies) would convert the PREVIOUS batch's labels."""
+        if self.draw is not None and hasattr(self.loss, 'needs_before_replay') and self.loss.needs_before_replay():
+            raise LirecError('RecordedTrainStep(draw=...): %s reads the batch on the host\'s side in front of every replay '
+                             '(before_replay), i.e. before the list has drawn it -- record without draw= and fill the batch '
+                             'before step()' % type(self.loss).__name__)
 
     def step(self):
         """Re-issue the recorded step; returns the loss as a device tensor (no synchronisation)."""
+        self._check_draw()
         if self.hyper_key(self.optim) != self._hyper:
             raise RuntimeError('RecordedTrainStep: the optimiser\'s hyper-parameters changed since the step was recorded (%s -> %s); the '
                                'recorded Adam launches carry them by value -- release() this object and record a new one (a learning-'

@@ -204,6 +204,30 @@ class ResidentLoader:
             at += B
 
 
+class _Cursor:
+    """The int64 device word an in-list draw reads (``lirec_collate_fields_at``) and the host's account of it: ``at`` is the value
+    the word has once everything enqueued so far has run (None: not known).  One owner, three moves: ``expect(at)`` -- the next
+    draw must find ``at``: one small fill on the current stream unless the word already holds it --, ``advanced(B)`` -- a launch that
+    moves the word on by ``B`` was enqueued (or will run before the next ``expect``) --, ``invalidate()``."""
+
+    def __init__(self, device):
+        self.word, self.at, self.device = None, None, device
+
+    def expect(self, at):
+        if self.word is None:
+            self.word = torch.empty(1, dtype=torch.int64, device=self.device)
+        if self.at != int(at):
+            self.word.fill_(int(at))
+            self.at = int(at)
+
+    def advanced(self, B):
+        assert self.at is not None, 'expect() first'
+        self.at += int(B)
+
+    def invalidate(self):
+        self.at = None
+
+
 class BlockLoader:
     """Batches of a dataset resident in a block store (``lirec_amd.blockstore.ResidentBlockDataset``), made ON THE DEVICE from
     sample ids -- ``ResidentLoader``'s contract for tiled datasets.  The batch sampler is drawn on the caller's thread, all at once
@@ -212,7 +236,19 @@ class BlockLoader:
     batch is ``to_device_batch(default_collate([dataset[i] for i in ids]), feature_dtype='q32')`` key for key, dtype for dtype,
     value for value -- ``features`` a ``Q32Block`` over the whole store that names the batch's samples, no row copied -- plus
     ``_layout`` and ``_dev_blob``.  Duplicate ids (a sampler that draws with replacement) are fine.
-    ``bind`` / ``unbind`` / ``n_collate`` / ``n_in_place`` as ``ResidentLoader``."""
+    ``bind`` / ``unbind`` / ``n_collate`` / ``n_in_place`` as ``ResidentLoader``.
+
+    ``bind(layout, blob, in_list=True)``: whoever bound the buffer draws the batch itself -- a recorded train step whose list
+    begins with ``collate_at(layout, blob)``, i.e. ``lirec_collate_fields_at`` at the loader's device ``cursor`` and the launch
+    that moves the cursor on by the batch.  ``next()`` then yields the views of ``blob`` WITHOUT a launch (``n_in_list`` counts
+    these; ``n_collate`` does not move) and promises that the cursor names this batch when the list runs: the host keeps the value
+    the device word will have (``_Cursor``) and writes the word -- one small write on the current stream -- whenever a batch
+    was handed out another way in between (an epoch's start, the eager interludes).  A batch yielded so holds its values only
+    once the list has run; ``materialise(batch)`` collates it after all (the step was not replayed).
+    ``stable_ids`` (set by whoever will bind in-list, before the epoch is drawn): the epoch's ids go into ONE buffer of a stable
+    address (``ids_base``, made once for the dataset's length, refilled by one copy per epoch) -- the address a recorded list
+    holds; two live iterators of one loader would then share it, so only one may be alive.  Off (the default): every ``iter()``
+    has a tensor of its own."""
 
     def __init__(self, dataset, batch_size=1, shuffle=False, sampler=None, drop_last=False, device='cuda'):
         if getattr(dataset, 'block_store', None) is None:
@@ -221,18 +257,26 @@ class BlockLoader:
         if sampler is None:
             sampler = torch.utils.data.RandomSampler(dataset) if shuffle else torch.utils.data.SequentialSampler(dataset)
         self.batch_sampler = torch.utils.data.BatchSampler(sampler, batch_size, drop_last)
-        self.n_collate = self.n_in_place = 0
-        self._bound = None                  # (layout, blob)
+        self.n_collate = self.n_in_place = self.n_in_list = 0
+        self._bound = None                  # (layout, blob, in_list)
+        self._bound_out = None              # the bound buffer's batch dict, cut once
         self._layouts = {}                  # batch size -> (layout, nbytes)
+        self.stable_ids = False             # the epoch's ids in one reused buffer (what an in-list draw reads) or a tensor per epoch
+        self.ids_base = None                # the epoch's ids under ``stable_ids`` (int32)
+        self._cursor = _Cursor(self.device)
+        self._last = None                   # the batch handed out last: (offset in the epoch's ids, B, in_list)
 
     def __len__(self):
         return len(self.batch_sampler)
 
-    def bind(self, layout, blob):
-        self._bound = (tuple(layout), blob)
+    def bind(self, layout, blob, in_list=False):
+        new = (tuple(layout), blob, bool(in_list))
+        if self._bound is None or self._bound[0] != new[0] or self._bound[1] is not blob:
+            self._bound_out = None
+        self._bound = new
 
     def unbind(self):
-        self._bound = None
+        self._bound = self._bound_out = None
 
     def layout(self, B):
         """(layout, bytes) of a batch of ``B`` samples: ``blockstore.batch_layout`` of the store's fields"""
@@ -244,28 +288,103 @@ class BlockLoader:
     def epoch_ids(self):
         return [list(idx) for idx in self.batch_sampler]
 
-    def collate_ids(self, ids, B):
-        """one batch from ``B`` sample ids on the device (int32; validated by the caller)"""
-        from . import ops
-        from ._lib import COLLATE_MAX_FIELDS
+    def _batch_of(self, layout, blob, B):
+        """(the batch dict over ``blob``, the (table, view) pairs a collate launch copies -- the ids last)"""
         from .blockstore import IDS_KEY
         from .features import layout_views
         store = self.store
-        layout, nbytes = self.layout(B)
-        in_place = self._bound is not None and self._bound[0] == tuple(layout)
-        blob = self._bound[1] if in_place else torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         views = layout_views(blob, layout)
         pairs = [(store.tables[k], views[k]) for k, _, _, _, _ in layout]
-        for at in range(0, len(pairs), COLLATE_MAX_FIELDS):            # (one launch for up to sixteen fields: every recipe's)
-            ops.collate_fields(ids, pairs[at:at + COLLATE_MAX_FIELDS])
-        self.n_collate += 1
-        self.n_in_place += int(in_place)
         clip_ids = views.pop(IDS_KEY)
         out = {}
         for k in store.keys:
             out[k] = store.features_of(clip_ids, B) if k == store.feature_key else views[k]
         out['_layout'], out['_dev_blob'] = layout, blob
+        return out, pairs
+
+    def collate_ids(self, ids, B):
+        """one batch from ``B`` sample ids on the device (int32; validated by the caller)"""
+        from . import ops
+        from ._lib import COLLATE_MAX_FIELDS
+        layout, nbytes = self.layout(B)
+        in_place = self._bound is not None and self._bound[0] == tuple(layout)
+        blob = self._bound[1] if in_place else torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        out, pairs = self._batch_of(layout, blob, B)
+        for at in range(0, len(pairs), COLLATE_MAX_FIELDS):            # (one launch for up to sixteen fields: every recipe's)
+            ops.collate_fields(ids, pairs[at:at + COLLATE_MAX_FIELDS])
+        self.n_collate += 1
+        self.n_in_place += int(in_place)
         return out
+
+    def collate_at(self, layout, blob):
+        """The launches that draw the batch at the device cursor into ``blob`` (a buffer of ``layout``) and move the cursor on by
+        the batch, on the current stream: what a recorded train step puts at the head of its list (``bind(..., in_list=True)``)."""
+        from . import ops
+        from ._lib import COLLATE_MAX_FIELDS
+        B = int(layout[-1][4][0])
+        assert self.ids_base is not None and self._cursor.at is not None, 'stable_ids and cursor_to_last() first'
+        _, pairs = self._batch_of(layout, blob, B)
+        for at in range(0, len(pairs), COLLATE_MAX_FIELDS):
+            ops.collate_fields_at(self.ids_base, self._cursor.word, B, pairs[at:at + COLLATE_MAX_FIELDS])
+        ops.counter_add(self._cursor.word, [B])
+        self._cursor.advanced(B)
+
+    @property
+    def cursor(self):
+        """the int64 device word of the in-list draw (None before the first in-list use)"""
+        return self._cursor.word
+
+    @property
+    def last_in_list(self) -> bool:
+        """was the batch handed out last left for a list to draw (it holds its values only once that list has run)?"""
+        return self._last is not None and self._last[2]
+
+    def can_draw_last_in_list(self) -> bool:
+        """may a list be recorded that draws the batch handed out last (its ids sit in the stable buffer)?"""
+        return self.stable_ids and self._last is not None and self.ids_base is not None
+
+    def cursor_to_last(self):
+        """the device cursor names the batch handed out last: what a list that is about to be recorded on that batch draws again"""
+        self._cursor.expect(self._last[0])
+
+    def _in_list(self, at, B):
+        """the bound buffer's batch, drawn by the list that owns the buffer when it runs: no launch here"""
+        self._cursor.expect(at)
+        self._cursor.advanced(B)            # (what the list leaves behind)
+        if self._bound_out is None:
+            self._bound_out = self._batch_of(self._bound[0], self._bound[1], B)[0]
+        self.n_in_list += 1
+        return dict(self._bound_out)
+
+    def materialise(self, batch):
+        """the batch handed out last, collated now into a buffer of its own -- for a batch yielded in-list whose list did not run
+        (its buffer still holds the previous batch); the cursor is written again before the next in-list batch"""
+        at, B, in_list = self._last
+        if not in_list:
+            return batch
+        self._cursor.invalidate()
+        bound = self._bound
+        self.unbind()
+        try:
+            out = self.collate_ids(self.ids_base[at:at + B], B)
+        finally:
+            self._bound = bound
+        self._last = (at, B, False)
+        return out
+
+    def _upload(self, flat):
+        """the epoch's ids into ``ids_base``: one host-to-device copy; the buffer is made once, for the dataset's length, and kept"""
+        import numpy as np
+        from ._lib import LirecError
+        n = int(flat.size)
+        if self.ids_base is None or self.ids_base.numel() < n:
+            if self._bound is not None and self._bound[2]:
+                raise LirecError('BlockLoader: an epoch of %d ids does not fit the id buffer a recorded step reads (%d)'
+                                 % (n, self.ids_base.numel()))
+            self.ids_base = torch.empty(max(n, len(self.dataset), 1), dtype=torch.int32, device=self.device)
+        if n:
+            self.ids_base[:n].copy_(torch.from_numpy(flat.astype(np.int32)))
+        return self.ids_base[:n]
 
     def __iter__(self):
         import numpy as np
@@ -273,9 +392,13 @@ class BlockLoader:
         flat = np.fromiter((i for idx in todo for i in idx), dtype=np.int64)
         if flat.size and (int(flat.min()) < 0 or int(flat.max()) >= self.store.n):
             raise IndexError('BlockLoader: the sampler drew a sample id outside [0, %d)' % self.store.n)
-        ids = torch.from_numpy(flat.astype(np.int32)).to(self.device)         # the epoch's order: one host-to-device copy
+        # the epoch's order: one host-to-device copy
+        ids = self._upload(flat) if self.stable_ids else torch.from_numpy(flat.astype(np.int32)).to(self.device)
         at = 0
         for idx in todo:
             B = len(idx)
-            yield self.collate_ids(ids[at:at + B], B)
+            b = self._bound
+            in_list = self.stable_ids and b is not None and b[2] and B > 0 and b[0] == tuple(self.layout(B)[0])
+            self._last = (at, B, in_list)
+            yield self._in_list(at, B) if in_list else self.collate_ids(ids[at:at + B], B)
             at += B

@@ -1247,6 +1247,22 @@ def collate_fields(ids, fields):
     check(lib().lirec_collate_fields(_p(ids), B, arr, len(fields), _stream()), 'lirec_collate_fields')
 
 
+def collate_fields_at(ids_base, cursor, B, fields):
+    """``collate_fields`` for the ``B`` ids at ``ids_base[cursor[0]:]`` -- ``cursor``: an int64 device word the kernel reads when it
+    runs, so the launch, replayed from a command list, draws the batch the cursor names then (lirec_collate_fields_at).  The cursor
+    is not moved (``counter_add(cursor, [B])`` behind the call does that); trusted: 0 <= cursor[0] <= ids_base.numel() - B."""
+    assert ids_base.dtype == torch.int32 and ids_base.is_contiguous() and ids_base.is_cuda and ids_base.numel() >= B >= 1, B
+    assert cursor.dtype == torch.int64 and cursor.is_cuda and cursor.numel() >= 1 and len(fields) <= _lib.COLLATE_MAX_FIELDS, len(fields)
+    if not fields:
+        return
+    arr = (_lib.CollateField * len(fields))()
+    for f, (src, dst) in enumerate(fields):
+        rb = src[0].numel() * src.element_size()
+        assert src.is_contiguous() and dst.is_contiguous() and dst.numel() * dst.element_size() == B * rb, (f, tuple(src.shape), tuple(dst.shape))
+        arr[f].src, arr[f].row_bytes, arr[f].dst = _p(src), rb, _p(dst)
+    check(lib().lirec_collate_fields_at(_p(ids_base), _p(cursor), B, arr, len(fields), _stream()), 'lirec_collate_fields_at')
+
+
 def collate_workspace(n_clip_all, n_track_all, device):
     """A workspace for ``collate_resident`` over stores of these row counts (uint8; the library clears it in every call)."""
     need = int(lib().lirec_collate_workspace_bytes(int(n_clip_all), int(n_track_all)))

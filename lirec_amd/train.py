@@ -24,7 +24,7 @@ import torch
 from . import parallel
 from .config import opt
 from .features import CLIP_WEIGHT, PinnedPool
-from .loader import ResidentLoader, make_loader
+from .loader import BlockLoader, ResidentLoader, make_loader
 from .test import testing
 from .util import Averaging, ModelSaver, ema_entry, save_checkpoint
 
@@ -74,10 +74,27 @@ def _flag_key(optimizer=None):
 def _recordable(model, batch) -> bool:
     """May this loader batch be stepped on by a recorded train step?  (opt.recorded_training; a CUDA model of the hot path; the
     batch's tensors in one device buffer -- features.batch_to_device -- with its pieces in the resident store.)  Under data
-    parallelism this is one rank's view: the loop takes the decision for all ranks (`_all_ranks`)."""
-    return bool(getattr(opt, 'recorded_training', True)) and '_dev_blob' in batch and 'piece_store' in batch and \
-        hasattr(model, '_run_forward') and model.flat_params().is_cuda and getattr(opt, 'pieces_gather', True) and \
-        getattr(opt, 'pieces_q32b', False) and getattr(opt, 'layer1_planes', False)
+    parallelism this is one rank's view: the loop takes the decision for all ranks (`_all_ranks`).
+    Second form -- a batch of a resident BLOCK store (lirec_amd.loader.BlockLoader), when ``opt.record_block_store`` asks for it:
+    one process, the batch's tensors in one device buffer of a static layout, its features a two-plane ``Q32Block`` that names
+    its samples, the gathered q32b layer-1 kernels in force (``opt.layer1_planes``, GEMM mode 2).  Anything else steps eagerly."""
+    if not (bool(getattr(opt, 'recorded_training', True)) and '_dev_blob' in batch and hasattr(model, '_run_forward')
+            and model.flat_params().is_cuda and getattr(opt, 'layer1_planes', False)):
+        return False
+    if 'piece_store' in batch:
+        return bool(getattr(opt, 'pieces_gather', True) and getattr(opt, 'pieces_q32b', False))
+    from . import ops
+    f = batch.get('features')
+    return bool(_block_store_mode()) and parallel.world_info()[1] == 1 and '_layout' in batch and \
+        isinstance(f, ops.Q32Block) and f.clip_ids is not None and f.planes == 2 and ops.get_gemm_mode() == 2
+
+
+def _block_store_mode() -> str:
+    """``opt.record_block_store``, checked: '' (eager steps over a block store), 'bind' or 'list'"""
+    mode = getattr(opt, 'record_block_store', '')
+    if mode not in ('', 'bind', 'list'):
+        raise ValueError('opt.record_block_store must be \'\', \'bind\' or \'list\', not %r' % (mode,))
+    return mode
 
 
 def _all_ranks(flag: bool, world: int) -> bool:
@@ -99,6 +116,8 @@ class _Stepper:
     static_layout) is stepped on by a RECORDED train step (lirec_amd.graph): the step's launches re-issued from C for ~0.1 ms of
     host time instead of ~0.6 ms of Python -- the loop is host-bound otherwise.  Recorded once, on the fourth such batch in a row
     (that batch's own, single step); a batch of another layout (the last, short one of an epoch) takes the eager step.
+    A device-collating loader (``binds``) writes a batch of the recorded layout straight into the step's inputs; over a block store
+    under ``opt.record_block_store = 'list'`` the recorded list draws its batch itself (``in_list``; BlockLoader.collate_at).
     State: ``recorded`` (None: no step is) with its ``layout``, ``blob`` (input buffer), ``flags`` (the ``_flag_key`` it has baked
     in) and ``released``; ``run`` batches in a row had ``last_layout``; ``run_barred``: a recording failed in this run, none is tried
     before the layout changes; ``overwrite_ok``: the coverage check's verdicts by (layout, flag key) -- a flag flip (:49-51) may
@@ -106,7 +125,8 @@ class _Stepper:
 
     def __init__(self, model, loss, optimizer, world, loader, stats, to_device=None, say=_print):
         self.model, self.loss, self.optimizer, self.world, self.loader, self.stats = model, loss, optimizer, world, loader, stats
-        self.to_device, self.say, self.binds = to_device, say, isinstance(loader, ResidentLoader)
+        self.to_device, self.say, self.binds = to_device, say, isinstance(loader, (ResidentLoader, BlockLoader))
+        self.in_list = False              # (the recorded step draws its batch itself: opt.record_block_store = 'list')
         self.recorded = self.layout = self.blob = self.flags = self.last_layout = None
         self.released = self.run_barred = self.dp_gave_up = False
         self.run, self.overwrite_ok = 0, {}
@@ -116,13 +136,18 @@ class _Stepper:
         self.recorded, self.run, self.run_barred = None, 0, False
 
     def begin_epoch(self):
+        if isinstance(self.loader, BlockLoader):
+            # (a list that draws its own batches reads the epoch's ids at ONE address: asked for before the epoch is drawn)
+            self.loader.stable_ids = _block_store_mode() == 'list' and self.world == 1
         if self.recorded is not None and self.flags != _flag_key(self.optimizer):      # (a recipe flag changed, :49-51)
             self._forget()
 
     def before_draw(self):
         """a device-collating loader is told before every draw where the recorded step's inputs are, so that a batch of that
         layout is written there -- behind the previous replay on this stream -- and nowhere else"""
-        if self.binds and self.recorded is not None:
+        if self.binds and self.recorded is not None and self.in_list:
+            self.loader.bind(self.layout, self.blob, in_list=True)
+        elif self.binds and self.recorded is not None:
             self.loader.bind(self.layout, self.blob)
         elif self.binds:
             self.loader.unbind()
@@ -138,6 +163,8 @@ class _Stepper:
             self._forget()                # (the learning rate changed inside the epoch)
         if self.recorded is not None and lay == self.layout:
             return self._replay(batch), len(batch['labels'])
+        if isinstance(self.loader, BlockLoader) and self.loader.last_in_list:
+            batch = self.loader.materialise(batch)      # (handed out for a list that will not run -- the step was forgotten: collated now)
         if self.to_device is not None:
             batch = self.to_device(batch)     # (every small tensor of the batch in ONE host-to-device copy: features.collate)
         n = len(batch['labels'])
@@ -179,10 +206,25 @@ class _Stepper:
         could not releases its step -- replaying alone, its collectives would come from other positions -- the step taken all the same."""
         from .graph import RecordedTrainStep
         lval = None
+        # (a block store under opt.record_block_store = 'list': the list begins with the launches that draw its batch at the loader's
+        #  device cursor -- set here to this batch, which the recording step then writes once more, the same bytes)
+        # (a loss that converts the batch's labels on the host's side in front of every replay -- the cross-entropy loss's int32
+        #  copies, loss.before_replay -- would read the buffer BEFORE the list has drawn the batch: such a step is recorded as
+        #  under 'bind', the batch written by the loader's call)
+        host_reads = getattr(self.loss, 'needs_before_replay', None)
+        in_list = isinstance(self.loader, BlockLoader) and _block_store_mode() == 'list' and self.loader.can_draw_last_in_list() and \
+            not (host_reads is not None and host_reads())
+        draw = None
+        if in_list:
+            self.loader.cursor_to_last()
+            loader, blob = self.loader, batch['_dev_blob']
+            draw = lambda: loader.collate_at(lay, blob)
+        extra = {'draw': draw} if draw is not None else {}      # (only when asked for: the call every other path makes is what it was)
         try:
             g = RecordedTrainStep(self.model, self.loss, self.optimizer, batch, warmup=0,
-                                  overwrite=self.overwrite_ok.get((lay, _flag_key(self.optimizer))))
+                                  overwrite=self.overwrite_ok.get((lay, _flag_key(self.optimizer))), **extra)
             self.recorded, self.layout, self.blob, self.flags, self.released = g, lay, batch['_dev_blob'], _flag_key(self.optimizer), False
+            self.in_list = in_list
             lval = g.loss_out.clone()
         except Exception as e:
             self.say('recorded train step not used: %s' % str(e)[:160])
@@ -197,8 +239,10 @@ class _Stepper:
         if self.released:
             self.recorded.resume()
             self.released = False
-        if batch.get('_dev_blob') is not self.blob:       # (else ResidentLoader wrote the batch into the step's inputs: nothing to copy)
-            self.blob.copy_(batch['_blob'], non_blocking=True)
+        assert not self.in_list or batch.get('_dev_blob') is self.blob, 'a list that draws its own batch runs on its bound buffer only'
+        if batch.get('_dev_blob') is not self.blob:       # (else the loader wrote the batch into the step's inputs: nothing to copy)
+            # (a host buffer -- or, a device-collated batch that was not written in place, its device buffer: one copy on this stream)
+            self.blob.copy_(batch['_blob'] if '_blob' in batch else batch['_dev_blob'], non_blocking=True)
             PinnedPool.copied(batch.get('_slots'))
             self.stats['input_copies'] += 1
         self.stats['replays'] += 1
