@@ -50,7 +50,8 @@ enum {
 /* dropout sites (one counter stream each) */
 enum { LIREC_SITE_H1_INTS = 0, LIREC_SITE_H1_CTX = 1, LIREC_SITE_E_INTS = 2,
        LIREC_SITE_E_CTX = 3, LIREC_SITE_GATE = 4,
-       LIREC_SITE_TRACK_SAMPLE = 5 };    /* the uniform draw of the positive-track sampler (lirec_margin_loss, sample) */
+       LIREC_SITE_TRACK_SAMPLE = 5,      /* the uniform draw of the positive-track sampler (lirec_margin_loss, sample) */
+       LIREC_SITE_CONTEXT_DRAW = 6 };    /* the per-epoch draw from over-long context lists (lirec_draw_context) */
 
 /* Row selection inside the feature block.  Logical row n of an operand maps to
  * physical row (n / group) * group_stride + (n % group) + group_off of the
@@ -1013,6 +1014,43 @@ int lirec_collate_fields(const int32_t* ids, int32_t B, const lirec_collate_fiel
  * NULL src or dst.  nf == 0: no launch, LIREC_OK.  (Added to ABI 124 without a new number: one new export, no struct changes.) */
 int lirec_collate_fields_at(const int32_t* ids_base, const int64_t* cursor, int32_t B, const lirec_collate_field* fields, int32_t nf,
                             lirec_stream_t stream);
+
+/* ---- train-mode context sampling (resident piece store) ----------------------------
+ * The reference's training loader draws np.random.choice(L, R, replace=False) from a context list of L > R clips on every
+ * __getitem__ (mixed_utils/classification_dataloader.py:387, :405, :488).  Here the draw is made ONCE PER EPOCH for the whole
+ * dataset, in place in the resident index_rows table that lirec_collate_resident reads; it is a function of (seed, epoch, sample,
+ * candidate) alone -- lirec_amd.features.draw_context is the same rule in numpy.  A slot is a (sample s, candidate c) with an
+ * over-long list; its id is s * T_max + c, i.e. its row of index_rows seen as [N * T_max, R + 1, 3].
+ *   slot_dst    int32 [S]       slot ids (read as uint32)
+ *   slot_off    int32 [S + 1]   ascending; the list of slot i is pool_rows[slot_off[i] .. slot_off[i + 1])
+ *   pool_rows   int32 [P, 3]    (clip-piece row, track-1 row, track-2 row) of every list entry
+ *   index_rows  int32 [N, E, 3] E = T_max * (R + 1); written in place
+ *   seed, epoch                 by value
+ * Entry j < L of slot i gets the key
+ *   (uint64(word 0 of philox4x32_10(counter = (j, slot, LIREC_SITE_CONTEXT_DRAW, epoch), key = (seed lo, seed hi))) << 32) | j
+ * and index_rows[slot, 1 + p, 0..2] = pool_rows[slot_off[i] + j_p] for p < R, j_p the entry with the p-th smallest key.  The keys of
+ * a slot are distinct, so nothing depends on an order of execution: two calls give the same bytes.  Row 0 of the slot and every
+ * other element of the table are not touched; every written element has one writer.  ONE launch, one workgroup per slot, a
+ * slot's keys in LDS (8 bytes each: 32 KiB at LIREC_CONTEXT_LIST_MAX entries); exact integer work, plain vector stores.
+ * TRUSTED, not checked on the device: every slot id below N * T_max, slot_off ascending from 0 to P with R < L <=
+ * LIREC_CONTEXT_LIST_MAX per slot, every entry of pool_rows in [-1, n_all) of its store.  The host validates the tables once when
+ * it uploads them.  (A list outside (0, LIREC_CONTEXT_LIST_MAX] is skipped by the kernel.)  The collate calls that read the table
+ * must be ordered around the call: the same stream.
+ * LIREC_EINVAL before any device call (also under the host-side dry run) for: a NULL struct; S negative; R < 1; E < R + 1; with
+ * S > 0: a NULL slot_dst, slot_off, pool_rows or index_rows; a pointer that is not 4-byte aligned.  S == 0: no launch, LIREC_OK
+ * (the checks come first).  Recorded into a command list like every other launch (added to ABI 124 without a new number: one new
+ * export and a new struct, index 41 of lirec_abi_sizeof; 24 .. 40 stay unassigned). */
+#define LIREC_CONTEXT_LIST_MAX 4096
+typedef struct {
+  const int32_t* slot_dst;                /* [S] */
+  const int32_t* slot_off;                /* [S + 1] */
+  const int32_t* pool_rows;               /* [P, 3] */
+  int32_t* index_rows;                    /* [N, E, 3] */
+  uint64_t seed;
+  uint32_t epoch;
+  int32_t S, R, E;
+} lirec_draw_context_args;
+int lirec_draw_context(const lirec_draw_context_args* a, lirec_stream_t stream);
 
 /* ---- feature assembly ---------------------------------------------
  * The reference's loader tiles every row of the (B, T, R+1, D) feature block on the host as

@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get('LIREC_LIB_PATH') or os.path.join(_HERE, 'liblirec_hip
 MAX_SEG = 4
 DEFAULT_GEMM_MODE = 2          # 0 exact f32-input MFMA, 1 naive cross-check, 2 split-precision bf16x3 MFMA (default), 3 single-pass bf16 on the large GEMMs
 
-SITE_H1_INTS, SITE_H1_CTX, SITE_E_INTS, SITE_E_CTX, SITE_GATE, SITE_TRACK_SAMPLE = 0, 1, 2, 3, 4, 5
+SITE_H1_INTS, SITE_H1_CTX, SITE_E_INTS, SITE_E_CTX, SITE_GATE, SITE_TRACK_SAMPLE, SITE_CONTEXT_DRAW = 0, 1, 2, 3, 4, 5, 6
 ABI_VERSION = 124
 LIREC_EINVAL = 10001
 
@@ -180,6 +180,15 @@ class CollateArgs(C.Structure):
                 ('fields', CollateField * COLLATE_MAX_FIELDS)]
 
 
+class DrawContextArgs(C.Structure):
+    """lirec_draw_context_args: the per-epoch draw from over-long context lists, in place in the resident index (lirec_draw_context)"""
+    _fields_ = [('slot_dst', _vp), ('slot_off', _vp), ('pool_rows', _vp), ('index_rows', _vp), ('seed', C.c_uint64),
+                ('epoch', C.c_uint32), ('S', _i32), ('R', _i32), ('E', _i32)]
+
+
+CONTEXT_LIST_MAX = 4096       # LIREC_CONTEXT_LIST_MAX
+
+
 class FeatureRows(C.Structure):
     """lirec_feature_rows: the batch's sample ids into a resident block store (lirec_set_feature_rows)"""
     _fields_ = [('clip_ids', _vp), ('n_clips', _i32), ('rows_per_clip', _i32), ('store_rows', _i64)]
@@ -288,6 +297,7 @@ _PROTOS = {
     'lirec_collate_resident': (_i32, [C.POINTER(CollateArgs), _vp]),
     'lirec_collate_fields': (_i32, [_vp, _i32, C.POINTER(CollateField), _i32, _vp]),
     'lirec_collate_fields_at': (_i32, [_vp, _vp, _i32, C.POINTER(CollateField), _i32, _vp]),
+    'lirec_draw_context': (_i32, [C.POINTER(DrawContextArgs), _vp]),
     'lirec_cast_f64_f32': (_i32, [_vp, _vp, _i64, _vp]),
     'lirec_grid_pool': (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i64, _vp]),
     'lirec_rows_max': (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _vp]),
@@ -339,7 +349,7 @@ def lib():
                                                                                                       (12, AdamGroupRange), (13, EvalTopkArgs),
                                                                                                       (15, PredictArgs), (17, CollateArgs),
                                                                                                       (19, ClipWeights), (21, FeatureRows),
-                                                                                                      (23, CollateField)]:
+                                                                                                      (23, CollateField), (41, DrawContextArgs)]:
         if L.lirec_abi_sizeof(which) != C.sizeof(st):
             raise LirecError('ABI mismatch for %s: library %d bytes, binding %d bytes'
                              % (st.__name__, L.lirec_abi_sizeof(which), C.sizeof(st)))

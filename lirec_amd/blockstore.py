@@ -196,6 +196,10 @@ class ResidentBlockDataset(torch.utils.data.Dataset):
 
     def __init__(self, dataset, device=None, feature_key='features'):
         from .config import opt
+        if getattr(dataset, 'context_draw', 'strided') == 'random':
+            # (the store would freeze whichever epoch's draw it was filled from; BlockStore.update is the way to change its samples)
+            raise LirecError('ResidentBlockDataset: a dataset with context_draw=\'random\' redraws its context every epoch, a block store '
+                             'holds one copy of every sample: make the store from a \'strided\' dataset')
         self.dataset = dataset
         self.block_store = BlockStore(dataset, opt.device if device is None else device, feature_key)
         self._weights = None

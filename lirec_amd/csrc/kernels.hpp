@@ -2632,6 +2632,37 @@ __global__ __launch_bounds__(256) void collate_fields_at_kernel(const CollateFie
   else collate_copy_rows<unsigned char>(f, ids, a.B);
 }
 
+// lirec_draw_context: one workgroup per slot.  The slot's L keys -- (Philox word << 32) | j, distinct -- go into LDS; entry j's rank
+// is the number of smaller keys (every lane of a wave reads the same LDS word at a time: a broadcast); the entries of rank p < R are
+// written to row 1 + p of the slot, three int32 each, one writer per element.  L^2 / 256 compares a thread: 64 k at L = 4096, once per
+// epoch.  A list outside (0, LIREC_CONTEXT_LIST_MAX] (the host validated the offsets) is left alone.
+constexpr int DRAW_THREADS = 256;
+__global__ __launch_bounds__(DRAW_THREADS) void draw_context_kernel(const lirec_draw_context_args a) {
+  __shared__ unsigned long long keys[LIREC_CONTEXT_LIST_MAX];
+  const int i = blockIdx.x, tid = threadIdx.x;
+  const int first = a.slot_off[i], L = a.slot_off[i + 1] - first;
+  if (L < 1 || L > LIREC_CONTEXT_LIST_MAX) return;                // (uniform over the workgroup: no barrier is skipped by some)
+  const unsigned slot = (unsigned)a.slot_dst[i];
+  const unsigned seed_lo = (unsigned)(a.seed & 0xffffffffull), seed_hi = (unsigned)(a.seed >> 32);
+  for (int j = tid; j < L; j += DRAW_THREADS) {
+    unsigned w[4];
+    philox4((unsigned)j, slot, (unsigned)LIREC_SITE_CONTEXT_DRAW, a.epoch, seed_lo, seed_hi, w);
+    keys[j] = ((unsigned long long)w[0] << 32) | (unsigned)j;
+  }
+  __syncthreads();
+  int* rows = a.index_rows + (long)slot * (a.R + 1) * 3;            // [R + 1, 3] of this (sample, candidate)
+  for (int j = tid; j < L; j += DRAW_THREADS) {
+    const unsigned long long mine = keys[j];
+    int rank = 0;
+    for (int k = 0; k < L; ++k) rank += keys[k] < mine ? 1 : 0;
+    if (rank < a.R) {
+      const int* src = a.pool_rows + (long)(first + j) * 3;
+      int* dst = rows + (long)(1 + rank) * 3;
+      dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2];
+    }
+  }
+}
+
 __global__ void dropout_mask_kernel(uint8_t* __restrict__ keep, int rows, int cols, unsigned seed_lo, unsigned seed_hi,
                                     const unsigned long long* __restrict__ seed_dev, unsigned site, unsigned thresh) {
   apply_seed_offset(seed_lo, seed_hi, seed_dev);

@@ -1147,6 +1147,7 @@ int lirec_abi_sizeof(int which) {
     case 19: return (int)sizeof(lirec_clip_weights);         // (18 stays unassigned)
     case 21: return (int)sizeof(lirec_feature_rows);         // (20 stays unassigned)
     case 23: return (int)sizeof(lirec_collate_field);        // (22 stays unassigned)
+    case 41: return (int)sizeof(lirec_draw_context_args);    // (24 .. 40 stay unassigned)
     default: return -1;
   }
 }
@@ -2911,6 +2912,18 @@ int lirec_collate_fields_at(const int32_t* ids_base, const int64_t* cursor, int3
   if (blocks > 1024) blocks = 1024;
   if (blocks < 1) blocks = 1;
   lirec::launch(collate_fields_at_kernel, dim3((unsigned)blocks, (unsigned)nf), dim3(256), 0, (hipStream_t)stream, a);
+  LIREC_CHECK_LAUNCH();
+  return LIREC_OK;
+}
+
+int lirec_draw_context(const lirec_draw_context_args* a, lirec_stream_t stream) {
+  if (!a) return LIREC_EINVAL;
+  if (a->S < 0 || a->R < 1 || a->E < (int64_t)a->R + 1) return LIREC_EINVAL;
+  const auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+  if (((at(a->slot_dst) | at(a->slot_off) | at(a->pool_rows) | at(a->index_rows)) & 3) != 0) return LIREC_EINVAL;
+  if (a->S > 0 && (!a->slot_dst || !a->slot_off || !a->pool_rows || !a->index_rows)) return LIREC_EINVAL;
+  if (a->S == 0) return LIREC_OK;
+  lirec::launch(draw_context_kernel, dim3((unsigned)a->S), dim3(DRAW_THREADS), 0, (hipStream_t)stream, *a);
   LIREC_CHECK_LAUNCH();
   return LIREC_OK;
 }

@@ -131,7 +131,11 @@ class ResidentLoader:
     ``bind(layout, blob)``: from now on a batch of that layout is written straight into ``blob`` (the input buffer of a recorded
     train step) instead of a buffer of its own; the call is stream-ordered behind whatever was enqueued before ``next()``, i.e.
     behind the previous replay.  ``unbind()`` ends it.  ``n_collate`` / ``n_in_place`` count the collate calls and those that wrote
-    into the bound buffer.  The workspace belongs to the loader: its batches must be drawn on one stream."""
+    into the bound buffer.  The workspace belongs to the loader: its batches must be drawn on one stream.
+
+    Over a ``PiecesDataset(context_draw='random')`` every ``iter()`` first brings the resident index to the draw of
+    ``dataset.epoch`` (``draw_context``: one launch per epoch, none when the table already holds that epoch); ``collate_ids``
+    called on its own reads the table as it is."""
 
     def __init__(self, dataset, batch_size=1, shuffle=False, sampler=None, drop_last=False, device='cuda'):
         if getattr(dataset, 'store', None) is None or getattr(dataset, 'emit', None) != 'pieces':
@@ -140,7 +144,7 @@ class ResidentLoader:
         if sampler is None:
             sampler = torch.utils.data.RandomSampler(dataset) if shuffle else torch.utils.data.SequentialSampler(dataset)
         self.batch_sampler = torch.utils.data.BatchSampler(sampler, batch_size, drop_last)
-        self.n_collate = self.n_in_place = 0
+        self.n_collate = self.n_in_place = self.n_draw = 0
         self._bound = None                  # (layout, blob)
         self._layouts = {}                  # batch size -> (layout, nbytes)
         self._tabs = self._ws = self._counts = None
@@ -197,11 +201,26 @@ class ResidentLoader:
         if flat.size and (int(flat.min()) < 0 or int(flat.max()) >= len(self.dataset)):
             raise IndexError('ResidentLoader: the sampler drew a sample id outside [0, %d)' % len(self.dataset))
         ids = torch.from_numpy(flat.astype(np.int32)).to(self.device)         # the epoch's order: one host-to-device copy
+        self.draw_context()
         at = 0
         for idx in todo:
             B = len(idx)
             yield self.collate_ids(ids[at:at + B], B)
             at += B
+
+    def draw_context(self):
+        """``PiecesDataset(context_draw='random')``: the resident index holds the draw of ``dataset.epoch`` from here on -- one
+        ``ops.draw_context`` on the current stream when it holds another epoch's (``n_draw`` counts them), behind the previous
+        epoch's collate calls and ahead of this epoch's.  The table belongs to the dataset: every loader over it sees the same."""
+        if getattr(self.dataset, 'context_draw', 'strided') != 'random':
+            return
+        from . import ops
+        tabs, epoch = self.dataset.device_tables(self.device), int(self.dataset.epoch)
+        if tabs['drawn_epoch'] != epoch:
+            ops.draw_context(tabs['slot_dst'], tabs['slot_off'], tabs['pool_rows'], tabs['index_rows'], self.dataset.R,
+                             self.dataset.context_seed, epoch)
+            tabs['drawn_epoch'] = epoch
+            self.n_draw += 1
 
 
 class _Cursor:

@@ -1298,3 +1298,21 @@ def collate_resident(ids, index_rows, n_clip_all, n_track_all, feature_index, cl
             (f, tuple(src.shape), tuple(dst.shape))
         a.fields[f].src, a.fields[f].row_bytes, a.fields[f].dst = _p(src), rb, _p(dst)
     check(lib().lirec_collate_resident(C.byref(a), _stream()), 'lirec_collate_resident')
+
+
+def draw_context(slot_dst, slot_off, pool_rows, index_rows, R, seed, epoch):
+    """The epoch's draw from every over-long context list, IN PLACE in the resident ``index_rows`` (int32 [N, T, R + 1, 3] or
+    [N, E, 3]) -- one launch on the current stream (lirec_draw_context, include/lirec_hip.h; ``features.draw_context`` is the rule in
+    numpy).  ``slot_dst`` int32 [S], ``slot_off`` int32 [S + 1], ``pool_rows`` int32 [P, 3]: trusted (``PiecesDataset.device_tables``
+    validated them).  ``seed``: 64 bits, ``epoch``: taken modulo 2^32, both by value."""
+    S, N = slot_dst.numel(), index_rows.shape[0]
+    i32 = lambda t: t.dtype == torch.int32 and t.is_contiguous()
+    assert i32(slot_dst) and i32(slot_off) and i32(pool_rows) and i32(index_rows), 'int32, contiguous'
+    assert slot_off.numel() == S + 1 and pool_rows.shape[-1] == 3 and index_rows.shape[-1] == 3, (S, tuple(slot_off.shape), tuple(pool_rows.shape))
+    if S == 0:                # (an empty tensor has no address to hand over; the library's answer to S == 0 is "no launch" too)
+        return
+    a = _lib.DrawContextArgs()
+    a.slot_dst, a.slot_off, a.pool_rows, a.index_rows = _p(slot_dst), _p(slot_off), _p(pool_rows), _p(index_rows)
+    a.seed, a.epoch = int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF
+    a.S, a.R, a.E = S, int(R), index_rows.numel() // (3 * N)
+    check(lib().lirec_draw_context(C.byref(a), _stream()), 'lirec_draw_context')
