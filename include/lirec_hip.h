@@ -743,6 +743,37 @@ int lirec_set_adam_clip(const float* coef_dev);
 int lirec_clip_finalize_guard(const double* partials, double* sq_dev, int32_t mode, float grad_scale, float max_norm, float* out,
                               int64_t* skipped_dev, int32_t count, lirec_stream_t stream);
 int lirec_set_adam_guard(const float* out_dev, const int64_t* skipped_dev);
+/* ---- gradient accumulation: one update per k micro-batches, decided on the device ---------
+ * For callers that re-issue the same launches every micro-step (a recorded step) and therefore cannot decide on the host whether a
+ * micro-step only accumulates ("hold") or closes its window and updates ("apply").  (Added to ABI 124 without a new number: exports
+ * only.)
+ *
+ * The WINDOW BLOCK: four int64 in device memory, 16-byte aligned -- [0] phase = the micro-batches already in the open window,
+ * 0 .. k-1, set by the caller before the first call; [1] hold, written by lirec_accum_begin; [2] a ticket, zero on entry and
+ * left zero; [3] reserved.
+ *
+ * lirec_accum_begin: the head launch of a micro-step, in the place of lirec_zero_count.  Zeroes the `bytes` at p (lirec_zero_count's
+ * rules: 16-byte aligned, any byte count) ONLY when the micro-step opens a window (phase 0); adds every_host[i] to ctr[i], i < n <= 4,
+ * on every call and apply_host[i] besides on the call that closes the window (phase + 1 >= k); leaves hold = 1 (a hold) or 0 (an
+ * apply) for the launches behind it on the stream, and the phase advanced (0 after an apply).  Every workgroup decides from the
+ * phase as it was on entry; the words are advanced by the workgroup that finishes last.  Nothing of an earlier step may still
+ * read the hold word when this launch runs: a caller joins its side streams before the next micro-step.  LIREC_EINVAL before any
+ * device call for: bytes < 0, p NULL with bytes > 0 or not 16-byte aligned, n outside 0..4, n > 0 with ctr, every_host or
+ * apply_host NULL, ctr not 8-byte aligned, win NULL or not 16-byte aligned, k < 1.
+ *
+ * lirec_set_adam_hold(hold_dev, k): while set, every lirec_adam_step, lirec_adam_step_counted, lirec_adam_step_ranges and
+ * lirec_adam_step_groups launch issued BY THE CALLING HOST THREAD does one uniform load of *hold_dev (word 1 of a window block) in
+ * front of everything else; non-zero: no element of p, g, m, v is read or written and -- unlike a guarded skip -- the
+ * count_dev / ticket / advance epilogue does NOT run (a hold is no update for a counting stream either).  Zero: the launch is the
+ * one issued without this call with the scale (float)((double)grad_scale / k) in the place of grad_scale, bit for bit.
+ * lirec_ema_step launches of the thread take the same gate.  With a guard or a clip coefficient also set the scale is multiplied
+ * on as ever, and a launch is a no-op when either flag says so.  The pointer is taken when the launch is issued: a recorded launch
+ * keeps it, every replay reads the word anew.  Host-thread state like lirec_set_adam_guard.  NULL, 0 (the default): exactly what
+ * is launched without this call.  A folded update (lirec_embed_bwd_args::adam) is REFUSED (LIREC_EINVAL) while a hold is set.
+ * LIREC_EINVAL for: hold_dev without k >= 1, k != 0 without hold_dev, hold_dev not 8-byte aligned. */
+int lirec_accum_begin(void* p, int64_t bytes, int64_t* ctr, const int64_t* every_host, const int64_t* apply_host, int32_t n,
+                      int64_t* win, int32_t k, lirec_stream_t stream);
+int lirec_set_adam_hold(const int64_t* hold_dev, int32_t k);
 /* ---- exponential moving average of the weights --------------------------------------
  * torch.optim.swa_utils.get_ema_multi_avg_fn(decay) / timm's ModelEmaV2 as a launch that rides behind an Adam launch on that
  * launch's stream: ema[i] <- fmaf(weight, p[i] - ema[i], ema[i]) for i < n, the difference rounded to fp32 first -- torch's

@@ -289,6 +289,8 @@ _PROTOS = {
     'lirec_set_adam_clip': (_i32, [_vp]),
     'lirec_clip_finalize_guard': (_i32, [_vp, _vp, _i32, _f32, _f32, _vp, _vp, _i32, _vp]),
     'lirec_set_adam_guard': (_i32, [_vp, _vp]),
+    'lirec_accum_begin': (_i32, [_vp, _i64, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _i32, _vp, _i32, _vp]),
+    'lirec_set_adam_hold': (_i32, [_vp, _i32]),
     'lirec_ema_step': (_i32, [_vp, _vp, _i64, _f32, _vp, _vp]),
     'lirec_eval_max_tracks': (_i32, [C.POINTER(EvalArgs), _vp]),
     'lirec_eval_clip_topk': (_i32, [C.POINTER(EvalTopkArgs), _vp]),

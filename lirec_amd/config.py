@@ -82,6 +82,7 @@ def defaults() -> dict:
         decoupled_weight_decay=False,  # FusedAdam: AdamW -- the decay multiplies the parameters by 1 - lr wd and stays out of the gradient
         skip_nonfinite=False,          # FusedAdam: a step whose trainable gradients hold a NaN / Inf is skipped, on the device (parameters, moments and the bias corrections' step untouched)
         ema_decay=0.0,                 # in (0.5, 1): FusedAdam keeps an exponential moving average of the weights, updated on the device behind every applied step (0: off)
+        accumulate_steps=1,            # FusedAdam: one update per this many micro-batches (gradient accumulation; 1: off)
         eval_ema=False,                # training(): the val / test evaluations run on the averaged weights (optimizer.ema_weights()); mode='train' stays on the live ones
         # per-clip loss weights (batch['clip_weight'], read by all five losses inside the loss kernel): 'sum' divides by the weight
         # sums (a weighted mean, as F.cross_entropy(weight=)), 'count' keeps the counts and the weights are plain multipliers

@@ -1270,6 +1270,49 @@ __global__ __launch_bounds__(256) void zero_count_kernel(uint4* __restrict__ p, 
   if (blockIdx.x == 0 && (int)threadIdx.x < ntail) tail[threadIdx.x] = 0;
 }
 
+// The head of a micro-step under gradient accumulation (lirec_accum_begin): zero_count_kernel with the decisions of the window
+// taken on the device.  `win`: the window block, four int64 in device memory --
+//   win[0]  phase: the micro-batches already in the open window, 0 .. k-1
+//   win[1]  hold:  written here for the launches BEHIND this one (the Adam / EMA launches under lirec_set_adam_hold): 1 while the
+//           micro-step only accumulates, 0 on the one that applies the update
+//   win[2]  ticket (its low int32; zero on entry, left zero)          win[3]  reserved
+// Every workgroup reads the phase, and zeroes its share of the buffer when the micro-step OPENS a window (phase 0).  The words
+// are advanced by ONE thread -- of the workgroup that arrives last, after every workgroup has read the phase and taken its
+// ticket behind its last store (adam_finish's scheme): no workgroup decides from a word a sibling may already have advanced.
+// That thread adds every[i] to ctr[i] on every call and apply[i] besides on the call that closes the window (phase + 1 >= k).
+// Nothing of an EARLIER step may still read win[1] when this launch runs: the accumulating step joins its side streams before
+// it ends (no deferred join: lirec_amd/graph.py), so stream order is all the flag needs.
+__global__ __launch_bounds__(256) void accum_begin_kernel(uint4* __restrict__ p, long n16, unsigned char* __restrict__ tail, int ntail,
+                                                          long long* ctr, long long e0, long long e1, long long e2, long long e3,
+                                                          long long a0, long long a1, long long a2, long long a3, int n,
+                                                          long long* win, int k) {
+  const long long phase = __hip_atomic_load(win, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (phase == 0) {
+    const uint4 z = {0u, 0u, 0u, 0u};
+    const long stride = (long)gridDim.x * blockDim.x;
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    for (; i + 3 * stride < n16; i += 4 * stride) { p[i] = z; p[i + stride] = z; p[i + 2 * stride] = z; p[i + 3 * stride] = z; }
+    for (; i < n16; i += stride) p[i] = z;
+    if (blockIdx.x == 0 && (int)threadIdx.x < ntail) tail[threadIdx.x] = 0;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int* ticket = reinterpret_cast<int*>(win + 2);
+    // (relaxed, as in adam_finish: the phase a workgroup decided from was consumed by its branch in front of the barrier above,
+    //  i.e. read before its ticket is taken; an acquire / release pair here writes the L2 back once per workgroup -- 2048 times
+    //  behind 74 MB of fresh zeros: measured 84 us against 12 for lirec_zero_count)
+    const int tk = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tk == (int)gridDim.x - 1) {
+      const bool apply = phase + 1 >= (long long)k;
+      const long long every[4] = {e0, e1, e2, e3}, app[4] = {a0, a1, a2, a3};
+      for (int i = 0; i < n; ++i) ctr[i] += every[i] + (apply ? app[i] : 0);
+      __hip_atomic_store(win + 1, apply ? 0ll : 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(win, apply ? 0ll : phase + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);           // ready for the next launch
+    }
+  }
+}
+
 // loader-typed reads: the pointer is declared fp32 / int32 in the ABI; with loader_types it is f64 / i64
 __device__ __forceinline__ float ld_f(const float* p, long i, bool f64) {
   return f64 ? (float)reinterpret_cast<const double*>(p)[i] : p[i];
@@ -1703,6 +1746,7 @@ struct AdamStep {
   const long long* step_dev;
   long long* count_dev; int* ticket; int advance;
   const float* scale; const long long* skipped;             // (ADAM_CLIP / ADAM_GUARD; not read otherwise)
+  const long long* hold;                                    // (HOLD kernels, lirec_set_adam_hold; not read otherwise)
 };
 // The five hyper-parameters by value in the launch
 struct AdamHyperArgs { float lr, beta1, beta2, eps, wd; };
@@ -1717,10 +1761,18 @@ __device__ __forceinline__ void adam_bias(float lr, float beta1, float beta2, lo
 
 // The head of every Adam kernel: the launch's step (ADAM_GUARD: less the skipped ones), the scale folded into `gscale`, and
 // -- ADAM_GUARD with the skip flag set -- `work` (elements or blocks) emptied, which ends the kernel's loop before it begins.
-struct AdamNow { long long t, counted; };                     // counted: *count_dev + 1, what adam_finish stores back
-template <int SCALE>
+// HOLD (lirec_set_adam_hold; gradient accumulation): one uniform load of the window's hold flag, which the step's head launch
+// (accum_begin_kernel) wrote earlier on this stream, IN FRONT of everything else.  Set: `work` emptied and `held` -- nothing of
+// p / g / m / v, of the counter or of the guard's block is read, and adam_finish leaves counter and ticket alone (a hold is no
+// update, for a counting stream either).  A template parameter like SCALE: the kernels without it hold neither load nor branch.
+struct AdamNow { long long t, counted; bool held; };          // counted: *count_dev + 1, what adam_finish stores back
+template <int SCALE, bool HOLD = false>
 __device__ __forceinline__ AdamNow adam_begin(const AdamStep& st, float& gscale, long& work) {
   AdamNow now;
+  now.held = false;
+  if constexpr (HOLD) {
+    if (*st.hold != 0) { work = 0; now.held = true; now.t = 1; now.counted = 0; return now; }
+  }
   now.counted = st.count_dev ? __hip_atomic_load(st.count_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1 : 0;
   now.t = st.count_dev ? now.counted : (st.step_dev ? *st.step_dev : (long long)st.step);
   if constexpr (SCALE == ADAM_CLIP) gscale *= *st.scale;
@@ -1737,8 +1789,9 @@ __device__ __forceinline__ bool adam_bias_on_device(const AdamStep& st) { return
 
 // The tail of every Adam kernel: with `advance`, the workgroup that finishes last stores the counter back.  Every workgroup has
 // read the counter by then: a workgroup takes its ticket behind its last element.
-__device__ __forceinline__ void adam_finish(const AdamStep& st, long long counted) {
-  if (st.count_dev && st.advance) {
+__device__ __forceinline__ void adam_finish(const AdamStep& st, const AdamNow& now) {
+  const long long counted = now.counted;
+  if (st.count_dev && st.advance && !now.held) {
     __syncthreads();
     if (threadIdx.x == 0) {
       const int tk = __hip_atomic_fetch_add(st.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1752,11 +1805,12 @@ __device__ __forceinline__ void adam_finish(const AdamStep& st, long long counte
 
 // The flat launch.  step_size / bc2_sqrt: the host's factors of a by-value step (lirec_adam_step), replaced here when the step
 // is on the device (graph replay) or the launch is guarded.
-template <int SCALE>
+template <int SCALE, bool HOLD = false>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, long n, const AdamHyperArgs hy,
                                                    float step_size, float bc2_sqrt, float gscale, const AdamStep st) {
-  const AdamNow now = adam_begin<SCALE>(st, gscale, n);
+  const AdamNow now = adam_begin<SCALE, HOLD>(st, gscale, n);
+  if (HOLD && now.held) return;                               // (uniform: the whole grid)
   if (adam_bias_on_device<SCALE>(st)) adam_bias(hy.lr, hy.beta1, hy.beta2, now.t, step_size, bc2_sqrt);
   const AdamFuse ad{p, g, m, v, step_size, bc2_sqrt, hy.beta1, hy.beta2, hy.eps, hy.wd, gscale, hy.lr, st.step_dev};
   const long stride = (long)gridDim.x * blockDim.x;
@@ -1764,7 +1818,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride)
     (void)adam4(ad, step_size, bc2_sqrt, 4 * i, reinterpret_cast<const f32x4*>(g)[i]);
   for (long i = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) (void)adam1(ad, step_size, bc2_sqrt, i, g[i]);
-  adam_finish(st, now.counted);
+  adam_finish(st, now);
 }
 
 // A table of ranges of a flat buffer, by value in the launch: range r = [off[r], off[r] + len[r]), off[r] a multiple of 4.  The
@@ -1861,12 +1915,13 @@ __device__ __forceinline__ void adam_range_block(const AdamFuse& ad, const Range
       [&](long at) { (void)adam1<DECOUPLED>(ad, step_size, bc2_sqrt, at, ad.g[at], decay); });
 }
 // The table launch: a range gives the bits adam_kernel gives on it with that range's step and hyper-parameters.
-template <int SCALE, class Hyper>
+template <int SCALE, class Hyper, bool HOLD = false>
 __global__ __launch_bounds__(256) void adam_table_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                          float* __restrict__ m, float* __restrict__ v,
                                                          const typename Hyper::Table rt, long nblocks, const Hyper hy,
                                                          float gscale, const AdamStep st) {
-  const AdamNow now = adam_begin<SCALE>(st, gscale, nblocks);
+  const AdamNow now = adam_begin<SCALE, HOLD>(st, gscale, nblocks);
+  if (HOLD && now.held) return;                               // (uniform: the whole grid)
   const bool on_device = adam_bias_on_device<SCALE>(st);
   AdamFuse ad{p, g, m, v, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, gscale, 0.f, st.step_dev};
   int cur = -1;
@@ -1882,7 +1937,7 @@ __global__ __launch_bounds__(256) void adam_table_kernel(float* __restrict__ p, 
     if (Hyper::kMayDecouple && decoupled) adam_range_block<true>(ad, rt, r, b, step_size, bc2_sqrt, decay);
     else adam_range_block<false>(ad, rt, r, b, step_size, bc2_sqrt, decay);
   }
-  adam_finish(st, now.counted);
+  adam_finish(st, now);
 }
 
 // The table launches with a clip coefficient keep kernels of their own, the table loop written out with scalar arguments.  On
@@ -2106,7 +2161,8 @@ __global__ __launch_bounds__(256) void cast_f64_f32_kernel(const double* __restr
 #define EMA_MAX_BLOCKS 2048
 __device__ __forceinline__ float ema1(float e, float p, float w) { return fmaf(w, __fsub_rn(p, e), e); }
 __global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ e, const float* __restrict__ p, long n, int head, float w,
-                                                  const float* __restrict__ guard) {
+                                                  const float* __restrict__ guard, const long long* __restrict__ hold) {
+  if (hold && *hold != 0) return;                             // (lirec_set_adam_hold: a held micro-step is no update of the average)
   if (guard && guard[2] != 0.f) return;
   const long stride = (long)gridDim.x * blockDim.x;
   const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -147,6 +147,8 @@ struct AdamThreadState {
   const float* clip;                     // lirec_set_adam_clip: the device float the launches scale their gradients by; NULL = off
   const float* guard;                    // lirec_set_adam_guard: the (coefficient, norm, skip) block and the count of skipped
   const int64_t* guard_skipped;          //   steps, both in device memory; NULL, NULL = off
+  const int64_t* hold;                   // lirec_set_adam_hold: the hold flag of an accumulation window (device int64) and the
+  int32_t hold_k;                        //   window's length k (the launches fold 1 / k into their scale); NULL, 0 = off
   const lirec_adam_hyper* hyper_row;     // lirec_set_adam_hyper_row: the device row a folded update reads its five hyper-parameters
                                          //   from; NULL = off: the values of lirec_fused_adam, by value
   const lirec_adam_hyper* map_table;     // lirec_set_adam_hyper_map: one row PER FIRST-LAYER PARAMETER -- the table, and the ranges
@@ -702,12 +704,13 @@ struct AdamLaunch {
   float gscale;
   AdamStep st;                        // the step's source; adam_launch adds the scale mode's operands
 };
-template <int SCALE>
+template <int SCALE, bool HOLD = false>
 static void adam_launch_as(const AdamLaunch& d, dim3 grid, hipStream_t s) {
   if (!d.groups && !d.ranges) {
-    lirec::launch(HIP_KERNEL_NAME(adam_kernel<SCALE>), grid, dim3(256), 0, s, d.p, d.g, d.m, d.v, (long)d.n, d.hy, d.step_size,
+    lirec::launch(HIP_KERNEL_NAME(adam_kernel<SCALE, HOLD>), grid, dim3(256), 0, s, d.p, d.g, d.m, d.v, (long)d.n, d.hy, d.step_size,
                   d.bc2_sqrt, d.gscale, d.st);
-  } else if constexpr (SCALE == ADAM_CLIP) {          // (the table forms with kernels of their own: see there)
+  } else if constexpr (SCALE == ADAM_CLIP && !HOLD) { // (the table forms with kernels of their own: see there; under a hold
+                                                      //  the template's, which take the gate)
     if (d.groups)
       lirec::launch(adam_groups_clip_kernel, grid, dim3(256), 0, s, d.p, d.g, d.m, d.v, *d.groups, d.nblocks, d.table, d.st.step,
                     d.gscale, d.st.step_dev, d.st.count_dev, d.st.ticket, d.st.advance, d.st.scale);
@@ -715,10 +718,10 @@ static void adam_launch_as(const AdamLaunch& d, dim3 grid, hipStream_t s) {
       lirec::launch(adam_ranges_clip_kernel, grid, dim3(256), 0, s, d.p, d.g, d.m, d.v, *d.ranges, d.nblocks, d.hy.beta1, d.hy.beta2,
                     d.hy.eps, d.hy.wd, d.gscale, d.hy.lr, d.st.step_dev, d.st.count_dev, d.st.ticket, d.st.advance, d.st.scale);
   } else if (d.groups) {
-    lirec::launch(HIP_KERNEL_NAME(adam_table_kernel<SCALE, AdamHyperTable>), grid, dim3(256), 0, s, d.p, d.g, d.m, d.v, *d.groups,
+    lirec::launch(HIP_KERNEL_NAME(adam_table_kernel<SCALE, AdamHyperTable, HOLD>), grid, dim3(256), 0, s, d.p, d.g, d.m, d.v, *d.groups,
                   d.nblocks, AdamHyperTable{d.table}, d.gscale, d.st);
   } else {
-    lirec::launch(HIP_KERNEL_NAME(adam_table_kernel<SCALE, AdamHyperByValue>), grid, dim3(256), 0, s, d.p, d.g, d.m, d.v, *d.ranges,
+    lirec::launch(HIP_KERNEL_NAME(adam_table_kernel<SCALE, AdamHyperByValue, HOLD>), grid, dim3(256), 0, s, d.p, d.g, d.m, d.v, *d.ranges,
                   d.nblocks, AdamHyperByValue{d.hy}, d.gscale, d.st);
   }
 }
@@ -729,7 +732,19 @@ static int adam_launch(AdamLaunch d, lirec_stream_t stream) {
   if (blocks < 1) blocks = 1;
   const dim3 grid((unsigned)blocks);
   const int pi = prof_start(PS_ADAM, s);
-  if (t_adam.guard) {                   // (guard over clip: AdamThreadState)
+  if (t_adam.hold) {                    // (lirec_set_adam_hold: the gated kernels, 1 / k folded into the scale they apply anyway)
+    d.st.hold = (const long long*)t_adam.hold;
+    d.gscale = (float)((double)d.gscale / (double)t_adam.hold_k);
+    if (t_adam.guard) {
+      d.st.scale = t_adam.guard; d.st.skipped = (const long long*)t_adam.guard_skipped;
+      adam_launch_as<ADAM_GUARD, true>(d, grid, s);
+    } else if (t_adam.clip) {
+      d.st.scale = t_adam.clip;
+      adam_launch_as<ADAM_CLIP, true>(d, grid, s);
+    } else {
+      adam_launch_as<ADAM_PLAIN, true>(d, grid, s);
+    }
+  } else if (t_adam.guard) {            // (guard over clip: AdamThreadState)
     d.st.scale = t_adam.guard; d.st.skipped = (const long long*)t_adam.guard_skipped;
     adam_launch_as<ADAM_GUARD>(d, grid, s);
   } else if (t_adam.clip) {
@@ -743,7 +758,7 @@ static int adam_launch(AdamLaunch d, lirec_stream_t stream) {
   return LIREC_OK;
 }
 static AdamStep adam_step_source(int32_t step, const int64_t* step_dev, int64_t* count_dev, int32_t* ticket, int32_t advance) {
-  return AdamStep{(int)step, (const long long*)step_dev, (long long*)count_dev, (int*)ticket, (int)(advance != 0), nullptr, nullptr};
+  return AdamStep{(int)step, (const long long*)step_dev, (long long*)count_dev, (int*)ticket, (int)(advance != 0), nullptr, nullptr, nullptr};
 }
 
 // One walk for every by-value table of ranges -- Adam's two and the norm's -- that checks the ranges, fills `rt` and counts the
@@ -790,6 +805,7 @@ static int fused_adam_fill(const lirec_fused_adam* adam, GemmGroup& g, AdamFuse&
   // (a clip coefficient needs the norm of the FINISHED gradient, which this very launch produces: the folded update cannot be
   //  clipped, and an unclipped one beside clipped launches would be a silent error)
   if (t_adam.clip || t_adam.guard) return LIREC_EINVAL;      // (a guard: the decision needs the finished gradient just the same)
+  if (t_adam.hold) return LIREC_EINVAL;                      // (a hold: the folded update has no gate -- it would apply on every micro-step)
   if (!adam->p || !adam->g || !adam->m || !adam->v || adam->n < 1 || (adam->step < 1 && !adam->step_dev)) return LIREC_EINVAL;
   if (((reinterpret_cast<uintptr_t>(adam->p) | reinterpret_cast<uintptr_t>(adam->g) | reinterpret_cast<uintptr_t>(adam->m) |
         reinterpret_cast<uintptr_t>(adam->v)) & 15) != 0 || (reinterpret_cast<uintptr_t>(adam->wq) & 255) != 0) return LIREC_EINVAL;
@@ -2768,6 +2784,14 @@ int lirec_set_adam_guard(const float* out_dev, const int64_t* skipped_dev) {
   return LIREC_OK;
 }
 
+int lirec_set_adam_hold(const int64_t* hold_dev, int32_t k) {
+  if (hold_dev == nullptr ? k != 0 : k < 1) return LIREC_EINVAL;          // (the pair: both, or NULL and 0)
+  if ((reinterpret_cast<uintptr_t>(hold_dev) & 7) != 0) return LIREC_EINVAL;
+  t_adam.hold = hold_dev;
+  t_adam.hold_k = k;
+  return LIREC_OK;
+}
+
 int lirec_ema_step(float* ema, const float* p, int64_t n, float weight, const float* guard_dev, lirec_stream_t stream) {
   static_assert(LIREC_EMA_MAX_BLOCKS == EMA_MAX_BLOCKS, "the header's grid cap is the kernel's");
   if (!ema || !p || n < 0) return LIREC_EINVAL;
@@ -2780,7 +2804,8 @@ int lirec_ema_step(float* ema, const float* p, int64_t n, float weight, const fl
   long blocks = (long)(((n - head) / 4 + 255) / 256);
   if (blocks > EMA_MAX_BLOCKS) blocks = EMA_MAX_BLOCKS;
   if (blocks < 1) blocks = 1;
-  lirec::launch(ema_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ema, p, (long)n, (int)head, weight, guard_dev);
+  lirec::launch(ema_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ema, p, (long)n, (int)head, weight, guard_dev,
+                (const long long*)t_adam.hold);
   LIREC_CHECK_LAUNCH();
   return LIREC_OK;
 }
@@ -2950,6 +2975,28 @@ int lirec_zero_count(void* p, int64_t bytes, int64_t* ctr, const int64_t* inc_ho
   if (blocks < 1) blocks = 1;
   lirec::launch(zero_count_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (uint4*)p, n16,
                 (unsigned char*)p + n16 * 16, ntail, (long long*)(n > 0 ? ctr : nullptr), inc[0], inc[1], inc[2], inc[3], (int)n);
+  LIREC_CHECK_LAUNCH();
+  return LIREC_OK;
+}
+
+int lirec_accum_begin(void* p, int64_t bytes, int64_t* ctr, const int64_t* every_host, const int64_t* apply_host, int32_t n,
+                      int64_t* win, int32_t k, lirec_stream_t stream) {
+  if (bytes < 0 || (!p && bytes > 0) || (reinterpret_cast<uintptr_t>(p) & 15) || n < 0 || n > 4 ||
+      (n > 0 && (!ctr || !every_host || !apply_host)) || (reinterpret_cast<uintptr_t>(ctr) & 7))
+    return LIREC_EINVAL;
+  if (!win || (reinterpret_cast<uintptr_t>(win) & 15) || k < 1) return LIREC_EINVAL;
+  long long every[4] = {0, 0, 0, 0}, app[4] = {0, 0, 0, 0};
+  for (int i = 0; i < n; ++i) { every[i] = every_host[i]; app[i] = apply_host[i]; }
+  const long n16 = (long)(bytes / 16);                    // (the loops of lirec_zero_count over the same buffer ...
+  const int ntail = (int)(bytes - n16 * 16);
+  long blocks = (n16 + 4 * 256 - 1) / (4 * 256);
+  // ... on a quarter of its grid at the most: every workgroup takes a ticket on ONE word, also on the calls that zero nothing --
+  // 2048 of them measured 26 us for a call that does nothing else; two workgroups per CU still fill the store path)
+  if (blocks > 512) blocks = 512;
+  if (blocks < 1) blocks = 1;
+  lirec::launch(accum_begin_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (uint4*)p, n16,
+                (unsigned char*)p + n16 * 16, ntail, (long long*)(n > 0 ? ctr : nullptr), every[0], every[1], every[2], every[3],
+                app[0], app[1], app[2], app[3], (int)n, (long long*)win, (int)k);
   LIREC_CHECK_LAUNCH();
   return LIREC_OK;
 }

@@ -207,6 +207,20 @@ class RecordedTrainStep:
         self.sync = getattr(model, 'grad_sync', None)
         if next_batch is not None and self.sync is not None:
             raise ValueError('RecordedTrainStep(next_batch=...): single-GPU form')
+        # (gradient accumulation, FusedAdam.accumulate_steps = k > 1: what the accumulating form is not built with is refused here,
+        #  with the other argument checks -- before anything of the optimiser or the device is touched)
+        self.accum = int(getattr(optimizer, 'accumulate_steps', 1))
+        self.win = None
+        if self.accum > 1:
+            if next_batch is not None:
+                raise LirecError('RecordedTrainStep(next_batch=...): the input-pipeline form is not built with gradient accumulation '
+                                 '(accumulate_steps = %d) -- record the plain form' % self.accum)
+            if self.sync is not None and self.sync.world > 1:
+                raise LirecError('RecordedTrainStep: gradient accumulation under data parallelism is not recorded (the bucket reductions '
+                                 'are issued from the host, which a replay gives no hold / apply decision) -- run the eager step')
+            if bool(getattr(optimizer, 'max_grad_norm', None)) or bool(getattr(optimizer, 'skip_nonfinite', False)):
+                raise LirecError('RecordedTrainStep: gradient accumulation with max_grad_norm / skip_nonfinite is not recorded (the norm '
+                                 'launches and the finalize have no hold gate) -- run the eager step')
         dev = model.flat_params().device
         optimizer._ensure_state()
         if hasattr(optimizer, 'fold_if_due'):
@@ -214,6 +228,12 @@ class RecordedTrainStep:
         # [forward calls (the dropout key's offset), Adam step, Adam step AS LANE 0 COUNTS IT]: the first two are advanced by the step's
         # first launch; the third by lane 0's own Adam launch, which under deferral may still run when the next step begins
         self.state = torch.tensor([model._fwd_train_calls, optimizer._step, optimizer._step], dtype=torch.int64, device=dev)
+        # Gradient accumulation (FusedAdam.accumulate_steps = k > 1): the list re-issues the same launches every micro-step, so the
+        # hold / apply decision lives beside ``state`` in device memory -- the WINDOW BLOCK of lirec_accum_begin, [phase, hold flag,
+        # ticket, -], which the step's head launch advances and the update's launches read (ops.adam_hold).  Constructed at any
+        # phase of a window: the block starts from the optimiser's host phase.
+        if self.accum > 1:
+            self.win = torch.tensor([optimizer.accum_phase, 0, 0, 0], dtype=torch.int64, device=dev)
         try:
             self._record(model, loss, optimizer, batch, warmup, next_batch, overwrite, dev)
         except BaseException:
@@ -236,6 +256,11 @@ class RecordedTrainStep:
         # (``overwrite``: the caller has run the check itself -- checked_overwrite_step on an earlier batch of this layout -- and
         #  passes its verdict: lirec_amd.train records with no warm-up step of its own)
         self.overwrite = bool(overwrite) if (overwrite is not None and getattr(model, 'grad_sync', None) is None) else False
+        # (gradient accumulation IS the accumulate mode of the weight-gradient kernels: never the overwrite mode, and therefore --
+        #  `defer` below needs it -- never a deferred side join: every micro-step joins lane 0 before it ends, so the head launch of
+        #  the next one rewrites the window's hold flag behind every launch that read it)
+        if self.accum > 1:
+            self.overwrite = False
         # Gradient clipping (FusedAdam.max_grad_norm): the norm needs every gradient of the step finished, so the clipped update is
         # issued whole on this stream behind backward -- no fused first-layer update, no un-joined side stream (`defer`)
         # (skip_nonfinite -- the guard -- takes the same route for the same reason: the decision needs the finished gradients)
@@ -249,7 +274,8 @@ class RecordedTrainStep:
         #  mode, which is checked on a warm-up step, then stays off)
         nwarm = max(int(warmup), 0)
         for w in range(nwarm):                     # lazy things happen here: scratch registered, side stream made, pools grown
-            self._one_step(check=(w == nwarm - 1 and self.sync is None and overwrite is None and bool(getattr(ops, 'set_grad_overwrite', None))))
+            self._one_step(check=(w == nwarm - 1 and self.sync is None and overwrite is None and self.accum == 1
+                                  and bool(getattr(ops, 'set_grad_overwrite', None))))
             self._advance_host()
         # The step is issued as a unit, so the update of the first-layer parameters -- the last gradients backward finishes -- is
         # folded into the launch that finishes them, which also keeps a q32b copy of the new weights for the next forward (no
@@ -257,7 +283,8 @@ class RecordedTrainStep:
         # q32b kernels (seen on the steps taken so far).
         self.fused = bool(self.sync is None and getattr(opt, 'fuse_dw1_adam', True) and getattr(model, 'last_layer1_planes', False)
                           and getattr(model, '_has_ints', False) and getattr(model, '_has_ctx', False)
-                          and hasattr(optimizer, 'arm_first_layer_update') and hasattr(model, 'refresh_w1q') and not clipping)
+                          and hasattr(optimizer, 'arm_first_layer_update') and hasattr(model, 'refresh_w1q') and not clipping
+                          and self.accum == 1)       # (accumulating: the plain update under the hold gate -- the fold has none)
         if self.fused and getattr(optimizer, 'device_hyper', False):
             # (parameter groups: the folded update reads one row of the hyper-parameter table per first-layer parameter -- all of
             #  them trainable and up to date, in one group or several, or frozen altogether)
@@ -319,6 +346,8 @@ class RecordedTrainStep:
         """the kernels read the dropout key's offset and the Adam step (the caller's and the side stream's count) from ``state``"""
         self.model._seed_dev, self.optim._step_dev = self.state[0:1], self.state[1:2]
         self.lanes.step_side_dev = self.state[2:3]
+        if getattr(self, 'win', None) is not None:
+            self.optim._win_dev = self.win       # (the window of an accumulating step: decided on the device from here on)
         if hasattr(self.loss, '_sample_key'):
             self.loss._sample_calls = self.model._fwd_train_calls
             self.loss._seed_dev = self.state[0:1]
@@ -338,7 +367,12 @@ class RecordedTrainStep:
             # make part of its keep bytes with the key after next (tests: ..._with_a_lagging_staging_stream_...)
             main, s3 = ops.current_stream_handle(), self._pre_lane.handle
             ops.stream_wait(main, s3)
-        self.optim.zero_grad(counters=(self.state, [1, 1]), zero=not over)
+        if self.accum > 1:
+            # (accumulating: lirec_accum_begin in the place of lirec_zero_count -- the key every micro-step, the Adam step on the
+            #  apply step, the zeroing pass where a window opens)
+            self.optim.begin_micro_step(self.state)
+        else:
+            self.optim.zero_grad(counters=(self.state, [1, 1]), zero=not over)
         if pipelined:
             # ... and the forward is told where they are
             self.lanes.prestaged = self.pre[k]
@@ -390,12 +424,16 @@ class RecordedTrainStep:
     def _advance_host(self):
         """Host mirrors of the device counters (checkpoints, switching back to the eager loop)."""
         self.model._fwd_train_calls += 1
-        self.optim._step += 1
-        self.optim._opt_called = True               # (torch's lr_scheduler: an optimiser step HAS been taken -- no order warning)
-        if hasattr(self.optim, '_advance_lags'):
-            self.optim._advance_lags()              # (frozen parameters sat this update out, as in the eager step())
-        if hasattr(self.optim, '_advance_ema'):
-            self.optim._advance_ema()               # (the host count behind ema_updates(); skipped steps come off on the device's word)
+        # (accumulating: the phase moves every micro-step; step, lags and the average's count on the apply step only -- the host
+        #  knows which it was without reading the device: the phase is a function of the number of calls)
+        applied = self.optim._advance_window() if getattr(self, 'accum', 1) > 1 else True
+        if applied:
+            self.optim._step += 1
+            self.optim._opt_called = True           # (torch's lr_scheduler: an optimiser step HAS been taken -- no order warning)
+            if hasattr(self.optim, '_advance_lags'):
+                self.optim._advance_lags()          # (frozen parameters sat this update out, as in the eager step())
+            if hasattr(self.optim, '_advance_ema'):
+                self.optim._advance_ema()           # (the host count behind ema_updates(); skipped steps come off on the device's word)
         if hasattr(self.loss, '_sample_key'):
             self.loss._sample_calls += 1
 
@@ -424,7 +462,10 @@ class RecordedTrainStep:
         # (the weight average: whether the lirec_ema_step launches were recorded, and the weight they carry by value.  Off, or an
         #  optimiser without one: today's key.)
         ema = getattr(optimizer, 'ema_decay', None)
-        return key + (('ema_decay', float(ema)),) if ema is not None else key
+        key = key + (('ema_decay', float(ema)),) if ema is not None else key
+        # (gradient accumulation: the head launch and the hold gate carry k by value.  Off (1): today's key.)
+        k = int(getattr(optimizer, 'accumulate_steps', 1))
+        return key + (('accumulate_steps', k),) if k > 1 else key
 
     def _check_core(self):
         if ops.get_gemm_mode() != self._gemm_mode:
@@ -532,6 +573,8 @@ class RecordedTrainStep:
         self.lanes.defer_join = False
         self.model._seed_dev = None
         self.optim._step_dev = None
+        if getattr(self, 'win', None) is not None:
+            self.optim._win_dev = None      # (the window goes on from the host's phase: eager steps in between continue it)
         self.lanes.step_side_dev = None
         if hasattr(self.loss, '_sample_key'):
             self.loss._seed_dev = None
@@ -546,6 +589,9 @@ class RecordedTrainStep:
         if hasattr(self.optim, 'fold_if_due'):
             self.optim.fold_if_due()      # (the eager steps in between may have changed the frozen set: before the counters attach)
         self.state.copy_(torch.tensor([self.model._fwd_train_calls, self.optim._step, self.optim._step], dtype=torch.int64), non_blocking=False)
+        if self.win is not None:
+            # (the window's phase from the host mirror, as the counters: no device read in either direction)
+            self.win.copy_(torch.tensor([self.optim.accum_phase, 0, 0, 0], dtype=torch.int64), non_blocking=False)
         self._attach_counters()
         if getattr(self, 'fused', False) and not self.model.refresh_w1q():
             raise RuntimeError('RecordedTrainStep.resume(): the q32b shadow of the first-layer weights cannot be rebuilt')

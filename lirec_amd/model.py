@@ -1633,7 +1633,8 @@ def create_model(n_classes, n_rels=0, verbose=False):
     optimizer = FusedAdam(model, lr=opt.lr, weight_decay=opt.weight_decay, max_grad_norm=getattr(opt, 'clip_grad_norm', 0.0) or None,
                           decoupled_weight_decay=bool(getattr(opt, 'decoupled_weight_decay', False)),
                           skip_nonfinite=bool(getattr(opt, 'skip_nonfinite', False)),
-                          ema_decay=getattr(opt, 'ema_decay', 0.0) or None)
+                          ema_decay=getattr(opt, 'ema_decay', 0.0) or None,
+                          accumulate_steps=int(getattr(opt, 'accumulate_steps', 1) or 1))
     if verbose:
         print(str(model))
         for name, param in model.named_parameters():

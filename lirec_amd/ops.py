@@ -967,6 +967,46 @@ class adam_guard:
         return False
 
 
+def accum_scale(grad_scale, k):
+    """the fp32 scale an update applies to the SUM of a window of ``k`` micro-batch gradients: (float)((double)(float)grad_scale
+    / k), what the launches under ``adam_hold`` compute from their ``grad_scale`` -- the eager apply step passes it by value"""
+    return C.c_float(C.c_float(float(grad_scale)).value / int(k)).value
+
+
+class adam_hold:
+    """``with ops.adam_hold(hold, k):`` -- the Adam and EMA launches this host thread issues inside read the device int64
+    ``hold`` (word 1 of an accumulation window block, written by ``accum_begin``) and do nothing while it is set; otherwise they
+    scale their gradients by ``accum_scale(grad_scale, k)`` (lirec_set_adam_hold); cleared on the way out, also when a launch
+    raises.  ``hold`` None: nothing is set."""
+
+    def __init__(self, hold, k=0):
+        self.hold, self.k = hold, int(k)
+
+    def __enter__(self):
+        if self.hold is not None:
+            assert self.hold.dtype == torch.int64 and self.k >= 1
+            check(lib().lirec_set_adam_hold(_p(self.hold), self.k), 'lirec_set_adam_hold')
+        return self
+
+    def __exit__(self, *exc):
+        if self.hold is not None:
+            check(lib().lirec_set_adam_hold(None, 0), 'lirec_set_adam_hold')
+        return False
+
+
+def accum_begin(t, ctr, every, apply, win, k):
+    """lirec_accum_begin, the head launch of a micro-step under gradient accumulation: zero the contiguous device tensor ``t``
+    when the micro-step opens a window, ``ctr[i] += every[i]`` always and ``+= apply[i]`` when it closes one, the hold flag and
+    the phase of the window block ``win`` (device int64[4], 16-byte aligned) advanced -- one launch."""
+    assert t.is_contiguous() and ctr.dtype == torch.int64 and len(every) == len(apply) <= 4 and ctr.numel() >= len(every)
+    assert win.dtype == torch.int64 and win.numel() >= 4 and win.is_contiguous()
+    n = len(every)
+    ev = (C.c_int64 * max(n, 1))(*[int(i) for i in every])
+    ap = (C.c_int64 * max(n, 1))(*[int(i) for i in apply])
+    check(lib().lirec_accum_begin(_p(t), t.numel() * t.element_size(), _p(ctr) if n else None, ev, ap, n, _p(win), int(k), _stream()),
+          'lirec_accum_begin')
+
+
 def ema_weight(decay):
     """the fp32 weight of one EMA update: the rounding of the double 1.0 - decay, as torch casts the Python scalar of
     ``lerp(ema, p, 1 - decay)``; ``decay`` outside (0.5, 1) -- NaN included -- is a ValueError (torch's lerp takes another

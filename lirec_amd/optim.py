@@ -73,6 +73,20 @@ parameter frozen from the start stays identical to its shadow, one frozen after 
 value; the alignment gaps, zeros in both buffers, stay zeros).  ``ema_weights()`` evaluates with the average, ``ema_state_dict()``
 is what a checkpoint keeps; ``state_dict()`` is unchanged.  timm's semantics; ``AveragedModel`` differs in its first update, which
 copies: ``ema_reset()`` after the first step reproduces it.
+
+Gradient accumulation (``accumulate_steps=k``, 1 = off by default): one update per k micro-batches with the stock loop --
+``zero_grad()``, backward, ``step()`` -- unchanged.  ``accum_phase`` counts the micro-batches already in the open window, a pure
+function of the number of ``step()`` calls.  ``zero_grad()`` zeroes only when the next micro-batch opens a window; calls 1 .. k-1 of
+``step()`` ("hold") touch nothing -- parameters, moments, average, ``_step``, lags and the skipped count keep their bits, and
+under data parallelism no bucket is reduced and nothing gathered (torch's ``no_sync``) --; call k ("apply") is one ordinary update
+on the accumulated gradient times ``grad_scale / k`` (``ops.accum_scale``: folded into the scale every Adam launch applies anyway,
+no pass over the gradients).  ``p.grad`` holds the UNSCALED SUM of the window so far (the clip's precedent: ``p.grad`` stays
+unclipped).  Clip, guard, AdamW, groups, frozen parameters and the average act at the apply step on the accumulated gradient: the
+norm is that of sum / k x grad_scale, a NaN anywhere in the window skips the window's update and counts ONE skipped step, the
+average takes one lerp per applied window; ``state_dict()`` counts updates.  A checkpoint taken inside a window does not hold the
+window's gradients.  In the eager loop the host takes the hold / apply decision; a recorded step re-issues the same launches every
+micro-step, so there it lives in device memory (``_win_dev``, the window block of lirec_accum_begin; the update's launches under
+``ops.adam_hold``) -- ``begin_micro_step`` is that step's head.
 """
 from __future__ import annotations
 
@@ -103,7 +117,8 @@ class FusedAdam(torch.optim.Optimizer):
             raise ValueError('Invalid weight_decay value: {}'.format(weight_decay))
 
     def __init__(self, model, lr=3e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5, max_grad_norm=None, param_groups=None,
-                 device_hyper=None, amsgrad=False, decoupled_weight_decay=False, skip_nonfinite=False, ema_decay=None):
+                 device_hyper=None, amsgrad=False, decoupled_weight_decay=False, skip_nonfinite=False, ema_decay=None,
+                 accumulate_steps=1):
         self.model = model
         self.lanes = getattr(model, 'lanes', None)       # (lirec_amd.lanes.StepLanes; None: every update on the caller's stream)
         params = list(model.parameters())
@@ -154,6 +169,70 @@ class FusedAdam(torch.optim.Optimizer):
         self._ema_skip_base = 0        # ... and skipped_total() at that moment: ema_updates() = done + calls - skipped since
         self._ema_done = 0
         self.ema_decay = ema_decay     # None: off; settable between steps (a recorded step is recorded again)
+        self._accum_k, self._accum_phase = 1, 0
+        self._win_dev = None           # device int64[4]: the window block while a recorded step holds the phase on the device (lirec_amd.graph)
+        self.accumulate_steps = accumulate_steps      # settable between windows (a recorded step is recorded again)
+
+    # -- gradient accumulation ------------------------------------------------------
+    @property
+    def accumulate_steps(self):
+        return self._accum_k
+
+    @accumulate_steps.setter
+    def accumulate_steps(self, k):
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError('FusedAdam.accumulate_steps must be an integer >= 1, not %r' % (k,))
+        if k != self._accum_k and self._accum_phase != 0:
+            raise RuntimeError('FusedAdam.accumulate_steps changed in the middle of a window (%d of %d micro-batches taken): change it '
+                               'after the step() that applies the window, or drop_window() first' % (self._accum_phase, self._accum_k))
+        if k != self._accum_k and self._win_dev is not None:
+            raise RuntimeError('FusedAdam.accumulate_steps changed while a recorded step holds the window on the device; release() '
+                               'the recorded step first')
+        self._accum_k = k
+        self._hold_sync()
+
+    @property
+    def accum_phase(self):
+        """host int: the micro-batches already in the open window, 0 .. accumulate_steps - 1 (0: the next one opens a window)"""
+        return self._accum_phase
+
+    @staticmethod
+    def window_after(phase, k):
+        """(phase after one more ``step()``, did that call apply?) -- the whole phase arithmetic: the call that finds k - 1
+        micro-batches in the window applies and closes it"""
+        return (0, True) if phase + 1 >= k else (phase + 1, False)
+
+    def _advance_window(self):
+        """one ``step()`` has been issued (the eager one, a replay: lirec_amd.graph); returns whether it applied"""
+        self._accum_phase, applied = self.window_after(self._accum_phase, self._accum_k)
+        self._hold_sync()
+        return applied
+
+    def drop_window(self):
+        """forget the open window: its micro-batches are dropped, the next ``zero_grad()`` zeroes (what ``training()`` does with a
+        partial window at its end).  Not while a recorded step holds the window on the device."""
+        if self._win_dev is not None:
+            raise RuntimeError('FusedAdam.drop_window(): a recorded step holds the window on the device; release() it first')
+        self._accum_phase = 0
+        self._hold_sync()
+
+    def _hold_sync(self):
+        """data parallelism: tell the gradient sync whether the NEXT backward belongs to a hold step -- its buckets are then not
+        reduced (torch's no_sync, automatic); the apply step's backward reduces the accumulated local gradients"""
+        sync = getattr(self.model, 'grad_sync', None)
+        if sync is not None and hasattr(sync, 'hold'):
+            sync.hold = self._accum_k > 1 and not self.window_after(self._accum_phase, self._accum_k)[1]
+
+    def _scale(self):
+        """what the update multiplies the gradient buffer by: ``grad_scale``, over k for the sum of a window"""
+        return self.grad_scale if self._accum_k == 1 else ops.accum_scale(self.grad_scale, self._accum_k)
+
+    def begin_micro_step(self, counters):
+        """lirec_amd.graph, accumulating form: the head launch of a recorded micro-step in the place of ``zero_grad(counters=)`` --
+        lirec_accum_begin on the window block: the dropout key's counter advanced every time, the Adam step (the caller's and
+        lane 0's, which issues no update of its own here) on the apply step only, the gradient buffer zeroed when a window opens"""
+        g = self.model.flat_grads(attach=True)
+        ops.accum_begin(g, counters, [1, 0, 0], [0, 1, 1], self._win_dev, self._accum_k)
 
     # -- exponential moving average of the weights ----------------------------------
     @property
@@ -468,6 +547,9 @@ class FusedAdam(torch.optim.Optimizer):
         increments): advanced by the same launch (lirec_amd.graph: the step counters of a replayed step).  ``zero=False``
         (lirec_amd.graph only): the counters alone -- the step's weight gradients overwrite the buffer (ops.set_grad_overwrite)."""
         g = self.model._flat_grad
+        self._hold_sync()
+        if self._accum_k > 1 and self._accum_phase != 0 and counters is None:
+            return                     # (inside a window: the micro-batches taken so far stay; p.grad is their unscaled sum)
         if counters is not None and not zero:
             ops.counter_add(counters[0], counters[1])
             return
@@ -577,10 +659,10 @@ class FusedAdam(torch.optim.Optimizer):
     def _finalize(self, partials, mode, count=False):
         """the finalize of the route: the guard's (bound 0 = no clipping) with the guard on, the clip's otherwise"""
         if self._guard_now:
-            ops.clip_finalize_guard(partials, self._clip_sq, mode, self.grad_scale, self._clip_now or 0.0, self._clip_out,
+            ops.clip_finalize_guard(partials, self._clip_sq, mode, self._scale(), self._clip_now or 0.0, self._clip_out,
                                     self._skipped_dev, count)
         else:
-            ops.clip_finalize(partials, self._clip_sq, mode, self.grad_scale, self._clip_now, self._clip_out)
+            ops.clip_finalize(partials, self._clip_sq, mode, self._scale(), self._clip_now, self._clip_out)
 
     def _scaled(self):
         """the context the route's Adam launches are issued in"""
@@ -612,6 +694,8 @@ class FusedAdam(torch.optim.Optimizer):
             return False
         if self._clip_max() is not None or self.skip_nonfinite:
             return False          # (the norm needs the finished first-layer gradients: they are updated with the rest, clipped)
+        if self._accum_k > 1:
+            return False          # (the fold has no hold gate: it would update on every micro-batch)
         row = hmap = None
         if self.resolve_device_hyper():
             # (every first-layer parameter trainable and up to date.  All of them in ONE group: the launch reads one row -- of the
@@ -783,6 +867,16 @@ class FusedAdam(torch.optim.Optimizer):
     def step(self, closure=None):
         loss = closure() if closure is not None else None
         self._ensure_state()
+        # Gradient accumulation.  Eager: the host decides -- a hold step issues nothing (no reduction under data parallelism either:
+        # GradSync.hold) and only moves the phase.  Recorded (``_win_dev``): every micro-step issues the whole update under the
+        # hold gate and the device decides; the host mirrors are advanced by the recorded step's caller.
+        accum_dev = self._accum_k > 1 and self._win_dev is not None
+        if self._accum_k > 1 and not accum_dev and not self.window_after(self._accum_phase, self._accum_k)[1]:
+            if self.lanes is not None:
+                self.lanes.after_backward = None       # (one-shot of the backward: no update takes it)
+                self._join_side()
+            self._advance_window()
+            return loss
         self.fold_if_due()                # (raises where a recorded step holds the step on the device)
         self._all_live = self.all_trainable()
         grp = self.param_groups[0]
@@ -793,8 +887,9 @@ class FusedAdam(torch.optim.Optimizer):
         g = self.model.flat_grads(attach=True)
         if self._step_dev is None:
             self._step += 1
+        # (accumulating: 1 / k folded into the scale -- by value here, by the launches themselves under the hold gate)
         args = (max(self._step, 1), grp['lr'], grp['betas'][0], grp['betas'][1], grp['eps'], grp['weight_decay'],
-                self.grad_scale, self._step_dev)
+                self.grad_scale if accum_dev else self._scale(), self._step_dev)
         flat = self.model.flat_params()
         sync, lanes = self.model.grad_sync, self.lanes
         self._clip_now = self._clip_max()
@@ -807,6 +902,10 @@ class FusedAdam(torch.optim.Optimizer):
             self._clip_buffers()
         if guard:
             self._guard_flags = self._flags()
+        if accum_dev and (clip or (sync is not None and sync.world > 1)):
+            from ._lib import LirecError
+            raise LirecError('FusedAdam: gradient accumulation with the window on the device (a recorded step) is not built with '
+                             'max_grad_norm / skip_nonfinite or under data parallelism -- run the eager step')
         if sync is not None and sync.world > 1:
             if getattr(opt, 'strict', False) and hasattr(sync, 'check_frozen_set'):
                 sync.check_frozen_set(self._flags(), self.group_membership() if len(self.param_groups) > 1 else ())
@@ -817,6 +916,7 @@ class FusedAdam(torch.optim.Optimizer):
                 if self._step_dev is None:
                     self._advance_lags()
                     self._advance_ema()
+                    self._advance_window()
                 return loss
             # data parallel: each bucket is updated as its reduction lands, the later buckets still in flight.  Sharded
             # (the default, lirec_amd.parallel): this rank holds the summed gradients of ITS slice of the bucket only, updates
@@ -860,6 +960,10 @@ class FusedAdam(torch.optim.Optimizer):
                 for a, b in self._minus(lo, hi, skip):
                     self._update(flat, g, a, b, args, role=role)
             side = lanes.take_after_backward(self.model._offsets) if lanes is not None else None
+            if accum_dev:
+                # (the window on the device: the whole update on this stream under the hold gate -- lane 0 issues no update of its
+                #  own, its step counter is advanced by the head launch beside the caller's: begin_micro_step)
+                side = None
             if clip:
                 # Clipped: the coefficient needs EVERY gradient finished, so nothing is updated beside the tail of backward -- the side
                 # streams are joined (below: the no-side branch), the norm is taken over the trainable ranges (frozen slices of the
@@ -900,9 +1004,12 @@ class FusedAdam(torch.optim.Optimizer):
             else:
                 # (no update on lane 0 after all: whatever a backward left running there writes the gradients this update reads)
                 self._join_side()
-                if self._step_dev is not None and lanes is not None and lanes.step_side_dev is not None:
+                if self._step_dev is not None and lanes is not None and lanes.step_side_dev is not None and not accum_dev:
                     ops.counter_add(lanes.step_side_dev, [1])      # (kept in step with the shared counter whichever path a step takes)
-                if clip:
+                if accum_dev:
+                    with ops.adam_hold(self._win_dev[1:2], self._accum_k):
+                        update(0, flat.numel())
+                elif clip:
                     if skip:
                         # (max_grad_norm was set between arm_first_layer_update() and this step: the backward has already applied
                         #  the first layers' update, unclipped -- nothing here can take it back)
@@ -922,6 +1029,7 @@ class FusedAdam(torch.optim.Optimizer):
         if self._step_dev is None:
             self._advance_lags()          # (a recorded step's caller advances the host mirrors itself, _step included)
             self._advance_ema()
+            self._advance_window()
         return loss
 
     def _clip_nothing(self):

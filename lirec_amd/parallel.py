@@ -78,6 +78,7 @@ class GradSync:
         self.pending = []
         self.launched = set()
         self.reduced = set()          # buckets a wait() has already seen through: the optimiser must not reduce them again
+        self.hold = False             # this backward's buckets are not reduced (FusedAdam.accumulate_steps: a hold step; set by the optimiser)
         self._launch_stream = None
         self._gathers = []
         self._slices = {}             # bucket start -> this rank's reduced gradient slice (reduce_scatter_tensor's output)
@@ -123,6 +124,10 @@ class GradSync:
         optionally, on the stream with raw handle ``also`` (the weight-gradient side stream).  The collective is issued
         from a launch stream that waits for both, so neither of them is held up."""
         if self.world == 1 or stage not in self.stages or stage in self.launched or stage in self.reduced:
+            return
+        if self.hold:
+            # (gradient accumulation, FusedAdam.accumulate_steps: this backward belongs to a hold step -- its gradients stay local,
+            #  as under torch's no_sync; the apply step's backward reduces the accumulated ones)
             return
         lo, hi = self.ranges[self.stages.index(stage)]
         g = self.get_flat_grad()
@@ -328,6 +333,8 @@ class DataParallel:
         #  membership is part of that check's hash; groups that differ between ranks are not supported.)
         if hasattr(optimizer, 'trainable_ranges'):
             model.grad_sync.trainable_ranges = optimizer.trainable_ranges
+        if hasattr(optimizer, '_hold_sync'):
+            optimizer._hold_sync()            # (gradient accumulation: is the next backward a hold step's?)
 
     def global_divisors(self, local, device=None):
         """``local``: this rank's denominators of a loss's batch means (numbers or 0-d tensors: clips, labelled rows, ...).

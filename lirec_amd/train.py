@@ -155,6 +155,8 @@ class _Stepper:
     def close(self):
         if self.recorded is not None:
             self.recorded.release()       # (back to the eager loop's way of passing the dropout key and Adam's step)
+        if getattr(self.optimizer, 'accum_phase', 0):
+            self.optimizer.drop_window()  # (a partial window at the end of training() is dropped: its micro-batches update nothing)
 
     def step(self, i, batch):
         """this batch's step: (loss value -- one element, on the device, not read --, labels); None: a one-label batch, skipped (:55-56)"""
@@ -180,7 +182,10 @@ class _Stepper:
             else:
                 self.run, self.run_barred = (1 if lay else 0), False
             self.last_layout = lay
+            # (gradient accumulation: no coverage check -- it fills the gradient buffer, which holds the open window, and the
+            #  accumulating recorded step never runs in overwrite mode anyway)
             if self.recorded is None and lay and self.run == 3 and not self.run_barred and \
+                    getattr(self.optimizer, 'accumulate_steps', 1) == 1 and \
                     (lay, _flag_key(self.optimizer)) not in self.overwrite_ok and _recordable(self.model, batch):
                 lval = self._checked(batch, lay)
             else:
@@ -381,7 +386,9 @@ def training(train_dataset, **kwargs):
             if took is None:
                 continue
             lval, n = took
-            sched_step()
+            # (gradient accumulation: a scheduler counts UPDATES -- after a step() the phase is 0 exactly when that call applied)
+            if getattr(optimizer, 'accum_phase', 0) == 0:
+                sched_step()
             ev = None
             if lval.is_cuda:
                 ev = torch.cuda.Event()
