@@ -79,7 +79,13 @@ def clip_frame_range(time2frame: dict, time_node: dict, n_frames: int, sampling_
 def track_boxes(track, dims, H, W, n_frames, sampling_fr):
     """[frame, y0, y1, x0, x1] per track element (visual_features.py:110-131): the face box is blown up to a person box
     (face = 0.35..0.65 of its width, 0.10..0.25 of its height), scaled to the I3D grid, floor / ceil to cells.  A frame
-    index equal to the grid length marks the element the reference skips (its row stays zero): frame -1 here."""
+    index equal to the grid length marks the element the reference skips (its row stays zero): frame -1 here.
+
+    The bounds returned are those the reference's slice ``[:, ry[0]:ry[1], rx[0]:rx[1]]`` SELECTS, always inside the grid
+    (0 <= y0, y1 <= H, 0 <= x0, x1 <= W).  They differ from ``ry`` / ``rx`` for a person box that ends left of or above the
+    frame: its upper bound is negative, and numpy counts a negative bound from the far end -- ``0:-3`` on 15 columns is columns
+    0..11, a finite mean over cells the box never touched; only from ``-W`` (``-H``) down is the crop empty (NaN).  A box that
+    starts right of / below the frame is an empty crop (y1 <= y0 or x1 <= x0)."""
     sh, sw = H / dims[0], W / dims[1]
     FH0, FH1, FW0, FW1 = 0.10, 0.25, 0.35, 0.65
     out = []
@@ -91,7 +97,9 @@ def track_boxes(track, dims, H, W, n_frames, sampling_fr):
         rx = [max(0, int(np.floor(spx))), min(int(W), int(np.ceil(spx + spw)))]
         ry = [max(0, int(np.floor(spy))), min(int(H), int(np.ceil(spy + sph)))]
         frame = int(el['frame'] * sampling_fr)
-        out.append([-1 if frame == n_frames else frame, ry[0], ry[1], rx[0], rx[1]])
+        y0, y1, _ = slice(ry[0], ry[1]).indices(int(H))
+        x0, x1, _ = slice(rx[0], rx[1]).indices(int(W))
+        out.append([-1 if frame == n_frames else frame, y0, y1, x0, x1])
     return out
 
 
@@ -128,6 +136,8 @@ def grid_pool(grid: torch.Tensor, box_lists) -> torch.Tensor:
     F, Cc, H, W = grid.shape
     boxes, est = _segments(box_lists, 5, grid.device)
     out = torch.empty((len(box_lists), Cc), dtype=torch.float32, device=grid.device)
+    if not box_lists:
+        return out                                     # (an empty tensor has no address to hand to the library)
     check(lib().lirec_grid_pool(grid.data_ptr(), F, Cc, H, W, boxes.data_ptr() if boxes.numel() else est.data_ptr(), est.data_ptr(),
                                 len(box_lists), out.data_ptr(), Cc, _stream()), 'lirec_grid_pool')
     return out
@@ -138,6 +148,8 @@ def rows_max(src: torch.Tensor, row_lists) -> torch.Tensor:
     assert src.is_cuda and src.dtype == torch.float32 and src.dim() == 2 and src.stride(1) == 1
     idx, est = _segments([[[r] for r in l] for l in row_lists], 1, src.device)
     out = torch.empty((len(row_lists), src.shape[1]), dtype=torch.float32, device=src.device)
+    if not row_lists:
+        return out
     check(lib().lirec_rows_max(src.data_ptr(), src.stride(0), idx.data_ptr() if idx.numel() else est.data_ptr(), est.data_ptr(),
                                len(row_lists), src.shape[1], out.data_ptr(), src.shape[1], _stream()), 'lirec_rows_max')
     return out

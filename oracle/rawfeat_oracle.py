@@ -8,7 +8,7 @@ numpy restatement of what the reference's feature classes compute for an uncache
   text         np.max over the token rows of the dialog lines overlapping the clip (text_utils/text_features.py:140-182,
                mixed_features.py:61)
 The integer bookkeeping (frame range, box corners, token rows) is taken as input -- lirec_amd.rawfeat holds the host
-statement of it, pinned by the same fixture.  Pinned to the reference by tests/golden/rawfeat.npz (oracle/make_golden_rawfeat.py).
+statement of it, pinned by the same fixture.  Pinned to the reference by tests/golden/rawfeat.npz and rawfeat_edges.npz (oracle/make_golden_rawfeat.py).
 """
 import numpy as np
 
