@@ -199,32 +199,24 @@ class RecordedTrainStep:
                                      'from BlockLoader, or run the eager step')
         if draw is not None and (next_batch is not None or getattr(model, 'grad_sync', None) is not None):
             raise ValueError('RecordedTrainStep(draw=...): the plain single-GPU form')
-        self.draw, self.loss = draw, loss
-        self._check_draw()
         self.model, self.loss, self.optim, self.batch, self.draw = model, loss, optimizer, batch, draw
+        self._check_draw()
         self.lanes = model.lanes       # (lirec_amd.lanes.StepLanes: the side streams and the state handed over between them)
         self.batches = [batch, next_batch] if next_batch is not None else [batch]
         self.sync = getattr(model, 'grad_sync', None)
         if next_batch is not None and self.sync is not None:
             raise ValueError('RecordedTrainStep(next_batch=...): single-GPU form')
-        # (gradient accumulation, FusedAdam.accumulate_steps = k > 1: what the accumulating form is not built with is refused here,
-        #  with the other argument checks -- before anything of the optimiser or the device is touched)
-        self.accum = int(getattr(optimizer, 'accumulate_steps', 1))
-        self.win = None
-        if self.accum > 1:
-            if next_batch is not None:
-                raise LirecError('RecordedTrainStep(next_batch=...): the input-pipeline form is not built with gradient accumulation '
-                                 '(accumulate_steps = %d) -- record the plain form' % self.accum)
-            if self.sync is not None and self.sync.world > 1:
-                raise LirecError('RecordedTrainStep: gradient accumulation under data parallelism is not recorded (the bucket reductions '
-                                 'are issued from the host, which a replay gives no hold / apply decision) -- run the eager step')
-            if bool(getattr(optimizer, 'max_grad_norm', None)) or bool(getattr(optimizer, 'skip_nonfinite', False)):
-                raise LirecError('RecordedTrainStep: gradient accumulation with max_grad_norm / skip_nonfinite is not recorded (the norm '
-                                 'launches and the finalize have no hold gate) -- run the eager step')
+        # (what the optimiser's route is not recorded with -- FusedAdam.route: accumulation in the input-pipeline form, under data
+        #  parallelism or on the norm route; the norm route under data parallelism -- is refused here, with the other argument checks:
+        #  before anything of the optimiser or the device is touched)
+        refuse = optimizer.route(pipelined=next_batch is not None).refuse
+        if refuse is not None:
+            raise LirecError(refuse)
+        self.accum = optimizer.accumulate_steps
+        self.win, self.overwrite, self.fused, self.defer = None, False, False, False
         dev = model.flat_params().device
         optimizer._ensure_state()
-        if hasattr(optimizer, 'fold_if_due'):
-            optimizer.fold_if_due()       # (skipped steps of another frozen set, or of a guard since switched off: while the step is by value)
+        optimizer.fold_if_due()           # (skipped steps of another frozen set, or of a guard since switched off: while the step is by value)
         # [forward calls (the dropout key's offset), Adam step, Adam step AS LANE 0 COUNTS IT]: the first two are advanced by the step's
         # first launch; the third by lane 0's own Adam launch, which under deferral may still run when the next step begins
         self.state = torch.tensor([model._fwd_train_calls, optimizer._step, optimizer._step], dtype=torch.int64, device=dev)
@@ -255,48 +247,28 @@ class RecordedTrainStep:
         # must not see a half-checked buffer).
         # (``overwrite``: the caller has run the check itself -- checked_overwrite_step on an earlier batch of this layout -- and
         #  passes its verdict: lirec_amd.train records with no warm-up step of its own)
-        self.overwrite = bool(overwrite) if (overwrite is not None and getattr(model, 'grad_sync', None) is None) else False
-        # (gradient accumulation IS the accumulate mode of the weight-gradient kernels: never the overwrite mode, and therefore --
-        #  `defer` below needs it -- never a deferred side join: every micro-step joins lane 0 before it ends, so the head launch of
-        #  the next one rewrites the window's hold flag behind every launch that read it)
-        if self.accum > 1:
-            self.overwrite = False
-        # Gradient clipping (FusedAdam.max_grad_norm): the norm needs every gradient of the step finished, so the clipped update is
-        # issued whole on this stream behind backward -- no fused first-layer update, no un-joined side stream (`defer`)
-        # (skip_nonfinite -- the guard -- takes the same route for the same reason: the decision needs the finished gradients)
-        clipping = bool(getattr(optimizer, 'max_grad_norm', None)) or bool(getattr(optimizer, 'skip_nonfinite', False))
-        if clipping and self.sync is not None and self.sync.world > 1:
-            raise LirecError('RecordedTrainStep: gradient clipping / skip_nonfinite under data parallelism is not recorded (the all-reduce '
-                             'of the squared norm sits between the recorded launches) -- run the eager step')
+        # (gradient accumulation IS the accumulate mode of the weight-gradient kernels: never the overwrite mode -- ``may_overwrite`` --
+        #  and therefore -- `defer` below needs it -- never a deferred side join: every micro-step joins lane 0 before it ends, so the
+        #  head launch of the next one rewrites the window's hold flag behind every launch that read it)
+        may_overwrite = self.sync is None and optimizer.route().may_overwrite
+        self.overwrite = bool(overwrite) if (overwrite is not None and may_overwrite) else False
         self.mid, self.parity, self.pre = None, 0, [None, None]
         # (warmup = 0: the caller has already run eager steps of this model -- lirec_amd.train records in the middle of an epoch,
         #  every batch being stepped on exactly once -- so the recording step is the only step taken here; the gradient-overwrite
         #  mode, which is checked on a warm-up step, then stays off)
         nwarm = max(int(warmup), 0)
         for w in range(nwarm):                     # lazy things happen here: scratch registered, side stream made, pools grown
-            self._one_step(check=(w == nwarm - 1 and self.sync is None and overwrite is None and self.accum == 1
-                                  and bool(getattr(ops, 'set_grad_overwrite', None))))
+            self._one_step(check=(w == nwarm - 1 and may_overwrite and overwrite is None and bool(getattr(ops, 'set_grad_overwrite', None))))
             self._advance_host()
         # The step is issued as a unit, so the update of the first-layer parameters -- the last gradients backward finishes -- is
         # folded into the launch that finishes them, which also keeps a q32b copy of the new weights for the next forward (no
         # separate Adam pass over that bucket, no staging of W1): FusedAdam.arm_first_layer_update.  Single GPU, layer 1 on the
-        # q32b kernels (seen on the steps taken so far).
-        self.fused = bool(self.sync is None and getattr(opt, 'fuse_dw1_adam', True) and getattr(model, 'last_layer1_planes', False)
+        # q32b kernels (seen on the steps taken so far), and the optimiser's route: the first layers folded, or frozen altogether --
+        # nothing writes them, the shadow stays current.  ('ordinary': the update writes no shadow, the forward stages the weights.)
+        route = optimizer.route()
+        self.fused = bool(getattr(opt, 'fuse_dw1_adam', True) and getattr(model, 'last_layer1_planes', False)
                           and getattr(model, '_has_ints', False) and getattr(model, '_has_ctx', False)
-                          and hasattr(optimizer, 'arm_first_layer_update') and hasattr(model, 'refresh_w1q') and not clipping
-                          and self.accum == 1)       # (accumulating: the plain update under the hold gate -- the fold has none)
-        if self.fused and getattr(optimizer, 'device_hyper', False):
-            # (parameter groups: the folded update reads one row of the hyper-parameter table per first-layer parameter -- all of
-            #  them trainable and up to date, in one group or several, or frozen altogether)
-            lo, hi, _ = model.first_layer_range()
-            if optimizer.trainable_ranges(lo, hi) and optimizer.first_layer_fold_ranges() is None:
-                self.fused = False
-        elif self.fused and hasattr(optimizer, 'trainable_ranges') and not optimizer.all_trainable():
-            # (first layers PARTLY trainable, or behind: the optimiser does not arm the fused update -- the ordinary update writes no
-            #  shadow, the forward stages the weights itself.  Frozen altogether: nothing writes them, the shadow stays current.)
-            lo, hi, _ = model.first_layer_range()
-            if optimizer.trainable_ranges(lo, hi) not in ([], [(lo, hi, 0)]):
-                self.fused = False
+                          and hasattr(model, 'refresh_w1q') and route.first != 'ordinary')
         if self.fused:
             self.fused = model.refresh_w1q()
         # (does the recorded forward read the q32b shadow of the first-layer weights?  step() rebuilds a stale one before it replays)
@@ -306,8 +278,9 @@ class RecordedTrainStep:
         self._side_unordered = False
         torch.cuda.synchronize()
         self.marks = []
-        # Deferral ("Lanes"): needs the overwrite mode -- no zeroing pass over gradients the deferred update still reads
-        self.defer = bool(self.overwrite and self.sync is None and getattr(opt, 'defer_side_join', True) and not clipping)
+        # Deferral ("Lanes"): needs the overwrite mode -- no zeroing pass over gradients the deferred update still reads --
+        # and a route that updates on lane 0
+        self.defer = bool(self.overwrite and getattr(opt, 'defer_side_join', True) and route.lane0)
         self.lanes.defer_join = self.defer
         if self.sync is not None:
             model.grad_sync = _MarkingSync(self.sync, self.marks)
@@ -318,8 +291,7 @@ class RecordedTrainStep:
                     self._pre_lane = self.lanes.staging(dev)
                     self.pre[0] = model.prestage(self.batches[0])
                     self.pre[1] = model.prestage(self.batches[1], advance=1)
-                if hasattr(optimizer, 'sync_hyper'):
-                    optimizer.sync_hyper()          # (a command list never contains a write to the hyper-parameter tables)
+                optimizer.sync_hyper()              # (a command list never contains a write to the hyper-parameter tables)
                 ops.CommandList.begin()
                 try:
                     if self.draw is not None:
@@ -338,15 +310,14 @@ class RecordedTrainStep:
         self._kept = kept
         self._hyper = self.hyper_key(optimizer)        # (baked into the recorded Adam launches by value: step() refuses a replay with others)
         self._gemm_mode = ops.get_gemm_mode()          # (the recorded launches ARE this core's kernels, reading its operand forms)
-        self._advance_host()
-        self.marks = [m for m in self.marks if self.sync is not None]
+        self._advance_host()             # (``marks`` holds entries under data parallelism only: _MarkingSync wrote them)
         self._loss_outs = getattr(self, '_loss_outs', [self.loss_out])
 
     def _attach_counters(self):
         """the kernels read the dropout key's offset and the Adam step (the caller's and the side stream's count) from ``state``"""
         self.model._seed_dev, self.optim._step_dev = self.state[0:1], self.state[1:2]
         self.lanes.step_side_dev = self.state[2:3]
-        if getattr(self, 'win', None) is not None:
+        if self.win is not None:
             self.optim._win_dev = self.win       # (the window of an accumulating step: decided on the device from here on)
         if hasattr(self.loss, '_sample_key'):
             self.loss._sample_calls = self.model._fwd_train_calls
@@ -394,7 +365,7 @@ class RecordedTrainStep:
                                'tensor the loss module returned, or its logits did not come straight from the model); the '
                                'backward launches cannot be recorded -- use the eager loop for this loss')
         before = ops.CommandList.mark()
-        if getattr(self, 'fused', False) and not check:
+        if self.fused and not check:
             self.optim.arm_first_layer_update()
         if over:
             ops.set_grad_overwrite(True)
@@ -426,14 +397,12 @@ class RecordedTrainStep:
         self.model._fwd_train_calls += 1
         # (accumulating: the phase moves every micro-step; step, lags and the average's count on the apply step only -- the host
         #  knows which it was without reading the device: the phase is a function of the number of calls)
-        applied = self.optim._advance_window() if getattr(self, 'accum', 1) > 1 else True
+        applied = self.optim._advance_window() if self.accum > 1 else True
         if applied:
             self.optim._step += 1
             self.optim._opt_called = True           # (torch's lr_scheduler: an optimiser step HAS been taken -- no order warning)
-            if hasattr(self.optim, '_advance_lags'):
-                self.optim._advance_lags()          # (frozen parameters sat this update out, as in the eager step())
-            if hasattr(self.optim, '_advance_ema'):
-                self.optim._advance_ema()           # (the host count behind ema_updates(); skipped steps come off on the device's word)
+            self.optim._advance_lags()              # (frozen parameters sat this update out, as in the eager step())
+            self.optim._advance_ema()               # (the host count behind ema_updates(); skipped steps come off on the device's word)
         if hasattr(self.loss, '_sample_key'):
             self.loss._sample_calls += 1
 
@@ -503,7 +472,7 @@ class RecordedTrainStep:
         # The recorded forward reads the weights' q32b forms the recorded updates keep current.  Anything else that changed the
         # parameters since the last replay -- load_state_dict, an eager optimizer.step() without release() -- has marked them stale
         # (host flags): rebuild them from the parameters as they are now, on this stream, before the replay reads them.
-        if getattr(self, 'fused', False) and self._shadow_w1 and not getattr(self.model, '_w1q_valid', False):
+        if self.fused and self._shadow_w1 and not getattr(self.model, '_w1q_valid', False):
             self.model.refresh_w1q()
         if self._side_unordered and not self.lanes.bucket0_on_side:
             lane = self.model._wgrad_lane()
@@ -573,12 +542,12 @@ class RecordedTrainStep:
         self.lanes.defer_join = False
         self.model._seed_dev = None
         self.optim._step_dev = None
-        if getattr(self, 'win', None) is not None:
+        if self.win is not None:
             self.optim._win_dev = None      # (the window goes on from the host's phase: eager steps in between continue it)
         self.lanes.step_side_dev = None
         if hasattr(self.loss, '_sample_key'):
             self.loss._seed_dev = None
-        if getattr(self, 'fused', False):
+        if self.fused:
             self.model.invalidate_w1q()     # (eager steps update the weights without their q32b shadow)
 
     def resume(self):
@@ -586,14 +555,13 @@ class RecordedTrainStep:
         copy) and the recorded list is valid again -- how a training loop steps on an odd-shaped batch in between
         (lirec_amd.train: the short last batch of an epoch)."""
         self._check_core()
-        if hasattr(self.optim, 'fold_if_due'):
-            self.optim.fold_if_due()      # (the eager steps in between may have changed the frozen set: before the counters attach)
+        self.optim.fold_if_due()          # (the eager steps in between may have changed the frozen set: before the counters attach)
         self.state.copy_(torch.tensor([self.model._fwd_train_calls, self.optim._step, self.optim._step], dtype=torch.int64), non_blocking=False)
         if self.win is not None:
             # (the window's phase from the host mirror, as the counters: no device read in either direction)
             self.win.copy_(torch.tensor([self.optim.accum_phase, 0, 0, 0], dtype=torch.int64), non_blocking=False)
         self._attach_counters()
-        if getattr(self, 'fused', False) and not self.model.refresh_w1q():
+        if self.fused and not self.model.refresh_w1q():
             raise RuntimeError('RecordedTrainStep.resume(): the q32b shadow of the first-layer weights cannot be rebuilt')
         self.lanes.defer_join = self.defer
         self.lanes.params_written()             # (eager steps in between: whoever wrote the parameters last, order the side stream)

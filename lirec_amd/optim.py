@@ -90,6 +90,7 @@ micro-step, so there it lives in device memory (``_win_dev``, the window block o
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import ctypes as C
 
@@ -97,6 +98,14 @@ import torch
 
 from . import ops
 from .config import opt
+
+
+# The route of one update, FusedAdam.route() -- DESIGN 4.4, "The update's route".  hold: a host-side hold step, nothing is issued;
+# norm / guard: the norm route (clip, guard) is in force / with the guard; window: the accumulation window is on the device; parallel:
+# world > 1; lane0: bucket 0 may be updated on lane 0; first: the first layers in a step issued as a unit -- 'value' / 'row' / 'map'
+# (folded into the backward: by value, reading one device row, through the per-parameter map), 'untouched' (frozen altogether) or
+# 'ordinary'; may_overwrite: the weight gradients may overwrite the buffer; refuse: why the step cannot be recorded, or None
+Route = collections.namedtuple('Route', 'hold norm guard window parallel lane0 first may_overwrite refuse')
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -148,7 +157,7 @@ class FusedAdam(torch.optim.Optimizer):
                              'hyper-parameters)' % len(self.param_groups))
         self._device_hyper_arg = None if device_hyper is None else bool(device_hyper)     # (None: left to default)
         self.device_hyper = many if device_hyper is None else bool(device_hyper)
-        self._ranges_key = self._ranges = None
+        self._ranges_key = self._ranges = self._first = None
         self.resolve_device_hyper()    # (a decoupled group: on, or a ValueError for an explicit False)
         self._tables = {}              # issuing stream ('main', 'side', 'early') -> [device float32[64], the rows it last received]
         self._m = self._v = None
@@ -679,6 +688,55 @@ class FusedAdam(torch.optim.Optimizer):
             first = False
         return first
 
+    # -- the update's route ----------------------------------------------------------
+    def route(self, pipelined=False):
+        """The ``Route`` the next ``step()`` takes -- EVERY exclusion between the features is written here and nowhere else (DESIGN
+        4.4, "The update's route").  ``pipelined``: for a recording in the input-pipeline form.  No device read, no allocation."""
+        m, k, sync = self.model, self._accum_k, getattr(self.model, 'grad_sync', None)
+        parallel = sync is not None and sync.world > 1
+        window = k > 1 and self._win_dev is not None
+        # (skip_nonfinite: the norm route whether or not a bound is set -- the decision needs the finished gradients as the norm does)
+        guard = bool(self.skip_nonfinite)
+        norm = guard or bool(self.max_grad_norm)
+        refuse = None
+        if k > 1 and pipelined:
+            refuse = ('RecordedTrainStep(next_batch=...): the input-pipeline form is not built with gradient accumulation '
+                      '(accumulate_steps = %d) -- record the plain form' % k)
+        elif k > 1 and parallel:
+            refuse = ('RecordedTrainStep: gradient accumulation under data parallelism is not recorded (the bucket reductions '
+                      'are issued from the host, which a replay gives no hold / apply decision) -- run the eager step')
+        elif k > 1 and norm:
+            refuse = ('RecordedTrainStep: gradient accumulation with max_grad_norm / skip_nonfinite is not recorded (the norm '
+                      'launches and the finalize have no hold gate) -- run the eager step')
+        elif norm and parallel:
+            refuse = ('RecordedTrainStep: gradient clipping / skip_nonfinite under data parallelism is not recorded (the all-reduce '
+                      'of the squared norm sits between the recorded launches) -- run the eager step')
+        # The folded first-layer update: single GPU; not on the norm route (the norm needs the finished first-layer gradients: they
+        # are updated with the rest, clipped); not accumulating (the fold has no hold gate: it would update on every micro-batch)
+        first = 'ordinary'
+        if sync is None and self.lanes is not None and hasattr(m, 'first_layer_range') and not norm and k == 1:
+            first = self._first_layers()
+        # lane 0 and the deferred join: the norm needs EVERY gradient finished, so nothing is updated beside the tail of backward; the
+        # window's update is issued whole on the caller's stream under the hold gate (lane 0's counter: begin_micro_step)
+        return Route(hold=k > 1 and not window and not self.window_after(self._accum_phase, k)[1], norm=norm, guard=guard,
+                     window=window, parallel=parallel, lane0=self.lanes is not None and not (norm or window or parallel), first=first,
+                     may_overwrite=k == 1, refuse=refuse)
+
+    def _first_layers(self):
+        """``Route.first`` as the frozen set and the groups allow it (cached with the trainable ranges)"""
+        self.resolve_device_hyper()
+        self.trainable_ranges()            # (refreshes the key: flags, lags, layout, device_hyper)
+        if self._first is None or self._first[0] is not self._ranges_key:
+            # (the folded launch updates EVERY first-layer parameter with the one global step: first_layer_fold_ranges -- by value
+            #  that is the one range of the whole bucket; under ``device_hyper`` one group, one row, or several, the map)
+            fold = self.first_layer_fold_ranges()
+            if fold is not None:
+                kind = 'value' if not self.device_hyper else 'row' if len(fold) == 1 else 'map'
+            else:
+                kind = 'ordinary' if self.trainable_ranges(*self.model.first_layer_range()[:2]) else 'untouched'
+            self._first = (self._ranges_key, kind)
+        return self._first[1]
+
     def arm_first_layer_update(self):
         """For a caller that issues backward and step as a unit (lirec_amd.graph.RecordedTrainStep; single GPU): the NEXT backward
         folds the update of the first layers of both embeddings (the last gradient bucket, 10 M parameters at the bench shape)
@@ -690,31 +748,19 @@ class FusedAdam(torch.optim.Optimizer):
         m = self.model
         if self._step_dev is None:
             self.fold_if_due()
-        if getattr(m, 'grad_sync', None) is not None or self.lanes is None or not hasattr(m, 'first_layer_range'):
+        first = self.route().first
+        if first not in ('value', 'row', 'map'):
             return False
-        if self._clip_max() is not None or self.skip_nonfinite:
-            return False          # (the norm needs the finished first-layer gradients: they are updated with the rest, clipped)
-        if self._accum_k > 1:
-            return False          # (the fold has no hold gate: it would update on every micro-batch)
         row = hmap = None
-        if self.resolve_device_hyper():
-            # (every first-layer parameter trainable and up to date.  All of them in ONE group: the launch reads one row -- of the
-            #  table of the stream that runs the backward's tail; in several: that table and the ranges with their groups)
+        if first != 'value':
+            # (the row -- the rows -- of the table of the stream that runs the backward's tail)
             rs = self.first_layer_fold_ranges()
-            if rs is None:
-                return False
             self.sync_hyper()
             self._rows_now = self.hyper_rows()
-            if len(rs) == 1:
+            if first == 'row':
                 row = self._table('main')[8 * rs[0][3]:8 * rs[0][3] + 8]
             else:
                 hmap = (self._table('main'), [(a, b - a, grp) for a, b, _, grp in rs])
-        elif not self.all_trainable():
-            # (the fused launch updates EVERY first-layer parameter of the call with the one global step: only when each of them
-            #  is trainable and has received every update so far)
-            lo, hi, _ = m.first_layer_range()
-            if self.trainable_ranges(lo, hi) != [(lo, hi, 0)]:
-                return False
         grp = self.param_groups[0]
         flat, g = m.flat_params(), m.flat_grads(attach=True)
         hyper = (max(self._step + (1 if self._step_dev is None else 0), 1), grp['lr'], grp['betas'][0], grp['betas'][1], grp['eps'],
@@ -728,8 +774,8 @@ class FusedAdam(torch.optim.Optimizer):
         return True
 
     def first_layer_fold_ranges(self):
-        """Under ``device_hyper``: the ranges (start, end, 0, group) of the first-layer bucket when the folded update can take it
-        -- every first-layer parameter trainable with lag 0, in at most 16 ranges (one range: one group) -- or None"""
+        """The ranges (start, end, 0[, group]) of the first-layer bucket when the folded update can take it -- every first-layer
+        parameter trainable with lag 0, in at most 16 ranges (under ``device_hyper`` one range: one group; by value: one) -- or None"""
         from ._lib import ADAM_MAP_MAX
         m = self.model
         lo, hi, _ = m.first_layer_range()
@@ -867,16 +913,29 @@ class FusedAdam(torch.optim.Optimizer):
     def step(self, closure=None):
         loss = closure() if closure is not None else None
         self._ensure_state()
-        # Gradient accumulation.  Eager: the host decides -- a hold step issues nothing (no reduction under data parallelism either:
-        # GradSync.hold) and only moves the phase.  Recorded (``_win_dev``): every micro-step issues the whole update under the
-        # hold gate and the device decides; the host mirrors are advanced by the recorded step's caller.
-        accum_dev = self._accum_k > 1 and self._win_dev is not None
-        if self._accum_k > 1 and not accum_dev and not self.window_after(self._accum_phase, self._accum_k)[1]:
+        route = self.route()
+        if route.hold:
+            # Gradient accumulation, eager: the host decides -- a hold step issues nothing (no reduction under data parallelism
+            # either: GradSync.hold) and only moves the phase.  (Recorded, ``route.window``: every micro-step issues the whole
+            # update under the hold gate and the device decides.)
             if self.lanes is not None:
                 self.lanes.after_backward = None       # (one-shot of the backward: no update takes it)
                 self._join_side()
-            self._advance_window()
-            return loss
+        elif route.parallel and route.norm:
+            self._step_parallel_clipped(*self._begin_update(route))
+        elif route.parallel:
+            self._step_parallel(*self._begin_update(route))
+        else:
+            self._step_single(route, *self._begin_update(route))
+        if route.hold or self._step_dev is None:
+            # (the host mirrors, _step included: a recorded step's caller advances them itself -- RecordedTrainStep._advance_host)
+            if self._advance_window():        # (applied: not a hold step)
+                self._advance_lags()
+                self._advance_ema()
+        return loss
+
+    def _begin_update(self, route):
+        """the prologue of every update that is issued; returns (flat parameters, flat gradients, the launches' arguments)"""
         self.fold_if_due()                # (raises where a recorded step holds the step on the device)
         self._all_live = self.all_trainable()
         grp = self.param_groups[0]
@@ -889,148 +948,133 @@ class FusedAdam(torch.optim.Optimizer):
             self._step += 1
         # (accumulating: 1 / k folded into the scale -- by value here, by the launches themselves under the hold gate)
         args = (max(self._step, 1), grp['lr'], grp['betas'][0], grp['betas'][1], grp['eps'], grp['weight_decay'],
-                self.grad_scale if accum_dev else self._scale(), self._step_dev)
+                self.grad_scale if route.window else self._scale(), self._step_dev)
         flat = self.model.flat_params()
-        sync, lanes = self.model.grad_sync, self.lanes
-        self._clip_now = self._clip_max()
-        # (skip_nonfinite: the clipped route, whether or not a bound is set -- `clip` from here on means "that route")
-        self._guard_now = guard = bool(self.skip_nonfinite)
-        clip = self._clip_now is not None or guard
-        if self._ema_w is not None and self._ema is None:
-            self._ensure_ema(flat)
-        if clip:
+        self._clip_now, self._guard_now = self._clip_max(), route.guard
+        if route.norm:
             self._clip_buffers()
-        if guard:
+        if route.guard:
             self._guard_flags = self._flags()
-        if accum_dev and (clip or (sync is not None and sync.world > 1)):
+        if route.window and route.refuse is not None:
             from ._lib import LirecError
-            raise LirecError('FusedAdam: gradient accumulation with the window on the device (a recorded step) is not built with '
-                             'max_grad_norm / skip_nonfinite or under data parallelism -- run the eager step')
-        if sync is not None and sync.world > 1:
+            raise LirecError(route.refuse)
+        if route.parallel:
+            sync = self.model.grad_sync
             if getattr(opt, 'strict', False) and hasattr(sync, 'check_frozen_set'):
                 sync.check_frozen_set(self._flags(), self.group_membership() if len(self.param_groups) > 1 else ())
-            if lanes is not None:
-                lanes.bucket0_on_side = False
-            if clip:
-                self._step_parallel_clipped(sync, flat, g, args)
-                if self._step_dev is None:
-                    self._advance_lags()
-                    self._advance_ema()
-                    self._advance_window()
-                return loss
-            # data parallel: each bucket is updated as its reduction lands, the later buckets still in flight.  Sharded
-            # (the default, lirec_amd.parallel): this rank holds the summed gradients of ITS slice of the bucket only, updates
-            # that slice (parameters and moments), and the slices are all-gathered back into everybody's parameter buffer
-            done, used = 0, None
-            for lo, hi, early in sync.wait_each():
-                a, b = sync.my_slice(lo, hi)
-                if early is not None:
-                    # (heads + gate: reduced long before backward ends, and nothing that is still to run reads them -- updated
-                    #  and gathered on the collective's launch stream, beside the tail of backward: GradSync.early_stream)
-                    with ops.on_stream(C.c_void_p(early.cuda_stream)), torch.cuda.stream(early):
-                        if b > a:
-                            self._update(flat, sync.grad_slice(g, lo, hi), a, b, args, g_is_slice=True, role='early')
-                        sync.gather_params(lo, hi)
-                    used = early
-                else:
-                    if b > a:
-                        self._update(flat, sync.grad_slice(g, lo, hi), a, b, args, g_is_slice=True)
-                    sync.gather_params(lo, hi)
-                done += hi - lo
-            assert done == flat.numel(), 'gradient buckets do not cover the parameter buffer'
-            if used is not None:          # the step ends when the early bucket's update has (one event)
-                ops.stream_wait(ops.current_stream_handle(), C.c_void_p(used.cuda_stream))
-            sync.finish_gathers()
-        else:
-            if sync is not None:
-                sync.wait()
-            # (the first layers' bucket was updated by the backward itself -- arm_first_layer_update -- or: an update from here
-            #  does not write the q32b shadow of the first-layer weights, which is stale from now on)
-            skip = []
-            if lanes is not None and lanes.take_fold_applied():
-                skip.append((self.model.first_layer_range()[0], flat.numel()))
-                # (the backward's fold ran on this stream before step() was entered: the range's average follows it here)
-                self._lerp(flat, *skip[0])
-            elif getattr(self.model, '_w1q_valid', False):
-                # (... unless the first layers are frozen altogether: nothing writes those weights, the shadow stays current)
-                if self._all_live or self.trainable_ranges(*self.model.first_layer_range()[:2]):
-                    self.model.invalidate_w1q()
+            if self.lanes is not None:
+                self.lanes.bucket0_on_side = False
+        return flat, g, args
 
-            def update(lo, hi, role='main'):
-                for a, b in self._minus(lo, hi, skip):
-                    self._update(flat, g, a, b, args, role=role)
-            side = lanes.take_after_backward(self.model._offsets) if lanes is not None else None
-            if accum_dev:
-                # (the window on the device: the whole update on this stream under the hold gate -- lane 0 issues no update of its
-                #  own, its step counter is advanced by the head launch beside the caller's: begin_micro_step)
-                side = None
-            if clip:
-                # Clipped: the coefficient needs EVERY gradient finished, so nothing is updated beside the tail of backward -- the side
-                # streams are joined (below: the no-side branch), the norm is taken over the trainable ranges (frozen slices of the
-                # buffer hold whatever a shared launch left there) and the whole update follows on this stream, clipped
-                side = None
-            if lanes is not None:
-                lanes.bucket0_on_side = side is not None
-            if side is not None:
-                # Single GPU with lane 0: the heads' and the gate's gradients (bucket 0, 53 % of the parameters) were finished there
-                # long before the main stream is through with the layer-1 weight gradients, and the lane is ordered behind every
-                # main-stream reader of these parameters.  Their update runs there, beside the MFMA-bound tail of backward.
-                side_h, hi0 = side
-                # (behind everything enqueued on this stream so far -- a caller may touch the gradients between backward() and step();
-                #  one event, ~6 us -- unless the step is issued as a unit: the wait would also put the update behind 0.19 ms of tail)
-                if not lanes.atomic_step:
-                    ops.stream_wait(side_h, ops.current_stream_handle())
-                with ops.on_stream(side_h):
-                    if self._step_dev is not None and lanes.step_side_dev is not None:
-                        # the step as THIS lane counts it ("Lanes": step_side_dev): the update launch reads the completed
-                        # steps (+ 1), its last workgroup advances them; stretches with nothing trainable issue no launch, the
-                        # counter is advanced all the same
-                        stretches = self._minus(0, hi0, skip)
-                        rs = [(a, b) for a, b in stretches if self._all_live or self.trainable_ranges(a, b)]
-                        if not rs:
-                            ops.counter_add(lanes.step_side_dev, [1])
-                        for i, (a, b) in enumerate(rs):
-                            self._update(flat, g, a, b, args, counted=(lanes.step_side_dev, lanes.side_ticket), last=(i == len(rs) - 1),
-                                         role='side')
-                        for a, b in stretches:            # (nothing trainable, no launch above: the average moves all the same)
-                            if (a, b) not in rs:
-                                self._lerp(flat, a, b)
-                    else:
-                        update(0, hi0, 'side')
-                update(hi0, flat.numel())
-                # (the step ends when lane 0's share has -- unless a replayed step leaves it un-joined: StepLanes.may_defer)
-                if not lanes.unjoined:
-                    ops.stream_wait(ops.current_stream_handle(), side_h)
+    def _step_parallel(self, flat, g, args):
+        # data parallel: each bucket is updated as its reduction lands, the later buckets still in flight.  Sharded
+        # (the default, lirec_amd.parallel): this rank holds the summed gradients of ITS slice of the bucket only, updates
+        # that slice (parameters and moments), and the slices are all-gathered back into everybody's parameter buffer
+        sync, done, used = self.model.grad_sync, 0, None
+        for lo, hi, early in sync.wait_each():
+            a, b = sync.my_slice(lo, hi)
+            if early is not None:
+                # (heads + gate: reduced long before backward ends, and nothing that is still to run reads them -- updated
+                #  and gathered on the collective's launch stream, beside the tail of backward: GradSync.early_stream)
+                with ops.on_stream(C.c_void_p(early.cuda_stream)), torch.cuda.stream(early):
+                    if b > a:
+                        self._update(flat, sync.grad_slice(g, lo, hi), a, b, args, g_is_slice=True, role='early')
+                    sync.gather_params(lo, hi)
+                used = early
             else:
-                # (no update on lane 0 after all: whatever a backward left running there writes the gradients this update reads)
-                self._join_side()
-                if self._step_dev is not None and lanes is not None and lanes.step_side_dev is not None and not accum_dev:
-                    ops.counter_add(lanes.step_side_dev, [1])      # (kept in step with the shared counter whichever path a step takes)
-                if accum_dev:
-                    with ops.adam_hold(self._win_dev[1:2], self._accum_k):
-                        update(0, flat.numel())
-                elif clip:
-                    if skip:
-                        # (max_grad_norm was set between arm_first_layer_update() and this step: the backward has already applied
-                        #  the first layers' update, unclipped -- nothing here can take it back)
-                        raise RuntimeError('FusedAdam.step(): max_grad_norm / skip_nonfinite was set after the backward of this step had '
-                                           'folded the first-layer update in (arm_first_layer_update); set it before the step begins')
-                    rs = [(0, flat.numel())] if self._all_live else [(a, b - a) for a, b, *_ in self.trainable_ranges()]
-                    if self._clip_accumulate(g, rs, True):
-                        self._clip_nothing()              # (nothing trainable: no update; norm 0, coefficient 1)
-                        self._lerp(flat, 0, flat.numel())
-                    else:
-                        if guard:         # (the one finalize of the step that counts)
-                            self._finalize(None, 2, count=True)
-                        with self._scaled():
-                            update(0, flat.numel())
-                else:
+                if b > a:
+                    self._update(flat, sync.grad_slice(g, lo, hi), a, b, args, g_is_slice=True)
+                sync.gather_params(lo, hi)
+            done += hi - lo
+        assert done == flat.numel(), 'gradient buckets do not cover the parameter buffer'
+        if used is not None:          # the step ends when the early bucket's update has (one event)
+            ops.stream_wait(ops.current_stream_handle(), C.c_void_p(used.cuda_stream))
+        sync.finish_gathers()
+
+    def _step_single(self, route, flat, g, args):
+        """the single-GPU update: bucket 0 on lane 0 where the route and the backward allow it, the rest on the caller's stream"""
+        sync, lanes = self.model.grad_sync, self.lanes
+        if sync is not None:
+            sync.wait()
+        # (the first layers' bucket was updated by the backward itself -- arm_first_layer_update -- or: an update from here
+        #  does not write the q32b shadow of the first-layer weights, which is stale from now on)
+        skip = []
+        if lanes is not None and lanes.take_fold_applied():
+            skip.append((self.model.first_layer_range()[0], flat.numel()))
+            # (the backward's fold ran on this stream before step() was entered: the range's average follows it here)
+            self._lerp(flat, *skip[0])
+        elif getattr(self.model, '_w1q_valid', False):
+            # (... unless the first layers are frozen altogether: nothing writes those weights, the shadow stays current)
+            if self._all_live or self.trainable_ranges(*self.model.first_layer_range()[:2]):
+                self.model.invalidate_w1q()
+
+        def update(lo, hi, role='main'):
+            for a, b in self._minus(lo, hi, skip):
+                self._update(flat, g, a, b, args, role=role)
+        side = lanes.take_after_backward(self.model._offsets) if lanes is not None else None
+        if not route.lane0:
+            side = None
+        if lanes is not None:
+            lanes.bucket0_on_side = side is not None
+        if side is not None:
+            side_h, hi0 = side
+            self._bucket0_on_lane0(side_h, hi0, skip, update, flat, g, args)
+            update(hi0, flat.numel())
+            # (the step ends when lane 0's share has -- unless a replayed step leaves it un-joined: StepLanes.may_defer)
+            if not lanes.unjoined:
+                ops.stream_wait(ops.current_stream_handle(), side_h)
+            return
+        # (no update on lane 0 after all: whatever a backward left running there writes the gradients this update reads)
+        self._join_side()
+        if self._step_dev is not None and lanes is not None and lanes.step_side_dev is not None and not route.window:
+            ops.counter_add(lanes.step_side_dev, [1])      # (kept in step with the shared counter whichever path a step takes)
+        if not route.norm:
+            # (the window on the device: under the hold gate; else nothing is set)
+            with ops.adam_hold(self._win_dev[1:2] if route.window else None, self._accum_k):
+                update(0, flat.numel())
+        else:
+            # The norm is taken over the trainable ranges (frozen slices of the buffer hold whatever a shared launch left there) and
+            # the whole update follows on this stream, clipped
+            if skip:
+                # (max_grad_norm was set between arm_first_layer_update() and this step: the backward has already applied
+                #  the first layers' update, unclipped -- nothing here can take it back)
+                raise RuntimeError('FusedAdam.step(): max_grad_norm / skip_nonfinite was set after the backward of this step had '
+                                   'folded the first-layer update in (arm_first_layer_update); set it before the step begins')
+            rs = [(0, flat.numel())] if self._all_live else [(a, b - a) for a, b, *_ in self.trainable_ranges()]
+            if self._clip_accumulate(g, rs, True):
+                self._clip_nothing()              # (nothing trainable: no update; norm 0, coefficient 1)
+                self._lerp(flat, 0, flat.numel())
+            else:
+                if route.guard:   # (the one finalize of the step that counts)
+                    self._finalize(None, 2, count=True)
+                with self._scaled():
                     update(0, flat.numel())
-        if self._step_dev is None:
-            self._advance_lags()          # (a recorded step's caller advances the host mirrors itself, _step included)
-            self._advance_ema()
-            self._advance_window()
-        return loss
+
+    def _bucket0_on_lane0(self, side_h, hi0, skip, update, flat, g, args):
+        # Single GPU with lane 0: the heads' and the gate's gradients (bucket 0, 53 % of the parameters) were finished there
+        # long before the main stream is through with the layer-1 weight gradients, and the lane is ordered behind every
+        # main-stream reader of these parameters.  Their update runs there, beside the MFMA-bound tail of backward.
+        # (behind everything enqueued on this stream so far -- a caller may touch the gradients between backward() and step();
+        #  one event, ~6 us -- unless the step is issued as a unit: the wait would also put the update behind 0.19 ms of tail)
+        if not self.lanes.atomic_step:
+            ops.stream_wait(side_h, ops.current_stream_handle())
+        with ops.on_stream(side_h):
+            if self._step_dev is None or self.lanes.step_side_dev is None:
+                update(0, hi0, 'side')            # (the step by value)
+                return
+            # the step as THIS lane counts it (DESIGN 4.4, "Lanes": step_side_dev): the update launch reads the completed
+            # steps (+ 1), its last workgroup advances them; stretches with nothing trainable issue no launch, the
+            # counter is advanced all the same
+            stretches = self._minus(0, hi0, skip)
+            rs = [(a, b) for a, b in stretches if self._all_live or self.trainable_ranges(a, b)]
+            if not rs:
+                ops.counter_add(self.lanes.step_side_dev, [1])
+            for i, (a, b) in enumerate(rs):
+                self._update(flat, g, a, b, args, counted=(self.lanes.step_side_dev, self.lanes.side_ticket), last=(i == len(rs) - 1),
+                             role='side')
+            for a, b in stretches:            # (nothing trainable, no launch above: the average moves all the same)
+                if (a, b) not in rs:
+                    self._lerp(flat, a, b)
 
     def _clip_nothing(self):
         """a clipped step with nothing to clip: (coefficient, norm) = (1, 0), written by the finalize from a zeroed sum -- two
@@ -1038,14 +1082,14 @@ class FusedAdam(torch.optim.Optimizer):
         ops.zero_(self._clip_sq)
         self._finalize(None, 2)
 
-    def _step_parallel_clipped(self, sync, flat, g, args):
+    def _step_parallel_clipped(self, flat, g, args):
         """The data-parallel update with gradient clipping: EVERY bucket's reduction lands first (no update beside the tail of
         backward, none while later buckets are on the wire -- the coefficient needs them all); each rank squares ITS slices of the
         trainable ranges -- under the sharded update nobody holds the whole reduced gradient -- one all-reduce of the single double
         adds them up (the same bits on every rank), and the slices are updated and gathered as ever, clipped.  ``grad_scale`` =
         1 / world enters the norm: every rank gets the coefficient of the AVERAGED gradient."""
         import torch.distributed as dist
-        cur = ops.current_stream_handle()
+        sync, cur = self.model.grad_sync, ops.current_stream_handle()
         buckets = []
         for lo, hi, early in sync.wait_each():
             if early is not None:            # (the reduction was waited for on the collectives' launch stream)

@@ -182,10 +182,10 @@ class _Stepper:
             else:
                 self.run, self.run_barred = (1 if lay else 0), False
             self.last_layout = lay
-            # (gradient accumulation: no coverage check -- it fills the gradient buffer, which holds the open window, and the
-            #  accumulating recorded step never runs in overwrite mode anyway)
+            # (a route that never overwrites -- FusedAdam.route, gradient accumulation: no coverage check -- it fills the gradient
+            #  buffer, which holds the open window; an optimiser without a route: the check as ever)
             if self.recorded is None and lay and self.run == 3 and not self.run_barred and \
-                    getattr(self.optimizer, 'accumulate_steps', 1) == 1 and \
+                    (not hasattr(self.optimizer, 'route') or self.optimizer.route().may_overwrite) and \
                     (lay, _flag_key(self.optimizer)) not in self.overwrite_ok and _recordable(self.model, batch):
                 lval = self._checked(batch, lay)
             else:

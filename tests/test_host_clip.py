@@ -263,3 +263,31 @@ def test_norm_over_trainable_ranges_leaves_the_frozen_slice_out():
     rs = FusedAdam.merged_ranges(offsets, {n: True for n in offsets}, {'b.bias': 2}, extent)
     assert [(a, b) for a, b, _ in rs] == [(0, 37), (40, 45), (48, 56)]
     assert CC.norm_over(g, [(a, b) for a, b, _ in rs]) == CC.norm_over(g, [(0, extent)])       # (the gaps hold zeros; fsum is exact)
+
+
+def test_the_norm_route_under_data_parallelism_is_refused_before_any_counter_is_attached(monkeypatch):
+    """the refusal comes from FusedAdam.route() with the constructor's other argument checks: nothing of the optimiser or the
+    model has been touched when it is raised"""
+    from lirec_amd import config
+    from lirec_amd import model as M
+    from lirec_amd._lib import LirecError
+    from lirec_amd.config import opt
+    attached = []
+    monkeypatch.setattr(RecordedTrainStep, '_attach_counters', lambda self: attached.append(self))
+    try:
+        config.recipe('int_rel_ch', joint_dim=16, rels_n_clips=3, text_dim=24, visual_dim=32, track_dim=32)
+        opt.device = 'cpu'
+        model, loss, optim = M.create_model(11, n_rels=5)
+        model.train()
+        model.grad_sync = type('Sync', (), dict(world=2))()
+        for setting in (dict(max_grad_norm=1.0), dict(skip_nonfinite=True)):
+            for k, v in setting.items():
+                setattr(optim, k, v)
+            assert optim.route().norm and optim.route().parallel
+            with pytest.raises(LirecError, match='under data parallelism is not recorded'):
+                RecordedTrainStep(model, loss, optim, {})
+            assert optim._step_dev is None and model._seed_dev is None and not attached
+            optim.max_grad_norm, optim.skip_nonfinite = None, False
+        assert optim.route().refuse is None
+    finally:
+        config.reset()
