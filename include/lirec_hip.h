@@ -788,6 +788,52 @@ int lirec_set_adam_hold(const int64_t* hold_dev, int32_t k);
  * (0, 0.5) (NaN included).  (Added to ABI 124 without a new number: an export only.) */
 #define LIREC_EMA_MAX_BLOCKS 2048
 int lirec_ema_step(float* ema, const float* p, int64_t n, float weight, const float* guard_dev, lirec_stream_t stream);
+/* ---- per-range gradient, weight and update statistics ---------------------------------
+ * What a training dashboard asks of every layer -- gradient norm, weight norm, the size of the Adam step against the weight, and
+ * WHERE a NaN sits -- as one deterministic pass over the flat buffers instead of six torch ops per parameter.  On demand: no other
+ * call issues it.  (Added to ABI 124 without a new number: two new exports and a new struct, index 43 of lirec_abi_sizeof; 42
+ * stays unassigned.)
+ *
+ * `entries` (HOST memory, copied into the launch by value): n_ranges in 1..LIREC_PARAM_STATS_MAX_RANGES ranges
+ * [offset, offset + length) of p / g / m / v -- the four buffers are addressed with the SAME element offsets; ANY offset, any
+ * length >= 0, in any order, overlapping or not.  `flags` says which groups of columns the entry asks for: bit 0 the gradient
+ * (needs g), bit 1 the parameter (needs p), bit 2 the update (needs m and v); a buffer no entry needs may be NULL.  Row r of `out`
+ * (device double[n_ranges][LIREC_PARAM_STATS_COLS]) is
+ *   cols 0-2  over x = g[i]:   the sum of x^2 over the finite x, the largest |x| over the finite x, the count of non-finite x
+ *   cols 3-5  over x = p[i]:   the same three
+ *   cols 6-8  over x = u_i = ((double)m[i] * inv_bc1) / (sqrt((double)v[i]) * inv_sqrt_bc2 + eps), every operation in double and
+ *             rounded on its own: the same three.  An element whose u_i is not finite -- a NaN or infinite m, a NaN or negative v,
+ *             0 / 0 -- is counted and left out.  (v = +Inf with a finite m gives u_i = 0, a finite value.)  With inv_bc1 =
+ *             1 / (1 - beta1^t), inv_sqrt_bc2 = 1 / sqrt(1 - beta2^t), lr * sqrt(col 6) is the norm of Adam's step t.
+ * A group that is not asked for, and every column of an empty range, is 0.  A NaN is counted, never propagated into a sum or a
+ * maximum; -0 and denormals are ordinary finite values; FLT_MAX squared is finite in double and is summed.
+ * DETERMINISM: a row is a pure function of the values in its range and of its own entry -- the same bits on every launch, stream,
+ * device and launch form (eager, recorded), wherever the buffers lie and whatever else the table holds.  The grid is a constant; a range is dealt in blocks of
+ * 1024 elements counted from the multiple of 4 at or below its offset, four consecutive elements a thread; every thread
+ * accumulates in double in element order (the square of an fp32 value is exact there); fixed shuffle / LDS trees, then a second
+ * launch, one workgroup per range, that takes the workgroups' partials in the order of the range's own blocks.  No floating-point atomics.
+ * ALIGNMENT: with every buffer in use on a 16-byte boundary a thread's four elements are one 16-byte load per buffer wherever
+ * they lie inside the range -- the whole of a range whose offset is a multiple of 4 but its last length % 4 elements; up to three
+ * head and three tail elements of another are loaded one by one.  If ANY buffer in use is off a 16-byte boundary (all of them by
+ * the same amount or not) the call falls back to scalar loads of the same elements in the same order: the same bits, more load
+ * instructions.  A pointer that is not 4-byte aligned is refused.
+ * `workspace`: caller-owned device memory of at least lirec_param_stats_ws_bytes(n_ranges) bytes (-1 for n_ranges outside
+ * 1..64), 8-byte aligned, not zeroed by anybody; free again when the call's launches have run.  Two launches (one when every
+ * length is 0) on `stream`, recorded into a command list like any other; profile site "param_stats".
+ * LIREC_EINVAL before any device call (also under the host-side dry run) for: entries NULL; n_ranges outside 1..64; a negative
+ * offset or length, or an end that would wrap; flags outside 0..7; a flag whose buffers are NULL; eps NaN, infinite or negative;
+ * inv_bc1 or inv_sqrt_bc2 NaN or infinite; out or workspace NULL or not 8-byte aligned; workspace_bytes below the query's answer;
+ * p, g, m or v not 4-byte aligned.  TRUSTED: every range lies inside the buffers it asks for. */
+#define LIREC_PARAM_STATS_MAX_RANGES 64
+#define LIREC_PARAM_STATS_COLS 9
+typedef struct {
+  int64_t offset, length;                /* elements */
+  int32_t flags;                         /* bit 0 gradient, bit 1 parameter, bit 2 update */
+  float inv_bc1, inv_sqrt_bc2, eps;      /* of the update columns; ignored without bit 2 (but checked) */
+} lirec_param_stat_entry;
+int64_t lirec_param_stats_ws_bytes(int32_t n_ranges);
+int lirec_param_stats(const float* p, const float* g, const float* m, const float* v, const lirec_param_stat_entry* entries,
+                      int32_t n_ranges, double* out, void* workspace, int64_t workspace_bytes, lirec_stream_t stream);
 /* ---- parameter groups: hyper-parameters in device memory ---------------------------
  * torch.optim.Adam's param_groups, and hyper-parameters that change between the replays of a recorded step (a learning-rate
  * schedule): lr, betas, eps and weight_decay live in a small TABLE in device memory, one 32-byte row per group, that the Adam
@@ -1127,7 +1173,7 @@ int lirec_dropout_mask(uint8_t* keep, int32_t rows, int32_t cols, const lirec_dr
 int lirec_version(void);
 /* sizeof() of ABI struct `which` (5 = eval; 0 embed_fwd, 1 embed_bwd, 2 margin_loss, 3 dropout,
  * 4 rowsel, 6 linear_fwd, 7 linear_bwd, 8 embed_dx, 9 embed_dx_indexed, 10 adam_range, 11 adam_hyper, 12 adam_group_range,
- * 13 eval_topk, 15 predict, 17 collate, 19 clip_weights, 21 feature_rows, 23 collate_field; 14, 16, 18, 20 and 22 are not assigned) so a binding can verify its mirror;
+ * 13 eval_topk, 15 predict, 17 collate, 19 clip_weights, 21 feature_rows, 23 collate_field, 41 draw_context, 43 param_stat_entry; 14, 16, 18, 20, 22, 24 .. 40 and 42 are not assigned) so a binding can verify its mirror;
  * -1 if unknown */
 int lirec_abi_sizeof(int which);
 /* GEMM core: 0 exact f32-input MFMA   1 one-thread-per-output HIP GEMM (bring-up cross-check)

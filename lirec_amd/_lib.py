@@ -130,6 +130,16 @@ CLIP_PARTIALS = 1024          # LIREC_CLIP_PARTIALS: the doubles lirec_grad_sq_p
 EMA_MAX_BLOCKS = 2048         # LIREC_EMA_MAX_BLOCKS: the grid cap of lirec_ema_step (256 threads x one f32x4 a workgroup and pass)
 
 
+class ParamStatEntry(C.Structure):
+    """lirec_param_stat_entry: one range of the flat buffers and the column groups asked of it (lirec_param_stats)"""
+    _fields_ = [('offset', _i64), ('length', _i64), ('flags', _i32), ('inv_bc1', _f32), ('inv_sqrt_bc2', _f32), ('eps', _f32)]
+
+
+PARAM_STATS_MAX_RANGES = 64   # LIREC_PARAM_STATS_MAX_RANGES
+PARAM_STATS_COLS = 9          # LIREC_PARAM_STATS_COLS: (sum of squares, largest magnitude, non-finite count) x (gradient, parameter, update)
+STAT_GRAD, STAT_PARAM, STAT_UPDATE = 1, 2, 4      # lirec_param_stat_entry::flags
+
+
 class LinearFwdArgs(C.Structure):
     _fields_ = [('A', _vp), ('lda', _i64), ('W', _vp), ('b', _vp), ('Y', _vp), ('ldy', _i64),
                 ('n', _i32), ('K', _i32), ('N', _i32), ('reserved_', _i32)]
@@ -292,6 +302,8 @@ _PROTOS = {
     'lirec_accum_begin': (_i32, [_vp, _i64, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _i32, _vp, _i32, _vp]),
     'lirec_set_adam_hold': (_i32, [_vp, _i32]),
     'lirec_ema_step': (_i32, [_vp, _vp, _i64, _f32, _vp, _vp]),
+    'lirec_param_stats_ws_bytes': (_i64, [_i32]),
+    'lirec_param_stats': (_i32, [_vp, _vp, _vp, _vp, C.POINTER(ParamStatEntry), _i32, _vp, _vp, _i64, _vp]),
     'lirec_eval_max_tracks': (_i32, [C.POINTER(EvalArgs), _vp]),
     'lirec_eval_clip_topk': (_i32, [C.POINTER(EvalTopkArgs), _vp]),
     'lirec_predict_clips': (_i32, [C.POINTER(PredictArgs), _vp]),
@@ -351,7 +363,8 @@ def lib():
                                                                                                       (12, AdamGroupRange), (13, EvalTopkArgs),
                                                                                                       (15, PredictArgs), (17, CollateArgs),
                                                                                                       (19, ClipWeights), (21, FeatureRows),
-                                                                                                      (23, CollateField), (41, DrawContextArgs)]:
+                                                                                                      (23, CollateField), (41, DrawContextArgs),
+                                                                                                      (43, ParamStatEntry)]:
         if L.lirec_abi_sizeof(which) != C.sizeof(st):
             raise LirecError('ABI mismatch for %s: library %d bytes, binding %d bytes'
                              % (st.__name__, L.lirec_abi_sizeof(which), C.sizeof(st)))

@@ -83,6 +83,7 @@ def defaults() -> dict:
         skip_nonfinite=False,          # FusedAdam: a step whose trainable gradients hold a NaN / Inf is skipped, on the device (parameters, moments and the bias corrections' step untouched)
         ema_decay=0.0,                 # in (0.5, 1): FusedAdam keeps an exponential moving average of the weights, updated on the device behind every applied step (0: off)
         accumulate_steps=1,            # FusedAdam: one update per this many micro-batches (gradient accumulation; 1: off)
+        param_stats_every=0,           # training(): every this many epochs, print per-parameter gradient / weight norms and the update-to-weight ratio (FusedAdam.param_stats; single process; 0: off)
         eval_ema=False,                # training(): the val / test evaluations run on the averaged weights (optimizer.ema_weights()); mode='train' stays on the live ones
         # per-clip loss weights (batch['clip_weight'], read by all five losses inside the loss kernel): 'sum' divides by the weight
         # sums (a weighted mean, as F.cross_entropy(weight=)), 'count' keeps the counts and the weights are plain multipliers

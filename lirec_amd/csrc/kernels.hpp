@@ -2180,6 +2180,158 @@ __global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ e, const f
 }
 
 // ---------------------------------------------------------------------------
+// Per-range statistics of the flat buffers (lirec_param_stats): for every entry of a table of up to PSTAT_MAX_RANGES ranges, the
+// sum of squares, the largest magnitude and the count of non-finite values of the gradient, of the parameter and of the Adam
+// update direction u = (m inv_bc1) / (sqrt(v) inv_sqrt_bc2 + eps) -- nine doubles a range.  16 bytes per element with all three
+// groups asked for and a double division and square root: HBM-bound.  Two launches:
+//   param_stats_partials_kernel  ALWAYS PSTAT_GRID workgroups -- a constant, never derived from the device.  A range is cut into
+//       blocks of ADAM_RANGE_BLOCK elements counted from the multiple of 4 at or below its offset, numbered across the table
+//       (blk0[r]: the first block of range r, from the host); workgroup w takes blocks w, w + PSTAT_GRID, ...; thread t of a block
+//       the four elements at 4t.  A quad that lies inside the range is four f32x4 loads where the buffers are 16-byte aligned
+//       (`vec`; the caller checked), otherwise -- a range's head and tail, buffers off alignment -- scalar loads of the elements
+//       inside: the SAME elements in the same order either way, so the grouping -- and every bit of the result -- follows from the
+//       table alone, not from where the buffers lie.  Every thread accumulates in double, in element order; a workgroup's blocks
+//       ascend, so it meets the ranges in order and, leaving range r, reduces its nine accumulators in a fixed tree (the wave's
+//       shuffles, the four waves through LDS) and stores them to ws[r][w][0..8] -- once per range it touched.
+//   param_stats_finish_kernel    one workgroup per range: the partials of the workgroups that touched the range -- known from
+//       blk0, so the workspace needs no zeroing -- taken in the order of the range's own blocks, four per thread, then the same
+//       tree; nine plain stores.  A row is therefore a function of its range's values and its own entry alone: the same bits
+//       wherever the entry stands in a table, whatever its neighbours.
+// Sums of squares and counts add, maxima take the larger: no floating-point atomics anywhere, no dependence on arrival order.
+// The square of an fp32 value is exact in double (24-bit significand squared: 48 bits; exponent range +-298 of +-1022), so the
+// gradient and parameter sums round only where two doubles are added; FLT_MAX squared is finite and is summed.  A NaN or an
+// infinity is counted and enters neither the sum nor the maximum.
+// ---------------------------------------------------------------------------
+#define PSTAT_MAX_RANGES 64
+#define PSTAT_GRID 1024
+#define PSTAT_COLS 9
+struct ParamStatTable {
+  long off[PSTAT_MAX_RANGES], len[PSTAT_MAX_RANGES], blk0[PSTAT_MAX_RANGES + 1];
+  int flags[PSTAT_MAX_RANGES];                                    // bit 0 gradient, 1 parameter, 2 update
+  float inv_bc1[PSTAT_MAX_RANGES], inv_sqrt_bc2[PSTAT_MAX_RANGES], eps[PSTAT_MAX_RANGES];
+  int count;
+};
+// (sum of squares, largest magnitude, non-finite count) of one group; the count is a double too: whole numbers below 2^53 add exactly
+struct StatAcc {
+  double sq, mx, bad;
+};
+// |x| <= DBL_MAX is false for a NaN and for an infinity.  A value left out contributes +0 to the sum and the maximum, which
+// changes neither (both are >= 0); -0 and denormals are ordinary values.
+__device__ __forceinline__ void stat_take(StatAcc& a, double x) {
+#pragma clang fp contract(off)
+  const double ax = fabs(x);
+  const bool fin = ax <= 1.7976931348623157e308;
+  const double xf = fin ? ax : 0.0;
+  const double sq = xf * xf;
+  a.sq = a.sq + sq;
+  a.mx = xf > a.mx ? xf : a.mx;
+  a.bad = a.bad + (fin ? 0.0 : 1.0);
+}
+// the update direction of one element, in double, every operation rounded on its own (five roundings: the product, the root, its
+// product, the sum, the quotient).  A negative v gives a NaN, v = 0 with eps = 0 a NaN or an infinity: counted by stat_take.
+__device__ __forceinline__ double stat_update(float m, float v, double inv_bc1, double inv_sqrt_bc2, double eps) {
+#pragma clang fp contract(off)
+  const double num = (double)m * inv_bc1;
+  const double root = sqrt((double)v);
+  const double den = root * inv_sqrt_bc2;
+  return num / (den + eps);
+}
+__device__ __forceinline__ double stat_combine(int col, double a, double b) { return (col % 3 == 1) ? (a > b ? a : b) : a + b; }
+// the workgroup's nine accumulators -> dst[0..8]: the wave's shuffles, then the four waves through LDS, in a fixed order.  Called
+// by every thread of the workgroup; `red` is free again on return.
+__device__ __forceinline__ void stat_block_reduce(const StatAcc (&acc)[3], double (*red)[PSTAT_COLS], double* __restrict__ dst) {
+#pragma unroll
+  for (int c = 0; c < PSTAT_COLS; ++c) {
+    double x = (c % 3 == 0) ? acc[c / 3].sq : ((c % 3 == 1) ? acc[c / 3].mx : acc[c / 3].bad);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x = stat_combine(c, x, __shfl_down(x, o, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][c] = x;
+  }
+  __syncthreads();
+  if (threadIdx.x < PSTAT_COLS) {
+    const int c = threadIdx.x;
+    dst[c] = stat_combine(c, stat_combine(c, red[0][c], red[1][c]), stat_combine(c, red[2][c], red[3][c]));
+  }
+  __syncthreads();
+}
+__global__ __launch_bounds__(256) void param_stats_partials_kernel(const float* __restrict__ p, const float* __restrict__ g,
+                                                                   const float* __restrict__ m, const float* __restrict__ v,
+                                                                   const ParamStatTable tb, int vec, double* __restrict__ ws) {
+  __shared__ double red[4][PSTAT_COLS];
+  StatAcc acc[3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};       // gradient, parameter, update
+  const long nblocks = tb.blk0[tb.count];
+  int r = 0, cur = -1;
+  bool want_g = false, want_p = false, want_u = false;                         // (of the current range: workgroup-uniform)
+  double inv_bc1 = 0.0, inv_sqrt_bc2 = 0.0, eps = 0.0;
+  long lo = 0, hi = 0, base = 0;
+  for (long wb = blockIdx.x; wb < nblocks; wb += PSTAT_GRID) {
+    while (wb >= tb.blk0[r + 1]) ++r;             // (uniform; an empty range has no block and is stepped over)
+    if (r != cur) {                               // (uniform: once per range the workgroup touches)
+      if (cur >= 0) {
+        stat_block_reduce(acc, red, ws + ((long)cur * PSTAT_GRID + blockIdx.x) * PSTAT_COLS);
+        acc[0] = acc[1] = acc[2] = StatAcc{0.0, 0.0, 0.0};
+      }
+      cur = r;
+      const int f = tb.flags[r];
+      want_g = (f & 1) != 0; want_p = (f & 2) != 0; want_u = (f & 4) != 0;
+      inv_bc1 = (double)tb.inv_bc1[r]; inv_sqrt_bc2 = (double)tb.inv_sqrt_bc2[r]; eps = (double)tb.eps[r];
+      lo = tb.off[r]; hi = lo + tb.len[r]; base = (lo & ~3L) - tb.blk0[r] * ADAM_RANGE_BLOCK;
+    }
+    const long at = base + wb * ADAM_RANGE_BLOCK + 4L * threadIdx.x;          // a multiple of 4
+    if (vec && at >= lo && at + 4 <= hi) {
+      f32x4 xg = {0.f, 0.f, 0.f, 0.f}, xp = xg, xm = xg, xv = xg;
+      if (want_g) xg = *reinterpret_cast<const f32x4*>(g + at);
+      if (want_p) xp = *reinterpret_cast<const f32x4*>(p + at);
+      if (want_u) { xm = *reinterpret_cast<const f32x4*>(m + at); xv = *reinterpret_cast<const f32x4*>(v + at); }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (want_g) stat_take(acc[0], (double)xg[j]);
+        if (want_p) stat_take(acc[1], (double)xp[j]);
+        if (want_u) stat_take(acc[2], stat_update(xm[j], xv[j], inv_bc1, inv_sqrt_bc2, eps));
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const long i = at + j;
+        if (i >= lo && i < hi) {
+          if (want_g) stat_take(acc[0], (double)g[i]);
+          if (want_p) stat_take(acc[1], (double)p[i]);
+          if (want_u) stat_take(acc[2], stat_update(m[i], v[i], inv_bc1, inv_sqrt_bc2, eps));
+        }
+      }
+    }
+  }
+  if (cur >= 0) stat_block_reduce(acc, red, ws + ((long)cur * PSTAT_GRID + blockIdx.x) * PSTAT_COLS);
+}
+__global__ __launch_bounds__(256) void param_stats_finish_kernel(const double* __restrict__ ws, const ParamStatTable tb,
+                                                                 double* __restrict__ out) {
+  __shared__ double red[4][PSTAT_COLS];
+  static_assert(PSTAT_GRID % 256 == 0, "every thread looks at the same number of partials");
+  const int r = blockIdx.x;
+  // The range's nb blocks begin at block `first` of the numbering: block k of the range went to workgroup (first + k) % PSTAT_GRID,
+  // so the workgroups that hold a partial are the min(nb, PSTAT_GRID) from first % PSTAT_GRID on, cyclically -- taken in THAT
+  // order, the order of the range's own blocks: the row does not depend on where in the table the range stands.
+  const long first = tb.blk0[r], nb = tb.blk0[r + 1] - first;
+  const int start = (int)(first % PSTAT_GRID), held = nb < PSTAT_GRID ? (int)nb : PSTAT_GRID;
+  StatAcc acc[3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+#pragma unroll
+  for (int j = 0; j < PSTAT_GRID / 256; ++j) {
+    const int d = (int)threadIdx.x * (PSTAT_GRID / 256) + j;
+    if (d < held) {
+      const int w = (start + d) % PSTAT_GRID;
+      const double* q = ws + ((long)r * PSTAT_GRID + w) * PSTAT_COLS;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        acc[k].sq = acc[k].sq + q[3 * k];
+        acc[k].mx = q[3 * k + 1] > acc[k].mx ? q[3 * k + 1] : acc[k].mx;
+        acc[k].bad = acc[k].bad + q[3 * k + 2];
+      }
+    }
+  }
+  stat_block_reduce(acc, red, out + (long)r * PSTAT_COLS);
+}
+
+// ---------------------------------------------------------------------------
 // Evaluation counters (lirec_eval_max_tracks; utils/evaluation.py:114-176, :179-271).  One workgroup per clip.
 // ---------------------------------------------------------------------------
 // (value, index) with numpy argmax semantics: the larger value wins, ties go to the lower index; index 0x7fffffff = empty.

@@ -3,6 +3,7 @@
 // checks, GEMM problem descriptors, kernel launches on the caller's stream.
 // No allocation, no synchronisation, no exceptions.
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -54,10 +55,11 @@ static thread_local lirec_ctx* t_ctx = &g_default_ctx;
 // ---------------------------------------------------------------------------
 enum { PS_EMBED_L1_FWD = 0, PS_EMBED_L2_FWD, PS_EMBED_DW2, PS_EMBED_DZ1, PS_EMBED_DW1, PS_GATE_FWD, PS_GATE_DW,
        PS_GATE_DEE, PS_LINEAR_FWD, PS_LINEAR_DW, PS_LINEAR_DA, PS_POOL_FWD, PS_POOL_BWD, PS_LOSS, PS_ADAM, PS_CAST,
-       PS_STAGE, PS_EMBED_DW1_RED, PS_GATE_STAGE, PS_COUNT };
+       PS_STAGE, PS_EMBED_DW1_RED, PS_GATE_STAGE, PS_PARAM_STATS, PS_COUNT };
 static const char* const g_site_names[PS_COUNT] = {
     "embed_l1_fwd", "embed_l2_fwd", "embed_dW2", "embed_dZ1", "embed_dW1", "gate_fwd", "gate_dW", "gate_dEE",
-    "linear_fwd", "linear_dW", "linear_dA", "pool_fwd", "pool_bwd", "loss", "adam", "cast", "stage", "embed_dW1_reduce", "gate_stage"};
+    "linear_fwd", "linear_dW", "linear_dA", "pool_fwd", "pool_bwd", "loss", "adam", "cast", "stage", "embed_dW1_reduce", "gate_stage",
+    "param_stats"};
 #define PROF_CAP 1024
 struct ProfRec { hipEvent_t a, b; int site; };
 static int g_prof_on = 0, g_nrec = 0, g_nev = 0;
@@ -1164,6 +1166,7 @@ int lirec_abi_sizeof(int which) {
     case 21: return (int)sizeof(lirec_feature_rows);         // (20 stays unassigned)
     case 23: return (int)sizeof(lirec_collate_field);        // (22 stays unassigned)
     case 41: return (int)sizeof(lirec_draw_context_args);    // (24 .. 40 stay unassigned)
+    case 43: return (int)sizeof(lirec_param_stat_entry);     // (42 stays unassigned)
     default: return -1;
   }
 }
@@ -2806,6 +2809,52 @@ int lirec_ema_step(float* ema, const float* p, int64_t n, float weight, const fl
   if (blocks < 1) blocks = 1;
   lirec::launch(ema_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ema, p, (long)n, (int)head, weight, guard_dev,
                 (const long long*)t_adam.hold);
+  LIREC_CHECK_LAUNCH();
+  return LIREC_OK;
+}
+
+int64_t lirec_param_stats_ws_bytes(int32_t n_ranges) {
+  static_assert(LIREC_PARAM_STATS_MAX_RANGES == PSTAT_MAX_RANGES && LIREC_PARAM_STATS_COLS == PSTAT_COLS,
+                "the header's table size and row width are the kernels'");
+  if (n_ranges < 1 || n_ranges > PSTAT_MAX_RANGES) return -1;
+  return (int64_t)n_ranges * PSTAT_GRID * PSTAT_COLS * (int64_t)sizeof(double);
+}
+
+int lirec_param_stats(const float* p, const float* g, const float* m, const float* v, const lirec_param_stat_entry* entries,
+                      int32_t n_ranges, double* out, void* workspace, int64_t workspace_bytes, lirec_stream_t stream) {
+  if (!entries || n_ranges < 1 || n_ranges > PSTAT_MAX_RANGES) return LIREC_EINVAL;
+  if (!out || !workspace || ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) & 7) != 0) return LIREC_EINVAL;
+  if (workspace_bytes < lirec_param_stats_ws_bytes(n_ranges)) return LIREC_EINVAL;
+  const uintptr_t addr = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                         reinterpret_cast<uintptr_t>(v);            // (a NULL pointer adds no bit)
+  if ((addr & 3) != 0) return LIREC_EINVAL;
+  ParamStatTable tb;
+  memset(&tb, 0, sizeof(tb));
+  double bytes = 0.0;
+  for (int r = 0; r < n_ranges; ++r) {
+    const lirec_param_stat_entry& e = entries[r];
+    if (e.offset < 0 || e.length < 0 || e.length > INT64_MAX - 8 - e.offset) return LIREC_EINVAL;      // (offset + length would wrap)
+    if (e.flags < 0 || e.flags > 7) return LIREC_EINVAL;
+    if (((e.flags & 1) && !g) || ((e.flags & 2) && !p) || ((e.flags & 4) && (!m || !v))) return LIREC_EINVAL;
+    if (!(e.eps >= 0.f && e.eps <= FLT_MAX) || !(fabsf(e.inv_bc1) <= FLT_MAX) || !(fabsf(e.inv_sqrt_bc2) <= FLT_MAX))
+      return LIREC_EINVAL;                                                                              // (NaN included)
+    tb.off[r] = (long)e.offset; tb.len[r] = (long)e.length; tb.flags[r] = e.flags;
+    tb.inv_bc1[r] = e.inv_bc1; tb.inv_sqrt_bc2[r] = e.inv_sqrt_bc2; tb.eps[r] = e.eps;
+    // blocks of ADAM_RANGE_BLOCK elements counted from the multiple of 4 at or below the offset; none for an empty range
+    const int64_t span = (e.offset & 3) + e.length;
+    tb.blk0[r + 1] = tb.blk0[r] + (long)(e.length ? (span + ADAM_RANGE_BLOCK - 1) / ADAM_RANGE_BLOCK : 0);
+    bytes += 4.0 * (double)e.length * ((e.flags & 1) + ((e.flags >> 1) & 1) + ((e.flags >> 2) & 1) * 2);
+  }
+  tb.count = n_ranges;
+  // f32x4 loads where every buffer in use lies on a 16-byte boundary; otherwise the scalar loads of the same elements
+  const int vec = (addr & 15) == 0;
+  hipStream_t s = (hipStream_t)stream;
+  const int pi = prof_start(PS_PARAM_STATS, s);
+  // (a table without a block -- every length 0 -- still runs the second launch: it writes the rows of zeros)
+  if (tb.blk0[n_ranges] > 0)
+    lirec::launch(param_stats_partials_kernel, dim3(PSTAT_GRID), dim3(256), 0, s, p, g, m, v, tb, vec, (double*)workspace);
+  lirec::launch(param_stats_finish_kernel, dim3((unsigned)n_ranges), dim3(256), 0, s, (const double*)workspace, tb, out);
+  prof_stop(pi, s, 0.0, bytes);
   LIREC_CHECK_LAUNCH();
   return LIREC_OK;
 }

@@ -909,6 +909,33 @@ def grad_sq_partials(g, ranges, partials):
     check(lib().lirec_grad_sq_partials(_p(_f32c(g)), _range_array([r[:2] for r in ranges]), len(ranges), _p(partials), _stream()), 'lirec_grad_sq_partials')
 
 
+def param_stats_ws_bytes(n_ranges):
+    """lirec_param_stats_ws_bytes: the bytes of workspace a ``param_stats`` call over ``n_ranges`` entries needs"""
+    return int(lib().lirec_param_stats_ws_bytes(int(n_ranges)))
+
+
+def param_stats(p, g, m, v, entries, out, ws):
+    """lirec_param_stats: row r of ``out`` (device float64[len(entries), 9], contiguous) = (sum of squares over the finite values,
+    largest finite magnitude, count of non-finite values) of the gradient ``g``, of the parameter ``p`` and of the update direction
+    (m inv_bc1) / (sqrt(v) inv_sqrt_bc2 + eps) over elements [offset, offset + length) of the flat fp32 buffers -- ``entries`` =
+    [(offset, length, flags[, inv_bc1, inv_sqrt_bc2, eps]), ...] (1..64, any offsets), ``flags``: 1 gradient | 2 parameter | 4 update;
+    a group not asked for is 0, and a buffer no entry asks for may be None.  ``ws``: device scratch of at least
+    ``param_stats_ws_bytes(len(entries))`` bytes.  Two launches on the current stream; the same bits every time."""
+    from ._lib import PARAM_STATS_COLS, ParamStatEntry
+    n = len(entries)
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= PARAM_STATS_COLS * n
+    assert ws.is_contiguous()
+    arr = (ParamStatEntry * max(n, 1))()
+    for a, e in zip(arr, entries):
+        a.offset, a.length, a.flags = int(e[0]), int(e[1]), int(e[2])
+        a.inv_bc1, a.inv_sqrt_bc2, a.eps = (float(e[3]), float(e[4]), float(e[5])) if len(e) > 3 else (1.0, 1.0, 0.0)
+        for bit, bufs in ((1, (g,)), (2, (p,)), (4, (m, v))):
+            if a.flags & bit:
+                assert all(b is not None and a.offset + a.length <= b.numel() for b in bufs), 'a range outside the buffers it asks for'
+    bufs = [None if b is None else _p(_f32c(b)) for b in (p, g, m, v)]
+    check(lib().lirec_param_stats(*bufs, arr, n, _p(out), _p(ws), ws.numel() * ws.element_size(), _stream()), 'lirec_param_stats')
+
+
 def clip_finalize(partials, sq, mode, grad_scale, max_norm, out):
     """lirec_clip_finalize: ``sq`` (device float64[1]) = / += the sum of ``partials`` (mode 0 / 1; 2: as it stands), then
     ``out`` (device float32[2]) = (clip coefficient, norm = sqrt(sq) * grad_scale)"""

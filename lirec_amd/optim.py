@@ -87,6 +87,12 @@ average takes one lerp per applied window; ``state_dict()`` counts updates.  A c
 window's gradients.  In the eager loop the host takes the hold / apply decision; a recorded step re-issues the same launches every
 micro-step, so there it lives in device memory (``_win_dev``, the window block of lirec_accum_begin; the update's launches under
 ``ops.adam_hold``) -- ``begin_micro_step`` is that step's head.
+
+Per-parameter statistics (``param_stats()``, ``nonfinite_params()``; on demand -- no step issues them): gradient norm and largest
+magnitude as the update sees them, weight norm, the size of the last applied Adam step against the weight and the counts of
+non-finite elements, for every parameter, from one deterministic pass over the four flat buffers (``lirec_param_stats``: double
+accumulation in a fixed order, no atomics, the same bits every call).  Single process only: under data parallelism the moments and
+the reduced gradients live in slices, and a defined answer would need collectives.
 """
 from __future__ import annotations
 
@@ -106,6 +112,33 @@ from .config import opt
 # (folded into the backward: by value, reading one device row, through the per-parameter map), 'untouched' (frozen altogether) or
 # 'ordinary'; may_overwrite: the weight gradients may overwrite the buffer; refuse: why the step cannot be recorded, or None
 Route = collections.namedtuple('Route', 'hold norm guard window parallel lane0 first may_overwrite refuse')
+
+# One parameter's row of ``ParamStats.host()``.  A column that was not asked for is None.
+ParamStat = collections.namedtuple('ParamStat', 'grad_norm grad_absmax grad_nonfinite param_norm param_absmax param_nonfinite '
+                                                'update_norm update_absmax update_nonfinite update_ratio')
+
+
+class ParamStats:
+    """What ``FusedAdam.param_stats()`` returns.  ``names``: every parameter in ``model.named_parameters()`` order; ``table``: device
+    float64 [P, 9], row i the raw columns of lirec_param_stats for ``names[i]`` (sums of squares, unscaled maxima, counts; a group
+    that was not asked for is 0 there) -- no synchronisation; ``flags``: per row, which groups were asked for (1 gradient,
+    2 parameter, 4 update); ``scale``: what the update multiplies the gradients by; ``lrs``: each parameter's group's lr.
+    ``host()``: ONE copy to the host, then {name: ParamStat}."""
+
+    def __init__(self, names, table, flags, scale, lrs):
+        self.names, self.table, self.flags, self.scale, self.lrs = list(names), table, list(flags), float(scale), list(lrs)
+
+    def host(self):
+        from ._lib import STAT_GRAD, STAT_PARAM, STAT_UPDATE
+        rows = self.table.cpu().tolist()
+        out = collections.OrderedDict()
+        for name, row, f, lr in zip(self.names, rows, self.flags, self.lrs):
+            g = (row[0] ** 0.5 * self.scale, row[1] * self.scale, int(row[2])) if f & STAT_GRAD else (None,) * 3
+            p = (row[3] ** 0.5, row[4], int(row[5])) if f & STAT_PARAM else (None,) * 3
+            u = (lr * row[6] ** 0.5, lr * row[7], int(row[8])) if f & STAT_UPDATE else (None,) * 3
+            ratio = u[0] / p[0] if (u[0] is not None and p[0]) else None
+            out[name] = ParamStat(*g, *p, *u, ratio)
+        return out
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -687,6 +720,86 @@ class FusedAdam(torch.optim.Optimizer):
             self._finalize(self._clip_partials, 0 if first else 1)
             first = False
         return first
+
+    # -- per-parameter statistics ---------------------------------------------------
+    @staticmethod
+    def stat_factors(t, beta1, beta2):
+        """(inv_bc1, inv_sqrt_bc2) of update ``t`` >= 1 as a lirec_param_stat_entry carries them: 1 / (1 - beta1^t) and
+        1 / sqrt(1 - beta2^t), computed in double and rounded to fp32"""
+        t = max(int(t), 1)
+        return (C.c_float(1.0 / (1.0 - float(beta1) ** t)).value, C.c_float(1.0 / (1.0 - float(beta2) ** t) ** 0.5).value)
+
+    def _stats_refusals(self, what):
+        self._ema_not_recording(what)
+        if getattr(getattr(self.model, 'grad_sync', None), 'world', 1) > 1:
+            from ._lib import LirecError
+            raise LirecError('FusedAdam.%s: single-process only -- under data parallelism the moments are current in this rank\'s '
+                             'slices alone and the reduced gradient lives in slice buffers, so a defined answer needs collectives, '
+                             'which this call deliberately does not issue' % what)
+
+    @torch.no_grad()
+    def param_stats(self, update=True):
+        """Per-parameter statistics of the gradient, the weight and the last Adam step, computed on the device in one
+        deterministic pass over the flat buffers (lirec_param_stats: two launches per 64 parameters, the same bits every time).
+        Returns a ``ParamStats``: ``names``, the device ``table`` (no synchronisation) and ``host()`` -- one copy, then
+        {name: ParamStat}.  One row per parameter, over exactly its ``numel`` elements: the alignment gaps of the flat layout are in
+        no row.
+
+        Gradient columns, for the parameters that require grad NOW: ``grad_norm`` = the L2 norm of the gradient buffer times
+        ``grad_scale`` -- over k inside or at the end of an accumulation window, where the buffer holds the unscaled sum so far --,
+        i.e. AS THE UPDATE SEES IT; ``grad_absmax`` scaled the same way; ``grad_nonfinite`` the count of NaN / Inf elements, which
+        enter neither of the two.  With clipping on and no non-finite value, the root of the sum of the trainable parameters'
+        squared norms is ``optimizer.grad_norm``.
+        Parameter columns, for every parameter: ``param_norm``, ``param_absmax``, ``param_nonfinite``.
+        Update columns (``update=True``), for the parameters that have received at least one update: with t that number of
+        updates and lr, betas, eps of the parameter's group, u = (m / (1 - beta1^t)) / (sqrt(v) / sqrt(1 - beta2^t) + eps) and
+        ``update_norm`` = lr ||u||, ``update_absmax`` = lr max|u|, ``update_ratio`` = update_norm / param_norm (None where the
+        norm is 0).  This is the size of the last APPLIED Adam step as the moments hold it now: decoupled weight decay's separate
+        term p (1 - lr wd) is not in it, and where the last ``step()`` was a hold or was skipped it still describes the step
+        before.  t comes from ``updates_received`` -- lags, and the device count of skipped steps when a guard has been on: that
+        is ONE READ OF A DEVICE INT, A SYNCHRONISATION, as ``skipped_total()`` is; ``update=False`` never synchronises.
+        A column that was not asked for -- gradient and update columns of a frozen parameter, update columns of a parameter never
+        updated or with ``update=False`` -- is None in ``host()``.
+
+        Joins the side stream first, so it is correct between replays of a recorded step.  RuntimeError while a step is being
+        recorded; LirecError under data parallelism (see the message)."""
+        from ._lib import PARAM_STATS_COLS, PARAM_STATS_MAX_RANGES, STAT_GRAD, STAT_PARAM, STAT_UPDATE
+        self._stats_refusals('param_stats()')
+        self._ensure_state()
+        self._join_side()
+        m = self.model
+        flat, g = m.flat_params(), m.flat_grads(attach=True)
+        live = self._flags()
+        counts = [0] * len(self._names)
+        if update:
+            S = self._read_skipped()
+            counts = self.updates_received(self._step, [self._lag.get(n, 0) for n in self._names],
+                                           self._guard_flags if S else live, S)
+        entries, flags, lrs = [], [], []
+        for n, f, t in zip(self._names, live, counts):
+            off, k = m._offsets[n]
+            grp = self.param_groups[self._group_of[n]]
+            fl = STAT_PARAM | (STAT_GRAD if f else 0) | (STAT_UPDATE if t >= 1 else 0)
+            fac = self.stat_factors(t, *grp['betas']) + (float(grp['eps']),) if t >= 1 else (1.0, 1.0, 0.0)
+            entries.append((off, k, fl) + fac)
+            flags.append(fl)
+            lrs.append(float(grp['lr']))
+        table = torch.empty((len(entries), PARAM_STATS_COLS), dtype=torch.float64, device=flat.device)
+        ws = getattr(self, '_stats_ws', None)
+        if ws is None or ws.device != flat.device:
+            ws = self._stats_ws = torch.empty(ops.param_stats_ws_bytes(PARAM_STATS_MAX_RANGES) // 8, dtype=torch.float64, device=flat.device)
+        row = 0
+        for ch in self._chunks(entries, PARAM_STATS_MAX_RANGES):      # (one stream: a chunk's launches are through with ws before the next's)
+            ops.param_stats(flat, g, self._m, self._v, ch, table[row:row + len(ch)], ws)
+            row += len(ch)
+        return ParamStats(self._names, table, flags, self._scale(), lrs)
+
+    def nonfinite_params(self):
+        """the names of the parameters whose gradient holds a NaN or an Inf right now: one ``param_stats(update=False)`` and one
+        read.  After a step that ``skip_nonfinite`` skipped it names the culprits -- the gradients stay as backward left them.
+        The refusals of ``param_stats()``."""
+        self._stats_refusals('nonfinite_params()')
+        return [n for n, s in self.param_stats(update=False).host().items() if s.grad_nonfinite]
 
     # -- the update's route ----------------------------------------------------------
     def route(self, pipelined=False):

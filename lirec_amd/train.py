@@ -332,6 +332,18 @@ def _evaluate_and_keep(epoch, start, train_dataset, val_dataset, test_dataset, m
             testing(test_dataset, model, loss, total_iter=epoch, train_start_time=start, mode='test')
 
 
+def _print_param_stats(optimizer, say):
+    """one line per parameter from ONE ``param_stats().host()`` read: the norms as the update sees them, the size of the last Adam
+    step against the weight, and the non-finite counts where there are any (a frozen parameter has no gradient columns, a
+    parameter never updated no ratio: '-')"""
+    fmt = lambda x: '-' if x is None else '%.4e' % x
+    say('parameter statistics (grad_norm, grad_absmax, param_norm, update_ratio):')
+    for name, s in optimizer.param_stats().host().items():
+        bad = ['%s %d' % (k, c) for k, c in (('grad', s.grad_nonfinite), ('param', s.param_nonfinite), ('update', s.update_nonfinite)) if c]
+        say('  %-40s %s  %s  %s  %s%s' % (name, fmt(s.grad_norm), fmt(s.grad_absmax), fmt(s.param_norm), fmt(s.update_ratio),
+                                         '  non-finite: ' + ', '.join(bad) if bad else ''))
+
+
 def training(train_dataset, **kwargs):
     rank, world = parallel.world_info()
     print = _print if rank == 0 else (lambda *a, **k: None)        # (one log, rank 0's)
@@ -360,6 +372,13 @@ def training(train_dataset, **kwargs):
     stats = training.last = {'replays': 0, 'input_copies': 0, 'loader': loader}
     to_dev = getattr(train_dataset, 'to_device', None) if str(opt.device).startswith('cuda') else None
     stepper = _Stepper(model, loss, optimizer, world, loader, stats, to_device=to_dev, say=print)
+    # opt.param_stats_every = N: at the end of every N-th epoch one line per parameter (FusedAdam.param_stats: two launches and ONE
+    # read); single process only -- under data parallelism one notice, and nothing else.  0 issues nothing.
+    stats_every = int(getattr(opt, 'param_stats_every', 0) or 0) if hasattr(optimizer, 'param_stats') else 0
+    if stats_every and max(world, getattr(getattr(model, 'grad_sync', None), 'world', 1)) > 1:
+        print('param_stats_every: per-parameter statistics are single-process only (under data parallelism they would need '
+              'collectives); ignored')
+        stats_every = 0
 
     def batches():
         it = iter(loader)
@@ -409,6 +428,8 @@ def training(train_dataset, **kwargs):
         print('train clips/s: %.1f' % (seen / max(time.time() - t_epoch, 1e-9)))
         if guarded():
             print('skipped steps: %d' % optimizer.skipped_total())        # (one read per epoch)
+        if stats_every and (epoch + 1) % stats_every == 0:
+            _print_param_stats(optimizer, print)
         losses.reset()
         if epoch % opt.test_fr == 0:
             _evaluate_and_keep(epoch, start, train_dataset, val_dataset, test_dataset, model, loss, optimizer, saver, rank, world)
