@@ -456,7 +456,7 @@ class _HotPathModule(nn.Module):
         m = getattr(self, name)
         return m.weight, m.bias
 
-    def _planes_buffer(self, X, rows, segs, J):
+    def _planes_buffer(self, X, rows, segs, J, R=0):
         """Workspace for layer 1 on q32b operands (opt.layer1_planes; lirec_embed_fwd_args.planes): the library uses it
         when the shapes qualify and splits on the fly otherwise.  Kept from forward to backward.  Training steps only:
         staging the feature rows pays because the weight gradient reads the staged rows again; the forward-only step keeps
@@ -473,6 +473,15 @@ class _HotPathModule(nn.Module):
             #  take `last_layer1_planes` for a promise that the fused first-layer update and the W1 shadow apply, which it then refuses)
             return None
         if bf16 and (not self.training or getattr(self, '_pieces_cur', None) is not None):
+            return None
+        if self._has_ctx and R > 64:
+            # (``R``: the context clips per candidate of this call.  More than 64: the library declines the pooled head's workspace --
+            #  its un-pool pass on planes holds one row weight per lane -- and with it the other head's of the same call
+            #  (lirec_hip.hip: plane_layout, planes_for_heads); both run on the on-the-fly core.  As above: no workspace, so that
+            #  `last_layer1_planes` promises nothing -- a recorded step folded the first-layer update on that promise and was refused)
+            if q32 or isinstance((getattr(self, '_pieces_cur', None) or {}).get('clip'), ops.Q32Block):
+                raise LirecError('q32b feature storage is read by the q32b layer-1 kernels only, which serve at most 64 context clips '
+                                 'per candidate (this batch: %d) -- give the features as an fp32 block' % R)
             return None
         # forward-only steps: the persistent kernels when the features are STORED as q32b (the rows are gathered, nothing is
         # staged: layer 1 at 146 us against the on-the-fly kernel's 203 at the bench shape); an fp32 block would have to be
@@ -515,8 +524,8 @@ class _HotPathModule(nn.Module):
         cmp = ops.compact_rows(mask, n, R, out=into['cmp'] if into else None) if opt.compact_ctx_rows else None
         if cmp is None and mask.dtype != torch.float32:
             raise LirecError('prestage needs opt.compact_ctx_rows')
-        pl_i = into['planes_i'] if into else self._planes_buffer(X, n, self._segs_i, J)
-        pl_c = into['planes_c'] if into else self._planes_buffer(X, n * R, self._segs_c, J)
+        pl_i = into['planes_i'] if into else self._planes_buffer(X, n, self._segs_i, J, R)
+        pl_c = into['planes_c'] if into else self._planes_buffer(X, n * R, self._segs_c, J, R)
         # the key of the step that will use the rows (see _begin_forward)
         if self._seed_dev is not None:
             seed = (int(opt.dropout_seed) - 1 + 1 + advance) & 0xFFFFFFFFFFFFFFFF     # that step's key = this + the device counter now
@@ -591,7 +600,7 @@ class _HotPathModule(nn.Module):
                                       W1q=self._w1q_of(head.mods, pl), **kw)
         if has_i:
             H1 = ops.new((n, self._segs_i.n * J), dtype=torch.float32, device=dev)
-            pl = pre['planes_i'] if pre is not None else self._planes_buffer(X, n, self._segs_i, J)
+            pl = pre['planes_i'] if pre is not None else self._planes_buffer(X, n, self._segs_i, J, R)
             args_i = head_args(self._head_i, H1, pl)
             st['H1_i'], st['planes_i'] = H1, pl
         if has_c:
@@ -612,7 +621,7 @@ class _HotPathModule(nn.Module):
             if cmp is not None:
                 mask = None
             st['mask'] = mask
-            pl = pre['planes_c'] if pre is not None else self._planes_buffer(X, n * R, segs, J)
+            pl = pre['planes_c'] if pre is not None else self._planes_buffer(X, n * R, segs, J, R)
             if pre is not None:
                 self.last_layer1_planes = True
             # (training steps: the pooling pass, which reads every valid row of H1 anyway, also leaves the SIGN BITS of H1 -- all
