@@ -1020,6 +1020,27 @@ typedef struct {
   int32_t B, T, C, NR, K, loader_types;
 } lirec_predict_args;
 int lirec_predict_clips(const lirec_predict_args* a, lirec_stream_t stream);
+/* lirec_predict_clips with every non-NULL output pointer the base of a DATASET-SIZED array: clip b writes row cursor[0] + b of each
+ * (trk_score: T doubles a row, the top lists: K entries a row).  cursor: an int64 device word the kernel reads when it runs (once
+ * per workgroup), so the launch, recorded into a command list, writes where the cursor points at replay time.  The launch does not
+ * move the cursor: lirec_counter_add(cursor, {B}, 1, stream) behind it does.  The same kernel body -- one workgroup per clip, one
+ * writer per element, the same LDS limit -- and the same LIREC_EINVAL cases as lirec_predict_clips, plus a NULL or misaligned
+ * (8 bytes) cursor; all before any device call, also under the dry run.  TRUSTED, as lirec_collate_fields_at trusts its cursor:
+ * 0 <= cursor[0] and cursor[0] + B <= the arrays' rows.  (Added to ABI 124 without a new number: one new export, no struct changes.) */
+int lirec_predict_clips_at(const lirec_predict_args* a, const int64_t* cursor, lirec_stream_t stream);
+/* dst row cursor[0] + r = src row r for r < rows: fp32, `cols` values a row (any cols >= 1: no multiple of 4 asked), row strides
+ * ld_src / ld_dst in elements (src may be a strided view: row 0 of each clip's group of rows).  What a forward-only command list
+ * keeps a batch's rows with in a dataset-sized buffer (the deferred relationship logits of the clip-level evaluation).  cursor as
+ * above: read by the kernel when it runs, not moved, trusted.  One launch, one writer per element.  LIREC_EINVAL before any device
+ * call (also under the dry run) for a NULL src, dst or cursor; rows < 0, cols < 1, ld_src or ld_dst < cols; src / dst not 4-byte,
+ * cursor not 8-byte aligned.  rows == 0: no launch, LIREC_OK.  (ABI 124: one new export.) */
+int lirec_rows_copy_at(const float* src, int64_t ld_src, int32_t rows, int32_t cols, float* dst, int64_t ld_dst, const int64_t* cursor,
+                       lirec_stream_t stream);
+/* acc[0] += v[0] on the device, in the accumulator's own type: fp32 (acc_f64 == 0) or float64 -- the fp32 addend converted first, one
+ * rounding: bit for bit what torch's `acc += v` gives on the same device tensors.  One thread, a plain load and store: launches on
+ * one stream are ordered, and nothing else may write acc meanwhile.  LIREC_EINVAL (also under the dry run) for a NULL acc or v, acc
+ * not 4-byte (float64: 8-byte) aligned, v not 4-byte aligned.  (ABI 124: one new export.) */
+int lirec_scalar_accumulate(void* acc, int32_t acc_f64, const float* v, lirec_stream_t stream);
 
 /* ---- collate on the device (resident piece store) ----------------------------------
  * The loader's per-batch work for a dataset whose pieces AND whose stacked sample tables are resident: what

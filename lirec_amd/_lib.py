@@ -307,6 +307,9 @@ _PROTOS = {
     'lirec_eval_max_tracks': (_i32, [C.POINTER(EvalArgs), _vp]),
     'lirec_eval_clip_topk': (_i32, [C.POINTER(EvalTopkArgs), _vp]),
     'lirec_predict_clips': (_i32, [C.POINTER(PredictArgs), _vp]),
+    'lirec_predict_clips_at': (_i32, [C.POINTER(PredictArgs), _vp, _vp]),
+    'lirec_rows_copy_at': (_i32, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp]),
+    'lirec_scalar_accumulate': (_i32, [_vp, _i32, _vp, _vp]),
     'lirec_collate_workspace_bytes': (_i64, [_i64, _i64]),
     'lirec_collate_resident': (_i32, [C.POINTER(CollateArgs), _vp]),
     'lirec_collate_fields': (_i32, [_vp, _i32, C.POINTER(CollateField), _i32, _vp]),

@@ -40,6 +40,11 @@ def defaults() -> dict:
         save_model=True, save_model_often=False, test=True, test_fr=2,
         resume=False, resume_train=False, resume_str='', model_name='',
         store_root='./store', sanity_check=False, log_prefix='',
+        # loop control of testing() / predict(), not in the reference (no step's numbers depend on it; tests/test_gpu_recorded_eval.py):
+        # over a resident block store, single GPU, device-side counters, the forward-only iteration (draw, forward, loss, counters /
+        # predictions) is recorded on the second full batch and replayed for every further one (lirec_amd.graph.RecordedEvalStep);
+        # short, singleton and host-prepared batches step eagerly.  Same bits as the eager loop.
+        record_eval=False,
         # build-side additions (not in the reference)
         dp_shard_eval=True,       # torch.distributed: testing() evaluates each clip on ONE rank and sums the counters (lirec_amd/test.py)
         # eval counters on the GPU, read once at the end, for all four recipes: max over tracks (lirec_eval_max_tracks) and clip-level

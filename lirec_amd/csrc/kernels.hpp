@@ -2610,7 +2610,9 @@ __device__ __forceinline__ void rank_select(const int* key, int n, int K, const 
   }
 }
 
-__global__ __launch_bounds__(256) void predict_clips_kernel(const lirec_predict_args a) {
+// The body of both kernels: clip b = blockIdx.x reads its logits at row b and writes row `ob` of every output array -- ob = b for
+// lirec_predict_clips, *cursor + b for lirec_predict_clips_at.
+__device__ __forceinline__ void predict_clips_body(const lirec_predict_args& a, const long ob) {
   extern __shared__ __attribute__((aligned(16))) float pr_sm[];
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   const bool has_rels = a.rels != nullptr;
@@ -2662,7 +2664,7 @@ __global__ __launch_bounds__(256) void predict_clips_kernel(const lirec_predict_
   }
   if (a.trk_score) {
     if (!has_rels || T > 64) track_maxima(S, Q, T, C, NR1, Mt);      // (with rels and T <= 64 the joint search has filled Mt)
-    for (int t = tid; t < T; t += nt) a.trk_score[(long)b * T + t] = Mt[t];
+    for (int t = tid; t < T; t += nt) a.trk_score[ob * T + t] = Mt[t];
   }
   // the top lists of the predicted track: its masked logits once more, as keys
   const bool want_cls = a.top_cls || a.top_cls_p, want_rel = has_rels && (a.top_rel || a.top_rel_p);
@@ -2675,20 +2677,28 @@ __global__ __launch_bounds__(256) void predict_clips_kernel(const lirec_predict_
       for (int c = tid; c < NR; c += nt) rkey[c] = topk_key(pad ? NEG_INF : a.rels[row * a.ld_rels + c]);
     __syncthreads();
     if (want_cls)
-      rank_select(key, C, K, S + j_trk * C, a.top_cls ? a.top_cls + (long)b * K : nullptr,
-                  a.top_cls_p ? a.top_cls_p + (long)b * K : nullptr);
+      rank_select(key, C, K, S + j_trk * C, a.top_cls ? a.top_cls + ob * K : nullptr,
+                  a.top_cls_p ? a.top_cls_p + ob * K : nullptr);
     if (want_rel)
-      rank_select(rkey, NR, K, Q + j_trk * NR1, a.top_rel ? a.top_rel + (long)b * K : nullptr,
-                  a.top_rel_p ? a.top_rel_p + (long)b * K : nullptr);
+      rank_select(rkey, NR, K, Q + j_trk * NR1, a.top_rel ? a.top_rel + ob * K : nullptr,
+                  a.top_rel_p ? a.top_rel_p + ob * K : nullptr);
   }
   if (tid == 0) {
-    a.trk[b] = j_trk;
-    if (a.cls) a.cls[b] = j_cls;
-    if (a.rel) a.rel[b] = j_rel;
+    a.trk[ob] = j_trk;
+    if (a.cls) a.cls[ob] = j_cls;
+    if (a.rel) a.rel[ob] = j_rel;
     if (a.score)
-      a.score[b] = has_rels ? (double)S[j_trk * C + j_cls] + (double)Q[j_trk * NR1 + j_rel] : (double)S[j_trk * C + j_cls];
-    if (a.flags) a.flags[b] = flg[0] | (flg[1] ? 0 : 2);
+      a.score[ob] = has_rels ? (double)S[j_trk * C + j_cls] + (double)Q[j_trk * NR1 + j_rel] : (double)S[j_trk * C + j_cls];
+    if (a.flags) a.flags[ob] = flg[0] | (flg[1] ? 0 : 2);
   }
+}
+
+__global__ __launch_bounds__(256) void predict_clips_kernel(const lirec_predict_args a) { predict_clips_body(a, (long)blockIdx.x); }
+
+// lirec_predict_clips_at: the outputs are dataset-sized arrays and clip b writes row *cursor + b -- a device word every workgroup
+// reads once, so a launch replayed from a command list writes where the cursor points at replay time.
+__global__ __launch_bounds__(256) void predict_clips_at_kernel(const lirec_predict_args a, const long long* __restrict__ cursor) {
+  predict_clips_body(a, (long)*cursor + (long)blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -2838,6 +2848,26 @@ __global__ __launch_bounds__(256) void collate_fields_at_kernel(const CollateFie
   else if ((al & 7) == 0) collate_copy_rows<uint2>(f, ids, a.B);
   else if ((al & 3) == 0) collate_copy_rows<unsigned>(f, ids, a.B);
   else collate_copy_rows<unsigned char>(f, ids, a.B);
+}
+
+// lirec_rows_copy_at: dst row *cursor + r = src row r, fp32, one element a thread (cols need not be a multiple of 4; either side may
+// carry a row stride).  One writer per element.
+__global__ __launch_bounds__(256) void rows_copy_at_kernel(const float* __restrict__ src, long ld_src, int rows, int cols,
+                                                           float* __restrict__ dst, long ld_dst, const long long* __restrict__ cursor) {
+  const long at = (long)*cursor, n = (long)rows * cols;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const long r = i / cols, c = i - r * cols;
+    dst[(at + r) * ld_dst + c] = src[r * ld_src + c];
+  }
+}
+
+// lirec_scalar_accumulate: acc[0] += v[0] in the accumulator's type -- what torch's `acc += v` computes for a one-element fp32 or
+// float64 accumulator and an fp32 addend (the addend converted to the accumulator's type, one rounding).  One thread.
+__global__ void scalar_accumulate_kernel(void* acc, int acc_f64, const float* __restrict__ v) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    if (acc_f64) *reinterpret_cast<double*>(acc) += (double)v[0];
+    else *reinterpret_cast<float*>(acc) += v[0];
+  }
 }
 
 // lirec_draw_context: one workgroup per slot.  The slot's L keys -- (Philox word << 32) | j, distinct -- go into LDS; entry j's rank

@@ -2886,7 +2886,8 @@ int lirec_eval_clip_topk(const lirec_eval_topk_args* a, lirec_stream_t stream) {
   return LIREC_OK;
 }
 
-int lirec_predict_clips(const lirec_predict_args* a, lirec_stream_t stream) {
+// the argument checks of both prediction exports; *shm_out: the header's LDS formula
+static int predict_check(const lirec_predict_args* a, uint64_t* shm_out) {
   if (!a || !a->ints || !a->trk) return LIREC_EINVAL;
   if (a->B < 0 || a->T < 1 || a->C < 1 || a->K < 1 || a->K > LIREC_PREDICT_MAX_K || a->ld_ints < a->C) return LIREC_EINVAL;
   if (a->rels && (a->NR < 1 || a->ld_rels < a->NR)) return LIREC_EINVAL;
@@ -2899,8 +2900,47 @@ int lirec_predict_clips(const lirec_predict_args* a, lirec_stream_t stream) {
   const uint64_t T = (uint64_t)a->T, C = (uint64_t)a->C, NR = a->rels ? (uint64_t)a->NR : 0, NR1 = a->rels ? NR + 1 : 0;
   const uint64_t shm = 4 * (T * C + T * NR1 + C + NR) + 8 * T + 144;
   if (shm > 160 * 1024) return LIREC_EINVAL;
+  *shm_out = shm;
+  return LIREC_OK;
+}
+
+int lirec_predict_clips(const lirec_predict_args* a, lirec_stream_t stream) {
+  uint64_t shm = 0;
+  if (predict_check(a, &shm) != LIREC_OK) return LIREC_EINVAL;
   if (a->B == 0) return LIREC_OK;
   lirec::launch(predict_clips_kernel, dim3(a->B), dim3(256), (unsigned)shm, (hipStream_t)stream, *a);
+  LIREC_CHECK_LAUNCH();
+  return LIREC_OK;
+}
+
+int lirec_predict_clips_at(const lirec_predict_args* a, const int64_t* cursor, lirec_stream_t stream) {
+  uint64_t shm = 0;
+  if (!cursor || (reinterpret_cast<uintptr_t>(cursor) & 7) != 0) return LIREC_EINVAL;
+  if (predict_check(a, &shm) != LIREC_OK) return LIREC_EINVAL;
+  if (a->B == 0) return LIREC_OK;
+  lirec::launch(predict_clips_at_kernel, dim3(a->B), dim3(256), (unsigned)shm, (hipStream_t)stream, *a, (const long long*)cursor);
+  LIREC_CHECK_LAUNCH();
+  return LIREC_OK;
+}
+
+int lirec_rows_copy_at(const float* src, int64_t ld_src, int32_t rows, int32_t cols, float* dst, int64_t ld_dst, const int64_t* cursor,
+                       lirec_stream_t stream) {
+  if (!src || !dst || !cursor || rows < 0 || cols < 1 || ld_src < cols || ld_dst < cols) return LIREC_EINVAL;
+  if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 3) != 0 || (reinterpret_cast<uintptr_t>(cursor) & 7) != 0)
+    return LIREC_EINVAL;
+  if (rows == 0) return LIREC_OK;
+  long blocks = ((long)rows * cols + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  lirec::launch(rows_copy_at_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, (long)ld_src, (int)rows, (int)cols,
+                dst, (long)ld_dst, (const long long*)cursor);
+  LIREC_CHECK_LAUNCH();
+  return LIREC_OK;
+}
+
+int lirec_scalar_accumulate(void* acc, int32_t acc_f64, const float* v, lirec_stream_t stream) {
+  if (!acc || !v || (reinterpret_cast<uintptr_t>(acc) & (acc_f64 ? 7 : 3)) != 0 || (reinterpret_cast<uintptr_t>(v) & 3) != 0)
+    return LIREC_EINVAL;
+  lirec::launch(scalar_accumulate_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, acc, (int)(acc_f64 != 0), v);
   LIREC_CHECK_LAUNCH();
   return LIREC_OK;
 }

@@ -144,6 +144,24 @@ def checked_overwrite_step(model, loss, optimizer, batch):
     return bool(ok), lv
 
 
+def _inside(blob, t) -> bool:
+    """does tensor ``t`` lie inside the device buffer ``blob``?"""
+    if not (torch.is_tensor(blob) and torch.is_tensor(t) and t.is_cuda):
+        return False
+    lo = blob.data_ptr()
+    return lo <= t.data_ptr() <= lo + blob.numel() * blob.element_size() - t.numel() * t.element_size()
+
+
+def _check_ids_in_blob(b, ids, who):
+    """a batch of a resident block store: the recorded launches read its sample ids through their ADDRESS -- a refill of the batch's
+    buffer reaches them only when the list lives inside that buffer; anywhere else every replay would read the recording batch's
+    ids again"""
+    if not _inside(b.get('_dev_blob'), ids):
+        raise LirecError('%s: the block-store batch\'s clip_ids do not lie inside the batch\'s own buffer '
+                         '(_dev_blob): a replay would keep reading the ids of the recording batch -- take the batch '
+                         'from BlockLoader, or run the eager step' % who)
+
+
 class RecordedTrainStep:
     """The train step as a command list recorded by the library while one ordinary eager step runs, then re-issued from
     C: the eager loop's launches on the eager loop's streams (so its kernel timeline: the weight-gradient side stream
@@ -188,15 +206,7 @@ class RecordedTrainStep:
                 raise LirecError('RecordedTrainStep(next_batch=...): the input-pipeline form is not built over block-store batches -- '
                                  'record the plain form')
             if ids is not None:
-                # (a batch of a resident block store: the recorded launches read its sample ids through their ADDRESS -- a refill of the
-                #  batch's buffer reaches them only when the list lives inside that buffer; anywhere else every replay would read
-                #  the recording batch's ids again)
-                blob = b.get('_dev_blob')
-                lo = blob.data_ptr() if torch.is_tensor(blob) else None
-                if lo is None or not lo <= ids.data_ptr() <= lo + blob.numel() * blob.element_size() - ids.numel() * 4:
-                    raise LirecError('RecordedTrainStep: the block-store batch\'s clip_ids do not lie inside the batch\'s own buffer '
-                                     '(_dev_blob): a replay would keep reading the ids of the recording batch -- take the batch '
-                                     'from BlockLoader, or run the eager step')
+                _check_ids_in_blob(b, ids, 'RecordedTrainStep')
         if draw is not None and (next_batch is not None or getattr(model, 'grad_sync', None) is not None):
             raise ValueError('RecordedTrainStep(draw=...): the plain single-GPU form')
         self.model, self.loss, self.optim, self.batch, self.draw = model, loss, optimizer, batch, draw
@@ -565,3 +575,149 @@ class RecordedTrainStep:
             raise RuntimeError('RecordedTrainStep.resume(): the q32b shadow of the first-layer weights cannot be rebuilt')
         self.lanes.defer_join = self.defer
         self.lanes.params_written()             # (eager steps in between: whoever wrote the parameters last, order the side stream)
+
+
+class RecordedEvalStep:
+    """One FORWARD-ONLY iteration over a resident block store as a command list: the in-list draw (``draw``: ``BlockLoader.collate_at``
+    -- the batch at the loader's device cursor, written into ``batch``'s own buffer, and the cursor's move), ``model(batch)`` under
+    ``model.eval()`` and ``torch.no_grad()``, then ``tail(out, batch)`` -- whatever the caller does with the logits in LIBRARY launches
+    (``testing()``: the loss, its accumulation and the device-side counters; ``predict()``: ``predict_clips_at``; both: the rows kept for
+    after the loop and the move of the output cursor).  Recorded while it runs on a real batch, which counts; ``step()`` re-issues
+    the list: one C loop in the place of ~20 launches driven from Python.
+
+    Nothing a step reads is passed by value per call: the batch through the loader's cursor, the output rows through the caller's
+    cursor word, the parameters through their addresses -- an evaluation forward reads neither the q32b shadow of the first-layer
+    weights nor staged gate weights (both belong to training forwards), so the list computes what an eager forward at that moment
+    would.  The object still lives for ONE call of ``testing()`` / ``predict()``: parameters, flags and scratch may change between
+    two evaluations, and nothing here watches them.
+
+    ``tail`` must not depend on a torch launch made from the batch (a dtype conversion, a host-side label copy): the list would not
+    contain it and every replay would read the recording batch's values.  ``loss`` (optional) is asked as ``RecordedTrainStep`` asks
+    it (``needs_before_replay``); the tail checks its own inputs (``in_batch``).  ``state``: device tensors the tail accumulates
+    into -- a recording that raises puts back what they held, so the caller can run the batch eagerly."""
+
+    def __init__(self, model, batch, draw, tail, loss=None, state=()):
+        if model.training:
+            raise ValueError('RecordedEvalStep records a forward-only step: call model.eval() first')
+        f = batch.get('features') if isinstance(batch, dict) else None
+        ids = getattr(f, 'clip_ids', None)
+        if ids is None:
+            raise LirecError('RecordedEvalStep: a batch of a resident block store (BlockLoader) is needed -- the list draws its own batches')
+        _check_ids_in_blob(batch, ids, 'RecordedEvalStep')
+        self.model, self.loss, self.batch = model, loss, batch
+        self._check_draw()
+        self.stream = torch.cuda.current_stream()
+        self.cmds, self.out = None, None
+        saved = [t.clone() for t in state]
+        try:
+            with torch.no_grad(), ops.keep_allocations() as kept:
+                ops.CommandList.begin()
+                try:
+                    draw()
+                    before = ops.CommandList.mark()
+                    if before < 1:
+                        raise RuntimeError('RecordedEvalStep: the draw issued no library launch')
+                    out = model(dict(batch))              # the model re-binds x['features'] (mlp/model.py:272)
+                    if ops.CommandList.mark() <= before:
+                        raise RuntimeError('RecordedEvalStep: the forward issued no library launch on the recording thread')
+                    self.out = tail(out, batch)
+                finally:
+                    self.cmds = ops.CommandList.end()
+        except BaseException:
+            # (a failed recording leaves the eager loop's state behind: the accumulators as they were, no list)
+            for t, s in zip(state, saved):
+                t.copy_(s)
+            self.release()
+            raise
+        self._kept = kept
+        self._gemm_mode = ops.get_gemm_mode()
+
+    in_batch = staticmethod(_inside)
+
+    def _check_draw(self):
+        if self.loss is not None and hasattr(self.loss, 'needs_before_replay') and self.loss.needs_before_replay():
+            raise LirecError('RecordedEvalStep: %s reads the batch on the host\'s side in front of every replay (before_replay), i.e. '
+                             'before the list has drawn it -- run the eager loop' % type(self.loss).__name__)
+
+    def step(self):
+        """Re-issue the recorded iteration on the batch the loader's cursor names now (no synchronisation)."""
+        if self.cmds is None:
+            raise RuntimeError('RecordedEvalStep: released')
+        self._check_draw()
+        if self.model.training:
+            raise RuntimeError('RecordedEvalStep: the model is in train mode -- the list holds an evaluation forward')
+        if ops.get_gemm_mode() != self._gemm_mode or not getattr(opt, 'layer1_planes', False):
+            raise RuntimeError('RecordedEvalStep: recorded under GEMM mode %d with opt.layer1_planes, the library is in mode %d now (flag %s) '
+                               '-- the recorded launches are that core\'s kernels' % (self._gemm_mode, ops.get_gemm_mode(), getattr(opt, 'layer1_planes', False)))
+        self.cmds.replay(0, -1)
+        return self.out
+
+    def release(self):
+        """the list and everything it kept alive go (the stream has been told to run them first)"""
+        if self.cmds is not None:
+            self.cmds.destroy()
+        self.cmds, self._kept = None, None
+
+
+class EvalStepper:
+    """The life of a ``RecordedEvalStep`` inside ONE call of ``testing()`` / ``predict()`` (``opt.record_eval``): the first batch of a
+    layout runs eagerly (lazy allocations happen), the next one of that layout is recorded -- a real batch, run once --, every further
+    one is a replay; a batch of another layout (the short last one, a singleton) runs eagerly in between, drawn by the loader's own
+    call, the loader's cursor account kept right by the loader.  A recording that raises bars further attempts: the loop finishes
+    eagerly.  ``replayed`` counts the replays."""
+
+    def __init__(self, model, loader, loss=None, say=print):
+        self.model, self.loader, self.loss, self.say = model, loader, loss, say
+        self.step = self.layout = None
+        self.seen, self.barred, self.replayed = set(), False, 0
+        loader.stable_ids = True          # (asked for before the epoch is drawn: a list reads the epoch's ids at ONE address)
+
+    @staticmethod
+    def wanted(loader, world=1) -> bool:
+        """``opt.record_eval`` over a BlockLoader in one process -- anything else is today's loop, with no complaint"""
+        from .loader import BlockLoader
+        return bool(getattr(opt, 'record_eval', False)) and isinstance(loader, BlockLoader) and world == 1
+
+    def take(self, batch, tail, state=()):
+        """(handled, batch): handled -- the batch was evaluated by the recording or by a replay and the caller does its host accounting
+        only; else the caller runs ``batch`` (materialised, had it been left to a list that will not run) eagerly."""
+        lay = tuple(batch.get('_layout', ())) if isinstance(batch, dict) else ()
+        if self.step is not None and lay == self.layout and self.loader.last_in_list:
+            try:
+                self.step.step()
+                self.replayed += 1
+                return True, batch
+            except Exception as e:
+                self._give_up('replay', e)
+        if self.loader.last_in_list:
+            return False, self.loader.materialise(batch)
+        if self.step is None and not self.barred and lay and lay in self.seen and self.loader.can_draw_last_in_list():
+            loader, blob = self.loader, batch['_dev_blob']
+            try:
+                loader.cursor_to_last()
+                self.step = RecordedEvalStep(self.model, batch, lambda: loader.collate_at(lay, blob), tail, loss=self.loss, state=state)
+                self.layout = lay
+                loader.bind(lay, blob, in_list=True)
+                return True, batch
+            except Exception as e:
+                self._give_up('recording', e)
+        if lay:
+            self.seen.add(lay)
+        return False, batch
+
+    def _give_up(self, what, e):
+        self.say('recorded evaluation step not used (%s): %s' % (what, str(e)[:160]))
+        self.barred = True
+        self.loader.unbind()
+        self.loader.cursor_lost()
+        if self.step is not None:
+            self.step.release()
+            self.step = None
+
+    def close(self):
+        """at the end of the call: the loader draws by its own calls again, the list goes"""
+        self.loader.unbind()
+        if self.step is not None:
+            torch.cuda.current_stream().synchronize()      # (the buffers the list kept alive are still being read)
+            self.step.release()
+            self.step = None

@@ -366,6 +366,11 @@ class BlockLoader:
         """the device cursor names the batch handed out last: what a list that is about to be recorded on that batch draws again"""
         self._cursor.expect(self._last[0])
 
+    def cursor_lost(self):
+        """a recording that drew in-list did not finish: the word may or may not have moved -- it is written again before the next
+        in-list batch"""
+        self._cursor.invalidate()
+
     def _in_list(self, at, B):
         """the bound buffer's batch, drawn by the list that owns the buffer when it runs: no launch here"""
         self._cursor.expect(at)

@@ -1299,6 +1299,67 @@ def predict_clips(ints, rels=None, mem=None, B=None, T=1, K=5, loader_types=Fals
     return out
 
 
+def _cursor_word(cursor):
+    assert cursor.dtype == torch.int64 and cursor.is_cuda and cursor.numel() >= 1, 'cursor: an int64 device word'
+    return _p(cursor)
+
+
+def predict_clips_at(ints, rels, mem, cursor, out, B=None, T=1, K=5, loader_types=False):
+    """``predict_clips`` into rows ``[cursor[0], cursor[0] + B)`` of DATASET-SIZED arrays (lirec_predict_clips_at): ``out`` -- a dict
+    of ``predict_buffers`` arrays, all of one row count n -- is written at the row an int64 device word names when the kernel runs,
+    so the launch, replayed from a command list, writes the next batch's rows once ``counter_add(cursor, [B])`` has moved the
+    word.  The cursor is not moved here; trusted: 0 <= cursor[0] <= n - B.  Inputs as ``predict_clips``.  Returns ``out``."""
+    assert ints.dim() == 2, tuple(ints.shape)
+    rows, Cc = ints.shape
+    B = rows // T if B is None else B
+    assert B >= 1 and B * T == rows and 1 <= K <= _lib.PREDICT_MAX_K, (B, T, rows, K)
+    assert rels is None or (rels.dim() == 2 and rels.shape[0] == rows), 'rels'
+    assert mem is None or (mem.dtype == (torch.float64 if loader_types else torch.float32) and mem.numel() == rows
+                           and mem.is_contiguous()), 'mem'
+    NR = rels.shape[1] if rels is not None else 0
+    assert 'trk' in out, 'predict_clips_at: the output dict must hold trk'
+    n = out['trk'].shape[0]
+    assert n >= B, (n, B)
+    tails = {'trk': (), 'cls': (), 'rel': (), 'score': (), 'trk_score': (T,), 'top_cls': (K,), 'top_cls_p': (K,), 'top_rel': (K,),
+             'top_rel_p': (K,), 'flags': ()}
+    dtypes = {'score': torch.float64, 'trk_score': torch.float64, 'top_cls_p': torch.float32, 'top_rel_p': torch.float32}
+    a = PredictArgs()
+    for k, t in out.items():
+        assert tuple(t.shape) == (n,) + tails[k] and t.dtype == dtypes.get(k, torch.int32) and t.is_contiguous(), (k, tuple(t.shape), t.dtype)
+        if k in ('top_rel', 'top_rel_p') and rels is None:
+            continue
+        setattr(a, k, _p(t))
+    # (a dimension of one element may carry any stride: the row stride only matters from the second row on)
+    a.ints, a.ld_ints = _p(_f32c(ints)), (ints.stride(0) if rows > 1 else Cc)
+    if rels is not None:
+        a.rels, a.ld_rels = _p(_f32c(rels)), (rels.stride(0) if rows > 1 else NR)
+    a.mem = _p(mem)
+    a.B, a.T, a.C, a.NR, a.K = B, T, Cc, NR, K
+    a.loader_types = int(bool(loader_types))
+    check(lib().lirec_predict_clips_at(C.byref(a), _cursor_word(cursor), _stream()), 'lirec_predict_clips_at')
+    return out
+
+
+def rows_copy_at(src, dst, cursor):
+    """``dst[cursor[0]:cursor[0] + rows] = src`` for fp32 matrices, the row read from an int64 device word when the kernel runs
+    (lirec_rows_copy_at): ``src`` [rows, cols], possibly a strided view of unit column stride, ``dst`` [n, cols] with n >= rows.  The
+    cursor is not moved; trusted: 0 <= cursor[0] <= n - rows."""
+    assert src.dim() == 2 and dst.dim() == 2 and src.shape[1] == dst.shape[1] >= 1 and dst.shape[0] >= src.shape[0], (tuple(src.shape), tuple(dst.shape))
+    rows, cols = src.shape
+    if rows == 0:
+        return
+    _f32c(src), _f32c(dst)
+    check(lib().lirec_rows_copy_at(_p(src), src.stride(0) if rows > 1 else cols, rows, cols, _p(dst),
+                                   dst.stride(0) if dst.shape[0] > 1 else cols, _cursor_word(cursor), _stream()), 'lirec_rows_copy_at')
+
+
+def scalar_accumulate(acc, v):
+    """``acc[0] += v[0]`` on the device (lirec_scalar_accumulate): ``acc`` a one-element fp32 or float64 device tensor, ``v`` fp32 --
+    bit for bit torch's ``acc += v``, as a launch a command list can carry."""
+    assert acc.numel() >= 1 and acc.dtype in (torch.float32, torch.float64) and v.numel() >= 1 and v.dtype == torch.float32, (acc.dtype, v.dtype)
+    check(lib().lirec_scalar_accumulate(_p(acc), int(acc.dtype == torch.float64), _p(v), _stream()), 'lirec_scalar_accumulate')
+
+
 def collate_fields(ids, fields):
     """dst row b = src row ids[b] for every (src [N, ...], dst [B, ...]) pair of contiguous device tensors, byte for byte, in one
     launch on the current stream (lirec_collate_fields).  ``ids``: int32 [B], trusted (the caller validated them)."""

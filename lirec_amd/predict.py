@@ -23,8 +23,10 @@ import torch
 from scipy.special import expit
 
 from . import ops
+from ._lib import LirecError
 from .config import opt
-from .loader import make_loader
+from .graph import EvalStepper, RecordedEvalStep
+from .loader import _Cursor, make_loader
 
 
 class Predictions:
@@ -65,9 +67,62 @@ def predict(dataset, model, top_k=5, batch_size=None):
     want_pairs = bool(opt.rels_multitask and opt.ctx == 1 and not opt.tr_maximize)
     bufs = dev_rels = None
     at, hashes, have_hash = 0, [], False
+    # opt.record_eval over a resident block store, one process: the iteration is recorded on the second full batch and replayed for
+    # the rest (lirec_amd.graph.EvalStepper) -- the outputs written at a device cursor.  None: the loop below, exactly.
+    stepper = rec = None
+    from . import parallel
+    if EvalStepper.wanted(loader, parallel.world_info()[1]) and to_dev is None and str(opt.device).startswith('cuda'):
+        stepper = EvalStepper(model, loader)
+        rec = {'cursor': _Cursor(torch.device(opt.device)), 'hashes': None}
+
+    def recorded_tail(out, batch):
+        """the device part of one iteration below with the output rows named by the cursor word (lirec_predict_clips_at,
+        lirec_rows_copy_at) and the word's move; ``mem_mask`` must be read in place from the batch's buffer (a converted copy would be
+        the recording batch's for every replay): raised before anything is written, and the loop stays eager"""
+        ints = out['inters']
+        C = ints.shape[-1]
+        rels = out.get('rels') if opt.ctx == 1 else None
+        if opt.tr_maximize:
+            bs = ints.shape[0]
+            T = ints.numel() // (bs * C)
+            mem = batch['mem_mask'].to(ints.device, non_blocking=True).double().contiguous()
+            if not RecordedEvalStep.in_batch(batch['_dev_blob'], mem):
+                raise LirecError('predict(record_eval): mem_mask is not read in place from the batch buffer')
+            ints2, rels2 = ints.reshape(bs * T, C), (rels.reshape(bs * T, -1) if rels is not None else None)
+        else:
+            bs, T, mem = batch['features'].shape[0], 1, None
+            ints2, rels2 = ints.reshape(bs, -1, C)[:, 0], (rels.reshape(bs, -1) if rels is not None else None)
+        h = batch.get('hash_rel') if want_pairs else None
+        if h is not None and not (h.dtype == torch.int64 and RecordedEvalStep.in_batch(batch['_dev_blob'], h)):
+            raise LirecError('predict(record_eval): hash_rel is not an int64 field of the batch buffer')
+        word = rec['cursor'].word
+        ops.predict_clips_at(ints2, rels2, mem, word, bufs, B=bs, T=T, K=top_k, loader_types=True)
+        if want_pairs:
+            ops.rows_copy_at(rels2, dev_rels, word)
+            if h is not None:
+                if rec['hashes'] is None:
+                    rec['hashes'] = torch.empty(dev_rels.shape[0], 2, dtype=torch.float32, device=dev_rels.device)
+                ops.rows_copy_at(h.reshape(bs, 1).view(torch.float32), rec['hashes'], word)    # (8-byte values moved as fp32 pairs)
+        ops.counter_add(word, [bs])
+
     try:
         with torch.no_grad():
             for batch in loader:
+                if stepper is not None:
+                    rec['cursor'].expect(at)
+                    done, batch = stepper.take(batch, recorded_tail)
+                    if done:
+                        # (the host's account of a batch the list wrote: what the loop below keeps)
+                        bs = batch['features'].shape[0]
+                        assert at + bs <= bufs['trk'].shape[0], 'a block store yields its own length'
+                        if want_pairs:
+                            have_hash = have_hash or 'hash_rel' in batch
+                            hashes.append(rec['hashes'][at:at + bs].view(torch.int64) if 'hash_rel' in batch
+                                          else torch.full((bs,), -1, dtype=torch.int64))
+                        at += bs
+                        rec['cursor'].advanced(bs)
+                        continue
+                    rec['cursor'].invalidate()    # (an eager batch moves `at` and not the word; a failed recording may have moved the word)
                 if to_dev is not None:
                     batch = to_dev(batch)
                 out = model(batch)
@@ -103,16 +158,20 @@ def predict(dataset, model, top_k=5, batch_size=None):
                     hashes.append(batch['hash_rel'] if 'hash_rel' in batch else torch.full((bs,), -1, dtype=torch.int64))
                 at += bs
     finally:
+        recorded_steps = 0
+        if stepper is not None:
+            recorded_steps = stepper.replayed
+            stepper.close()                               # (the list lives for this call: parameters change between calls)
         model.train(was_training)
     if bufs is None:
-        predict.last = {}
+        predict.last = {'recorded_steps': 0}
         return Predictions({}, 0)
     last = {k: v[:at] for k, v in bufs.items()}
     arrays = {k: v.cpu().numpy() for k, v in last.items()}            # one device-to-host copy per field
     pairs = None
     if have_hash:
         pairs = pair_scores(dev_rels[:at].cpu().numpy(), torch.cat([h.reshape(-1).cpu() for h in hashes]).numpy())
-    predict.last = dict(last, n_clips=at)
+    predict.last = dict(last, n_clips=at, recorded_steps=recorded_steps)
     return Predictions(arrays, at, pairs)
 
 

@@ -11,6 +11,8 @@ host: their logits wait in a device buffer and come back in ONE copy after the l
 the host path's order bit for bit.  ``device_metrics=False`` and ``ints != 1`` keep the host
 counters on logits copied back once per batch.  Differences, on purpose: no interaction-name file is
 read (:29-32 only builds an unused table), and clips/s is printed next to the metrics.
+``opt.record_eval`` (off by default) over a resident block store: the forward-only iteration is recorded on the second full batch
+and replayed for the rest (``lirec_amd.graph.EvalStepper``) -- the same bits.
 """
 from __future__ import annotations
 
@@ -20,8 +22,10 @@ import numpy as np
 import torch
 
 from . import ops
+from ._lib import LirecError
 from .config import opt
-from .loader import make_loader
+from .graph import EvalStepper, RecordedEvalStep
+from .loader import _Cursor, make_loader
 from .metrics import Precision, RelationshipsAcc
 from .util import Averaging
 
@@ -50,9 +54,91 @@ def testing(test_dataset, model, loss, total_iter=1, mode='val', train_start_tim
     dev_counters = dev_loss = dev_conf = dev_rels = dev_tracks = None
     n_batches = n_out = rels_at = 0
     rels_parts = []                                   # (offset, rows, labelled rows, their labels, their pair hashes) per batch
+    to_dev = getattr(test_dataset, 'to_device', None) if (on_device and str(opt.device).startswith('cuda')) else None
+    # opt.record_eval over a resident block store, one process, device-side counters: the iteration is recorded on the second full
+    # batch and replayed for the rest (lirec_amd.graph.EvalStepper).  None: the loop below, exactly.
+    stepper = rec = None
+    if EvalStepper.wanted(loader, world) and (on_device or on_device_topk) and to_dev is None and str(opt.device).startswith('cuda'):
+        stepper = EvalStepper(model, loader, loss=loss, say=print if verbose else (lambda *a, **k: None))
+        rec = {'cursor': _Cursor(torch.device(opt.device)), 'labels': None, 'hashes': None}
+
+    def keep_rows(t, buf):
+        """rows of an int64 batch field into a dataset-sized buffer at the output cursor -- 8-byte values moved as fp32 pairs"""
+        rows = t.reshape(t.shape[0], -1).view(torch.float32)
+        if buf is None:
+            buf = torch.empty(dev_rels.shape[0], rows.shape[1], dtype=torch.float32, device=rows.device)
+        ops.rows_copy_at(rows, buf, rec['cursor'].word)
+        return buf
+
+    def kept_rows(buf, like, at, bs):
+        return buf[at:at + bs].view(torch.int64).reshape((bs,) + tuple(like.shape[1:]))
+
+    def recorded_tail(out, batch):
+        """the device part of one iteration below in LIBRARY launches only -- what a command list carries: ``dev_loss += lv`` by
+        lirec_scalar_accumulate, ``dev_rels[at:at + bs].copy_(rl)`` by lirec_rows_copy_at at the output cursor (with the batch's labels
+        and pair hashes, which the eager loop keeps as views of a buffer per batch: a replayed step has ONE buffer).  Every batch field
+        the kernels read must be read IN PLACE from the batch's buffer -- a converted copy would be the recording batch's for every
+        replay: raised before anything is accumulated, and the loop stays eager."""
+        blob, labels, ints = batch['_dev_blob'], batch['labels'], out['inters']
+        bs = labels.shape[0]
+
+        def in_place(t, what):
+            t = t.to(ints.device).contiguous()
+            if not RecordedEvalStep.in_batch(blob, t):
+                raise LirecError('testing(record_eval): %s is not read in place from the batch buffer' % what)
+            return t
+        lv = loss(out, batch)
+        y = in_place(labels.long().reshape(-1), 'labels')
+        if on_device:
+            Tn = ints.numel() // (bs * ints.shape[-1])
+            rels = out['rels'] if opt.ctx == 1 else None
+            args = (in_place(batch['mem_mask'].double(), 'mem_mask'), y,
+                    in_place(batch['rels_label'].long(), 'rels_label') if rels is not None else None,
+                    in_place(batch['gt_tracks'].long(), 'gt_tracks'), in_place(batch['just_zeros'].to(torch.bool), 'just_zeros'))
+            ops.scalar_accumulate(dev_loss, lv.detach().reshape(-1)[:1])
+            ops.eval_max_tracks(ints.reshape(bs * Tn, -1), rels.reshape(bs * Tn, -1) if rels is not None else None, *args, dev_counters,
+                                bs, Tn, ints.shape[-1], rels.shape[-1] if rels is not None else 0, loader_types=True)
+            return
+        if opt.soft_gt:
+            soft = in_place(batch['soft_labels'].double(), 'soft_labels').reshape(bs, -1)
+            ops.scalar_accumulate(dev_loss, lv.detach().reshape(-1)[:1])
+            ops.eval_clip_topk(ints, y, dev_counters, conf=dev_conf, soft=soft, loader_types=True)
+        elif opt.rels_multitask:
+            if opt.ctx == 1:
+                in_place(batch['rels_label'], 'rels_label'), in_place(batch['hash_rel'], 'hash_rel')
+                if batch['rels_label'].dtype != torch.int64 or batch['hash_rel'].dtype != torch.int64:
+                    raise LirecError('testing(record_eval): rels_label / hash_rel are kept as int64 rows')
+            ops.scalar_accumulate(dev_loss, lv.detach().reshape(-1)[:1])
+            ops.eval_clip_topk(ints.reshape(bs, -1, ints.shape[-1])[:, 0], y, dev_counters, conf=dev_conf,
+                               y_stride=labels.numel() // bs, loader_types=True)
+            if opt.ctx == 1:
+                ops.rows_copy_at(out['rels'].detach().reshape(bs, -1), dev_rels, rec['cursor'].word)
+                rec['labels'] = keep_rows(batch['rels_label'], rec['labels'])
+                rec['hashes'] = keep_rows(batch['hash_rel'], rec['hashes'])
+                ops.counter_add(rec['cursor'].word, [bs])
+        else:
+            if opt.tracks:
+                raise LirecError('testing(record_eval): the track count of this recipe is a torch reduction per batch')
+            ops.scalar_accumulate(dev_loss, lv.detach().reshape(-1)[:1])
+            ops.eval_clip_topk(ints, y, dev_counters, conf=dev_conf, loader_types=True)
+
     with torch.no_grad():
-        to_dev = getattr(test_dataset, 'to_device', None) if (on_device and str(opt.device).startswith('cuda')) else None
         for idx, batch in enumerate(loader):
+            if stepper is not None and len(batch['labels']) != 1:
+                rec['cursor'].expect(rels_at)
+                done, batch = stepper.take(batch, recorded_tail, state=[t for t in (dev_counters, dev_loss, dev_conf) if t is not None])
+                if done:
+                    # (the host's account of a batch the list evaluated: what the two device branches below keep)
+                    bs = len(batch['labels'])
+                    n_clips, n_batches = n_clips + bs, n_batches + 1
+                    if on_device_topk and opt.rels_multitask and not opt.soft_gt and opt.ctx == 1:
+                        assert rels_at + bs <= dev_rels.shape[0], 'a block store yields its own length'
+                        rels_parts.append((rels_at, bs, None, kept_rows(rec['labels'], batch['rels_label'], rels_at, bs),
+                                           kept_rows(rec['hashes'], batch['hash_rel'], rels_at, bs)))
+                        rels_at += bs
+                        rec['cursor'].advanced(bs)
+                    continue
+                rec['cursor'].invalidate()        # (an eager batch moves rels_at and not the word; a failed recording may have moved the word)
             if to_dev is not None:
                 batch = to_dev(batch)             # (one host-to-device copy for the batch's small tensors; device counters only)
             labels = batch['labels']
@@ -155,6 +241,10 @@ def testing(test_dataset, model, loss, total_iter=1, mode='val', train_start_tim
                 if opt.tracks:
                     total_tracks += int(np.sum(batch['just_zeros'].cpu().numpy()))
                 conf_mat = prec.update_probs(inters, labels, conf_mat=conf_mat)
+    recorded_steps = 0
+    if stepper is not None:
+        recorded_steps = stepper.replayed
+        stepper.close()                                           # (the list lives for this call: parameters change between evaluations)
     if on_device and dev_counters is not None:
         prec.add_device_counters(dev_counters)                    # the only device-to-host copies of the evaluation
         losses.update(float(dev_loss) / max(n_batches, 1), max(n_batches, 1))
@@ -224,7 +314,7 @@ def testing(test_dataset, model, loss, total_iter=1, mode='val', train_start_tim
 
     out = {'total': out_val, 'ints': out_ints}
     testing.last = {'precision': prec, 'relationships': prec_rels, 'conf_mat': conf_mat, 'loss': losses.avg, 'n_clips': n_clips,
-                    'metrics_on_device': bool(on_device or on_device_topk)}
+                    'metrics_on_device': bool(on_device or on_device_topk), 'recorded_steps': recorded_steps}
     if opt.rels_multitask:
         out['rels'] = out_rels
     if opt.tr_maximize:
