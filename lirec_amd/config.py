@@ -40,6 +40,12 @@ def defaults() -> dict:
         save_model=True, save_model_often=False, test=True, test_fr=2,
         resume=False, resume_train=False, resume_str='', model_name='',
         store_root='./store', sanity_check=False, log_prefix='',
+        # resume_train with resume_str set: training() continues the run of that checkpoint -- training(resume=opt.resume_str) --
+        # which must have been written with save_train_state (lirec_amd.train.TrainState; DESIGN "Continuing a run").
+        # save_train_state: every checkpoint training() writes carries ck['train_state'], and the kept best checkpoints are
+        # written whenever the kept set changes.  checkpoint_every = N > 0: the rolling <store_root>/last.pth.tar, with the train
+        # state, after every N taken steps and at every epoch's end (single process; moved into place by os.replace).
+        save_train_state=False, checkpoint_every=0,
         # loop control of testing() / predict(), not in the reference (no step's numbers depend on it; tests/test_gpu_recorded_eval.py):
         # over a resident block store, single GPU, device-side counters, the forward-only iteration (draw, forward, loss, counters /
         # predictions) is recorded on the second full batch and replayed for every further one (lirec_amd.graph.RecordedEvalStep);

@@ -31,11 +31,21 @@ class ThreadedLoader:
         return self.collate_fn([self.dataset[i] for i in idx])
 
     def __iter__(self):
+        return self._batches(None)
+
+    def iter_from(self, start):
+        """an epoch's batches from the ``start``-th on (a resumed run, lirec_amd.train): the batch sampler is drawn HERE, whole --
+        the permutation comes from the caller's RNG state as it is at this call -- and no sample of the batches passed over is
+        fetched"""
+        return self._batches(list(self.batch_sampler)[int(start):])
+
+    def _batches(self, todo):
         if self.num_workers == 0:
-            for idx in self.batch_sampler:
+            for idx in (self.batch_sampler if todo is None else todo):
                 yield self._make(idx)
             return
-        todo = list(self.batch_sampler)                     # (the sampler is drawn on the caller's thread: its RNG state is the caller's)
+        if todo is None:
+            todo = list(self.batch_sampler)                 # (the sampler is drawn on the caller's thread: its RNG state is the caller's)
         n, depth = len(todo), self.num_workers * self.prefetch
         slots = [queue.Queue(maxsize=1) for _ in range(n)]  # one slot per batch: ordered hand-over
         nxt, lock, stop = [0], threading.Lock(), threading.Event()
@@ -195,15 +205,24 @@ class ResidentLoader:
         return out
 
     def __iter__(self):
+        return self._batches(None, 0)
+
+    def iter_from(self, start):
+        """an epoch's batches from the ``start``-th on (a resumed run, lirec_amd.train): the batch sampler is drawn HERE, whole, and
+        no batch passed over is collated"""
+        return self._batches(self.epoch_ids(), int(start))
+
+    def _batches(self, todo, start):
         import numpy as np
-        todo = self.epoch_ids()
+        if todo is None:
+            todo = self.epoch_ids()
         flat = np.fromiter((i for idx in todo for i in idx), dtype=np.int64)
         if flat.size and (int(flat.min()) < 0 or int(flat.max()) >= len(self.dataset)):
             raise IndexError('ResidentLoader: the sampler drew a sample id outside [0, %d)' % len(self.dataset))
         ids = torch.from_numpy(flat.astype(np.int32)).to(self.device)         # the epoch's order: one host-to-device copy
         self.draw_context()
-        at = 0
-        for idx in todo:
+        at = sum(len(idx) for idx in todo[:start])
+        for idx in todo[start:]:
             B = len(idx)
             yield self.collate_ids(ids[at:at + B], B)
             at += B
@@ -411,15 +430,25 @@ class BlockLoader:
         return self.ids_base[:n]
 
     def __iter__(self):
+        return self._batches(None, 0)
+
+    def iter_from(self, start):
+        """an epoch's batches from the ``start``-th on (a resumed run, lirec_amd.train): the batch sampler is drawn HERE, whole; the
+        epoch's ids go up as ever and the first batch handed out sits at its own offset in them -- where an in-list draw's cursor is
+        then expected (``_Cursor.expect``) --; no batch passed over is collated"""
+        return self._batches(self.epoch_ids(), int(start))
+
+    def _batches(self, todo, start):
         import numpy as np
-        todo = self.epoch_ids()
+        if todo is None:
+            todo = self.epoch_ids()
         flat = np.fromiter((i for idx in todo for i in idx), dtype=np.int64)
         if flat.size and (int(flat.min()) < 0 or int(flat.max()) >= self.store.n):
             raise IndexError('BlockLoader: the sampler drew a sample id outside [0, %d)' % self.store.n)
         # the epoch's order: one host-to-device copy
         ids = self._upload(flat) if self.stable_ids else torch.from_numpy(flat.astype(np.int32)).to(self.device)
-        at = 0
-        for idx in todo:
+        at = sum(len(idx) for idx in todo[:start])
+        for idx in todo[start:]:
             B = len(idx)
             b = self._bound
             in_list = self.stable_ids and b is not None and b[2] and B > 0 and b[0] == tuple(self.layout(B)[0])

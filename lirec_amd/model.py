@@ -439,6 +439,19 @@ class _HotPathModule(nn.Module):
         p = float(opt.dropout) if self.training else 0.0
         return ops.make_dropout(self._cur_seed, p, site, site2, self._seed_dev)
 
+    @property
+    def dropout_calls(self) -> int:
+        """train-mode forwards so far: the dropout key of the next one is ``opt.dropout_seed`` + this.  With a recorded step
+        attached the count lives on the device and this is its host mirror (RecordedTrainStep._advance_host).  Settable (a resumed
+        run, lirec_amd.train.TrainState) while no recorded step holds the count."""
+        return self._fwd_train_calls
+
+    @dropout_calls.setter
+    def dropout_calls(self, n):
+        if self._seed_dev is not None:
+            raise RuntimeError('Model.dropout_calls: a recorded step holds the count on the device; release() it first')
+        self._fwd_train_calls = int(n)
+
     def _begin_forward(self):
         ops.ensure_scratch(self._device())
         if self.training and self._seed_dev is not None:
@@ -1373,6 +1386,18 @@ class _MarginBase(_DPMeans, nn.Module):
     _sample_calls = 0
     _seed_dev = None              # device int64[1] added to the sampling key (lirec_amd.graph)
     last_probs = None
+
+    @property
+    def sample_calls(self) -> int:
+        """track draws so far (``tr_cat_distr``): the key of the next one is ``opt.dropout_seed`` + this; the host mirror while a
+        recorded step holds the count on the device.  Settable as ``Model.dropout_calls`` is."""
+        return self._sample_calls
+
+    @sample_calls.setter
+    def sample_calls(self, n):
+        if self._seed_dev is not None:
+            raise RuntimeError('loss.sample_calls: a recorded step holds the count on the device; release() it first')
+        self._sample_calls = int(n)
 
     def _sample_key(self):
         if self._seed_dev is not None:

@@ -84,7 +84,7 @@ no pass over the gradients).  ``p.grad`` holds the UNSCALED SUM of the window so
 unclipped).  Clip, guard, AdamW, groups, frozen parameters and the average act at the apply step on the accumulated gradient: the
 norm is that of sum / k x grad_scale, a NaN anywhere in the window skips the window's update and counts ONE skipped step, the
 average takes one lerp per applied window; ``state_dict()`` counts updates.  A checkpoint taken inside a window does not hold the
-window's gradients.  In the eager loop the host takes the hold / apply decision; a recorded step re-issues the same launches every
+window's gradients in ``state_dict()``; ``window_state()`` / ``load_window_state()`` carry them (lirec_amd.train.TrainState).  In the eager loop the host takes the hold / apply decision; a recorded step re-issues the same launches every
 micro-step, so there it lives in device memory (``_win_dev``, the window block of lirec_accum_begin; the update's launches under
 ``ops.adam_hold``) -- ``begin_micro_step`` is that step's head.
 
@@ -256,6 +256,37 @@ class FusedAdam(torch.optim.Optimizer):
         if self._win_dev is not None:
             raise RuntimeError('FusedAdam.drop_window(): a recorded step holds the window on the device; release() it first')
         self._accum_phase = 0
+        self._hold_sync()
+
+    def window_state(self):
+        """the open accumulation window as a checkpoint keeps it (lirec_amd.train.TrainState; ``state_dict()`` does not hold it):
+        {'phase', 'k', 'grads'} -- ``grads`` a host copy of the flat gradient buffer, the unscaled sum of the window's micro-batches
+        so far, when the phase is not 0, else None.  The phase is the host's (a recorded step keeps its mirror current); the copy
+        waits for the side stream and the device."""
+        grads = None
+        if self._accum_phase != 0:
+            self._join_side()
+            grads = self.model.flat_grads(attach=True).detach().cpu().clone()
+        return {'phase': int(self._accum_phase), 'k': int(self._accum_k), 'grads': grads}
+
+    @torch.no_grad()
+    def load_window_state(self, ws):
+        """continue the window of ``window_state()``: the gradients back into the flat buffer, the phase set -- the next
+        ``zero_grad()`` then leaves them alone and the next ``step()`` counts on from there.  Not under a recorded step."""
+        if self._win_dev is not None:
+            raise RuntimeError('FusedAdam.load_window_state(): a recorded step holds the window on the device; release() it first')
+        phase, k = int(ws['phase']), int(ws['k'])
+        if k != self._accum_k:
+            raise ValueError('FusedAdam.load_window_state: the window was taken with accumulate_steps=%d, this optimiser has %d' % (k, self._accum_k))
+        if not 0 <= phase < k or (phase != 0 and ws.get('grads') is None):
+            raise ValueError('FusedAdam.load_window_state: phase %d of %d%s' % (phase, k, ' without the window\'s gradients' if phase else ''))
+        if phase != 0:
+            g = self.model.flat_grads(attach=True)
+            if ws['grads'].numel() != g.numel():
+                raise ValueError('FusedAdam.load_window_state: %d gradient elements, the model has %d' % (ws['grads'].numel(), g.numel()))
+            self._join_side()
+            g.copy_(ws['grads'].reshape(-1))
+        self._accum_phase = phase
         self._hold_sync()
 
     def _hold_sync(self):
@@ -691,6 +722,14 @@ class FusedAdam(torch.optim.Optimizer):
     def skipped_total(self):
         """every step skipped so far, folded ones included, as a host int (one read of the device count: synchronises)"""
         return self._skipped_folded + self._read_skipped()
+
+    def continue_skipped_from(self, total):
+        """``skipped_total()`` goes on from ``total`` (a resumed run: ``load_state_dict`` has the per-parameter steps, in which the
+        skipped ones are already missing, and starts the count at 0).  Nothing the update reads changes; the average's count of
+        its own updates, which takes the skipped steps off, keeps its value."""
+        delta = int(total) - self.skipped_total()
+        self._skipped_folded += delta
+        self._ema_skip_base += delta
 
     def fold_if_due(self):
         """at the top of an eager step, and before a recording attaches its counters: fold when the frozen set is no longer the one

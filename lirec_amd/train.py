@@ -16,6 +16,7 @@ import contextlib
 import copy
 import os
 import math
+import random
 import time
 from datetime import datetime
 
@@ -26,7 +27,7 @@ from .config import opt
 from .features import CLIP_WEIGHT, PinnedPool
 from .loader import BlockLoader, ResidentLoader, make_loader
 from .test import testing
-from .util import Averaging, ModelSaver, ema_entry, save_checkpoint
+from .util import Averaging, ModelSaver, ema_entry, load_train_state, save_checkpoint
 
 
 _COPY_STREAMS = {}
@@ -300,12 +301,158 @@ def _check_distributed(train_dataset, model, loss, sampler, world):
     return train_dataset, sampler
 
 
+# ---------------------------------------------------------------------------
+# continuing a run (DESIGN "Continuing a run")
+# ---------------------------------------------------------------------------
+
+# opt fields that steer the loop, its logs, its files and the launch form -- every launch form gives the eager loop's bits -- but no
+# step's numbers: the two halves of a continued run may differ in them.  Every other plain field of opt is in the fingerprint.
+_LOOP_FIELDS = frozenset((
+    'epochs', 'store_root', 'resume', 'resume_train', 'resume_str', 'model_name', 'log_prefix', 'save_model', 'save_model_often',
+    'save_train_state', 'checkpoint_every', 'test', 'test_fr', 'num_workers', 'device', 'sanity_check', 'param_stats_every',
+    'tr_sum_max_flag', 'recorded_training', 'record_block_store', 'record_eval', 'device_collate', 'device_metrics', 'dp_shard_eval',
+    'strict'))
+
+
+def _hyper_fingerprint(optimizer):
+    """what of the optimiser must not differ between the halves of a continued run: ``RecordedTrainStep.hyper_key`` without the
+    learning rates (the scheduler moves them; the checkpoint's are loaded) and without the lags (state, which is loaded too) --
+    betas, eps, weight decay, the groups' membership, the frozen set, clip, guard, average and accumulation.  An optimiser that is
+    not a FusedAdam: its groups' settings but ``lr``."""
+    if not hasattr(optimizer, 'frozen_key'):
+        return repr([sorted((k, repr(v)) for k, v in g.items() if k not in ('params', 'lr', 'initial_lr'))
+                     for g in optimizer.param_groups])
+    from .graph import RecordedTrainStep
+    key, frozen = RecordedTrainStep.hyper_key(optimizer), optimizer.frozen_key()
+    if not getattr(optimizer, 'device_hyper', False):
+        key = key[1:]                     # (by value the key begins with the first group's lr)
+    else:
+        rows = [(tuple(float(b) for b in g['betas']), float(g['eps']), float(g['weight_decay']), bool(g.get('decoupled_weight_decay')))
+                for g in optimizer.param_groups]
+        key = key + (('groups', tuple(rows)),)      # (in device tables, not in the key: compared here)
+    key = tuple(k for k in key if not (frozen and k == frozen))
+    return repr(key + (('requires_grad', tuple(bool(p.requires_grad) for p in optimizer.model._plist)),))
+
+
+def fingerprint(train_dataset, model, optimizer) -> dict:
+    """{field: value} of everything that must be the same in both halves of a continued run"""
+    fp = {'batch_size': int(opt.batch_size), 'dropout': float(opt.dropout), 'dropout_seed': int(opt.dropout_seed),
+          'accumulate_steps': int(getattr(optimizer, 'accumulate_steps', 1))}
+    for k, v in sorted(opt.__dict__.items()):
+        if isinstance(v, (bool, int, float, str)) and k not in _LOOP_FIELDS and k not in fp:
+            fp['opt.' + k] = v
+    fp['optimizer'] = _hyper_fingerprint(optimizer)
+    fp['len(train_dataset)'] = len(train_dataset)
+    fp['parameter names'] = [n for n, _ in model.named_parameters()]
+    return fp
+
+
+class TrainState:
+    """What defines the NEXT step of a ``training()`` call beside the model's and the optimiser's ``state_dict()`` -- the one place
+    that knows: ``capture`` reads it, ``as_dict`` is ``ck['train_state']`` (plain Python, numpy and CPU tensors), ``from_dict``
+    checks the version, ``check`` the fingerprint, ``restore`` puts it back.  A feature that adds state to a step adds a field here.
+
+    Version 1: ``epoch`` (the epoch in progress), ``batches_done`` (loader batches of it already consumed; 0: the epoch starts),
+    ``steps_taken``, ``seen`` and ``loss_sum`` / ``loss_count`` (the cut epoch's clip count and loss average), ``dropout_calls``,
+    ``sample_calls`` (the host mirrors: current under a recorded step, no device read), ``skipped_total`` (the one device read),
+    ``window`` (FusedAdam.window_state), ``scheduler``, ``rng`` ({'torch', 'numpy', 'python'} at capture) and ``epoch_rng`` (torch's
+    just before the running epoch's ``iter(loader)``: its permutation is drawn from it), ``tr_sum_max_flag``, ``start``, ``saver``
+    (ModelSaver.state_dict) and ``fingerprint``."""
+    VERSION = 1
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+    @classmethod
+    def capture(cls, train_dataset, model, loss, optimizer, scheduler=None, saver=None, *, epoch, batches_done, steps_taken, seen,
+                losses, epoch_rng, start):
+        import numpy as np
+        return cls(version=cls.VERSION, epoch=int(epoch), batches_done=int(batches_done), steps_taken=int(steps_taken), seen=int(seen),
+                   loss_sum=losses.sum, loss_count=losses.count,
+                   dropout_calls=int(getattr(model, 'dropout_calls', 0)), sample_calls=int(getattr(loss, 'sample_calls', 0)),
+                   skipped_total=int(optimizer.skipped_total()) if hasattr(optimizer, 'skipped_total') else 0,
+                   window=optimizer.window_state() if hasattr(optimizer, 'window_state') else None,
+                   scheduler=copy.deepcopy(scheduler.state_dict()) if scheduler is not None else None,
+                   rng={'torch': torch.get_rng_state(), 'numpy': np.random.get_state(), 'python': random.getstate()},
+                   epoch_rng=epoch_rng, tr_sum_max_flag=bool(opt.tr_sum_max_flag), start=start,
+                   saver=saver.state_dict() if saver is not None else None,
+                   fingerprint=fingerprint(train_dataset, model, optimizer))
+
+    def as_dict(self) -> dict:
+        return dict(self.__dict__)
+
+    @classmethod
+    def from_dict(cls, d):
+        if not isinstance(d, dict) or d.get('version') != cls.VERSION:
+            raise ValueError('train state of version %r: this build reads version %d only' % (d.get('version') if isinstance(d, dict) else d, cls.VERSION))
+        return cls(**d)
+
+    def check(self, train_dataset, model, optimizer):
+        """ValueError naming the first field in which this run is not the checkpoint's"""
+        now = fingerprint(train_dataset, model, optimizer)
+        for k in list(self.fingerprint) + [k for k in now if k not in self.fingerprint]:
+            if k not in now or k not in self.fingerprint or now[k] != self.fingerprint[k]:
+                raise ValueError('training(resume=): %s differs -- the checkpoint was written with %r, this run has %r'
+                                 % (k, self.fingerprint.get(k, '<absent>'), now.get(k, '<absent>')))
+
+    def restore_rng(self):
+        import numpy as np
+        torch.set_rng_state(self.rng['torch'])
+        np.random.set_state(self.rng['numpy'])
+        random.setstate(self.rng['python'])
+
+    def restore(self, ck, model, loss, optimizer, scheduler=None, saver=None, losses=None, world=1):
+        """the checkpoint ``ck`` and this state into freshly built objects: model, optimiser (state_dict, then what is outside it:
+        the skipped count, the average, the open window), scheduler, the call counters, ``opt.tr_sum_max_flag``, the kept-metric
+        history, the cut epoch's loss average, the RNGs as they were at capture"""
+        model.load_state_dict(ck['state_dict'])
+        optimizer.load_state_dict(ck['optimizer'])
+        if hasattr(optimizer, 'continue_skipped_from'):
+            optimizer.continue_skipped_from(self.skipped_total)
+        if 'ema' in ck and hasattr(optimizer, 'load_ema_state_dict'):
+            optimizer.load_ema_state_dict(ck['ema']['state_dict'], updates=ck['ema'].get('updates'))
+        if self.window is not None and self.window['phase'] != 0:
+            if world > 1:
+                raise ValueError('training(resume=): the checkpoint was taken inside an accumulation window; under torch.distributed '
+                                 'the window\'s gradients are each rank\'s own and the file holds rank 0\'s only')
+            optimizer.load_window_state(self.window)
+        if (scheduler is None) != (self.scheduler is None):
+            raise ValueError('training(resume=): scheduler differs -- the checkpoint was written %s one, this run has %s'
+                             % (('without', 'one') if self.scheduler is None else ('with', 'none')))
+        if scheduler is not None:
+            scheduler.load_state_dict(copy.deepcopy(self.scheduler))
+        if hasattr(model, 'dropout_calls'):
+            model.dropout_calls = self.dropout_calls
+        if hasattr(loss, 'sample_calls'):
+            loss.sample_calls = self.sample_calls
+        opt.tr_sum_max_flag = self.tr_sum_max_flag
+        if saver is not None and self.saver is not None:
+            saver.load_state_dict(self.saver)
+        if losses is not None:
+            losses.sum, losses.count = self.loss_sum, self.loss_count
+            losses.avg = losses.sum / losses.count if losses.count else 0.0
+        self.restore_rng()
+
+
+def _iter_from(loader, start):
+    """the epoch's batches from the ``start``-th on, the batch sampler drawn from the torch RNG as it is NOW and no sample of a batch
+    passed over touched: the project's loaders have ``iter_from``; a stock ``DataLoader`` is drawn once over the bare indices --
+    which consumes the RNG exactly as its own ``iter()`` does -- and built anew over the explicit remaining batch list."""
+    if hasattr(loader, 'iter_from'):
+        return loader.iter_from(start)
+    DL = torch.utils.data.DataLoader
+    drawn = list(DL(range(len(loader.dataset)), batch_sampler=loader.batch_sampler, num_workers=0, collate_fn=list))
+    return iter(DL(loader.dataset, batch_sampler=drawn[start:], num_workers=loader.num_workers, collate_fn=loader.collate_fn,
+                   pin_memory=loader.pin_memory))
+
+
 def _evaluate_and_keep(epoch, start, train_dataset, val_dataset, test_dataset, model, loss, optimizer, saver, rank, world):
     """the periodic evaluation: the train set, then -- opt.test -- the validation set, whose metrics decide whether this epoch's
-    checkpoint is kept (and the test set evaluated).  COLLECTIVE under torch.distributed: every rank takes the same path."""
+    checkpoint is kept (and the test set evaluated); returns whether it was.  COLLECTIVE under torch.distributed: every rank takes
+    the same path."""
     testing(train_dataset, model, loss, total_iter=epoch, mode='train', train_start_time=start)
     if not (opt.test and val_dataset is not None):
-        return
+        return False
     # (opt.eval_ema: val / test see the averaged weights -- FusedAdam.ema_weights: swapped in by value, the live ones restored bit for bit)
     averaged = getattr(opt, 'eval_ema', False) and getattr(optimizer, 'ema_decay', None) is not None
     eval_weights = optimizer.ema_weights if averaged else contextlib.nullcontext
@@ -318,7 +465,7 @@ def _evaluate_and_keep(epoch, start, train_dataset, val_dataset, test_dataset, m
     if world > 1:                             # rank 0 keeps the history the decision is taken against: its verdict, everywhere
         keep = bool(parallel.all_reduce_counters({'keep': int(keep)})['keep'])
     if not keep:
-        return
+        return False
     if hasattr(optimizer, 'consolidate_state'):
         optimizer.consolidate_state()         # (a collective: every rank is here)
     if rank == 0:
@@ -330,6 +477,7 @@ def _evaluate_and_keep(epoch, start, train_dataset, val_dataset, test_dataset, m
     if test_dataset is not None:
         with eval_weights():
             testing(test_dataset, model, loss, total_iter=epoch, train_start_time=start, mode='test')
+    return True
 
 
 def _print_param_stats(optimizer, say):
@@ -345,11 +493,19 @@ def _print_param_stats(optimizer, say):
 
 
 def training(train_dataset, **kwargs):
+    """``resume=`` (a path, or a loaded checkpoint dict; ``opt.resume_train`` with ``opt.resume_str`` set is the same): continue the
+    run that wrote that checkpoint -- with ``opt.save_train_state`` or as the rolling file of ``opt.checkpoint_every`` -- on the
+    bits of the run that was never cut.  The caller builds model, loss, optimiser, datasets and scheduler exactly as for the first
+    run; everything is loaded here (``TrainState``).  A ``sampler=`` of the caller's own is the caller's to make resumable: the
+    loop restores the RNGs and calls ``set_epoch``, nothing else."""
     rank, world = parallel.world_info()
     print = _print if rank == 0 else (lambda *a, **k: None)        # (one log, rank 0's)
     start = datetime.now().strftime('%Y%m%d-%H%M%S')
     print('set parameters and model, train start time: %s' % start)
     model, loss, optimizer = kwargs['model'], kwargs['loss'], kwargs['optimizer']
+    resume = kwargs.get('resume')
+    if resume is None and getattr(opt, 'resume_train', False) and getattr(opt, 'resume_str', ''):
+        resume = opt.resume_str
     val_dataset = kwargs.get('val_dataset', kwargs.get('test_dataset'))
     test_dataset = kwargs.get('test_dataset') if 'val_dataset' in kwargs else None
     # scheduler= any object with .step() (torch.optim.lr_scheduler.*), called after every optimiser step -- eager or replayed --
@@ -380,15 +536,40 @@ def training(train_dataset, **kwargs):
               'collectives); ignored')
         stats_every = 0
 
-    def batches():
-        it = iter(loader)
+    keep_state = bool(getattr(opt, 'save_train_state', False))
+    every = int(getattr(opt, 'checkpoint_every', 0) or 0)
+    if every and world > 1:
+        print('checkpoint_every: the rolling checkpoint is single-process only (under data parallelism a cut inside an epoch is not '
+              'continued); ignored')
+        every = 0
+    rolling = os.path.join(opt.store_root, 'last.pth.tar')
+    first_epoch, resumed, steps_taken = 0, None, 0
+    if resume is not None:
+        ck, ts = load_train_state(resume)
+        resumed = TrainState.from_dict(ts)
+        resumed.check(train_dataset, model, optimizer)
+        resumed.restore(ck, model, loss, optimizer, scheduler, saver, losses, world=world)
+        first_epoch, steps_taken, start = resumed.epoch, resumed.steps_taken, resumed.start
+        print('resumed at epoch %d, batch %d (%d steps taken; train start time: %s)' % (resumed.epoch, resumed.batches_done, steps_taken, start))
+        if first_epoch >= opt.epochs:
+            print('nothing to do: the checkpoint\'s run had finished its %d epochs' % opt.epochs)
+            return model
+        if opt.tr_sum_max and first_epoch > 20:           # (the flip at epoch 20 has happened, mlp/train.py:49-51)
+            opt.tr_sum_max_flag = True
+
+    def capture(epoch, batches_done, seen, epoch_rng):
+        return TrainState.capture(train_dataset, model, loss, optimizer, scheduler, saver, epoch=epoch, batches_done=batches_done,
+                                  steps_taken=steps_taken, seen=seen, losses=losses, epoch_rng=epoch_rng, start=start).as_dict()
+
+    def batches(it):
         while True:
             stepper.before_draw()
             try:
                 yield next(it)
             except StopIteration:
                 return
-    for epoch in range(opt.epochs):
+    epoch_rng = torch.get_rng_state()
+    for epoch in range(first_epoch, opt.epochs):
         model.train()
         train_dataset.epoch = epoch
         if hasattr(sampler, 'set_epoch'):
@@ -399,7 +580,19 @@ def training(train_dataset, **kwargs):
         seen, end, t_epoch = 0, time.time(), time.time()
         pending = []
         stepper.begin_epoch()
-        for i, batch in enumerate(batches()):
+        # (a run cut inside this epoch: the epoch's permutation drawn again from the RNG state it was drawn from, the batches already
+        #  stepped on passed over untouched, then the RNG as it was at the cut)
+        skip = resumed.batches_done if (resumed is not None and epoch == first_epoch) else 0
+        if skip:
+            torch.set_rng_state(resumed.epoch_rng)
+            seen = resumed.seen
+        if keep_state or every:
+            epoch_rng = torch.get_rng_state()
+        it = _iter_from(loader, skip) if skip else iter(loader)
+        if skip:
+            torch.set_rng_state(resumed.rng['torch'])
+        since_write = 0
+        for i, batch in enumerate(batches(it), skip):
             data_time.update(time.time() - end)
             took = stepper.step(i, batch)
             if took is None:
@@ -416,6 +609,12 @@ def training(train_dataset, **kwargs):
             batch_time.update(time.time() - end)
             end = time.time()
             seen += n
+            steps_taken += 1
+            since_write += 1
+            if every and since_write >= every:
+                _flush_losses(pending, losses, finite_only=guarded())
+                save_checkpoint(rolling, epoch, model, optimizer, train_state=capture(epoch, i + 1, seen, epoch_rng), atomic=True)
+                since_write = 0
             if i % 10 == 0 and i:
                 _flush_losses(pending, losses, wait=False, finite_only=guarded())
                 print('Epoch: [{0}][{1}/{2}]\tTime {bt.val:.3f} ({bt.avg:.3f})\tData {dt.val:.3f} ({dt.avg:.3f})\t'
@@ -432,14 +631,21 @@ def training(train_dataset, **kwargs):
             _print_param_stats(optimizer, print)
         losses.reset()
         if epoch % opt.test_fr == 0:
-            _evaluate_and_keep(epoch, start, train_dataset, val_dataset, test_dataset, model, loss, optimizer, saver, rank, world)
+            kept = _evaluate_and_keep(epoch, start, train_dataset, val_dataset, test_dataset, model, loss, optimizer, saver, rank, world)
             print(getattr(opt, 'log_prefix', ''))
+            if kept and keep_state and rank == 0:
+                saver.save()              # (the kept checkpoints live in host memory until then: they survive an interruption)
         if opt.save_model and opt.save_model_often and epoch % 30 == 0 and rank == 0:
             saver.save()
+        if every:                         # (the epoch is over: "epoch + 1, no batch done" -- the next epoch starts)
+            save_checkpoint(rolling, epoch, model, optimizer, train_state=capture(epoch + 1, 0, 0, epoch_rng), atomic=True)
+    # (before close() drops a partial accumulation window: a run continued from the final checkpoint goes on inside it)
+    final_state = capture(epoch + 1, 0, 0, epoch_rng) if (keep_state and opt.save_model) else None
     stepper.close()
     opt.resume_str = os.path.join(opt.store_root, '%d.pth.tar' % epoch)
     if opt.save_model:
-        save_checkpoint(opt.resume_str, epoch, model, optimizer)
+        # (the flag off: the call is what it always was)
+        save_checkpoint(opt.resume_str, epoch, model, optimizer, *(() if final_state is None else (final_state,)))
     return model
 
 

@@ -83,7 +83,7 @@ class ModelSaver:
             if len(self.eval[key]) >= self.n:
                 w = self._worst(key)
                 self.eval[key].pop(w)
-                self.models[key].pop(w)
+                self.models[key].pop(w, None)        # (an entry restored by load_state_dict lives in its file only)
                 self.saved[key].pop(w, None)
             self.eval[key][epoch] = v
             self.models[key][epoch] = model
@@ -98,11 +98,28 @@ class ModelSaver:
                 if os.path.join(d, fn) not in keep:
                     os.remove(os.path.join(d, fn))
             for epoch, v in self.eval[key].items():
-                if epoch in self.saved[key]:
+                if epoch in self.saved[key] or epoch not in self.models[key]:
                     continue
                 fn = os.path.join(d, 'v%.4f_ep%d.pth.tar' % (v, epoch))
                 torch.save(self.models[key][epoch], fn)
                 self.saved[key][epoch] = fn
+
+    def state_dict(self):
+        """what the keep-this-checkpoint decisions are taken against -- ``eval``, ``saved`` (the files written so far) and ``n`` -- as
+        plain dicts whose order is the insertion order (``_worst`` resolves ties by it).  The kept checkpoint dicts themselves are
+        not in it: they are on disk once ``save()`` has run."""
+        return {'n': self.n, 'eval': {k: dict(v) for k, v in self.eval.items()}, 'saved': {k: dict(v) for k, v in self.saved.items()}}
+
+    def load_state_dict(self, sd):
+        """continue from ``state_dict()``: the same ``check()`` verdicts and evictions from here on.  A kept entry whose file was
+        never written stays in the history but cannot be written later (its checkpoint dict is gone; ``save()`` passes it over) --
+        ``training()`` with ``opt.save_train_state`` saves whenever the kept set changes, so that there is none."""
+        self.n = int(sd['n'])
+        self.eval, self.models, self.saved = defaultdict(dict), defaultdict(dict), defaultdict(dict)
+        for k, v in sd['eval'].items():
+            self.eval[k] = dict(v)
+        for k, v in sd['saved'].items():
+            self.saved[k] = dict(v)
 
 
 def ema_entry(optimizer):
@@ -113,9 +130,12 @@ def ema_entry(optimizer):
     return {'decay': float(optimizer.ema_decay), 'updates': int(optimizer.ema_updates()), 'state_dict': optimizer.ema_state_dict()}
 
 
-def save_checkpoint(path, epoch, model, optimizer):
+def save_checkpoint(path, epoch, model, optimizer, train_state=None, atomic=False):
     """COLLECTIVE under torch.distributed (every rank calls it): the sharded update's moments are gathered by all ranks, the file
-    is written by rank 0 alone, and nobody returns before it is on disk."""
+    is written by rank 0 alone, and nobody returns before it is on disk.  ``train_state`` (a dict: lirec_amd.train.TrainState):
+    kept as ``ck['train_state']`` -- what ``training(resume=)`` continues from; None: the keys are what they always were.
+    ``atomic``: written under a temporary name beside ``path`` and moved into place (``os.replace``): an interruption during the
+    write leaves the previous file as it was."""
     import torch.distributed as dist
     multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
     if hasattr(optimizer, 'consolidate_state'):
@@ -128,9 +148,32 @@ def save_checkpoint(path, epoch, model, optimizer):
         ema = ema_entry(optimizer)
         if ema is not None:
             ck['ema'] = ema                 # (beside the optimizer state, which stays what a stock Adam loads)
-        torch.save(ck, path)
+        if train_state is not None:
+            ck['train_state'] = train_state
+        if atomic:
+            tmp = '%s.tmp.%d' % (path, os.getpid())
+            try:
+                torch.save(ck, tmp)
+                os.replace(tmp, path)
+            finally:
+                if os.path.exists(tmp):
+                    os.remove(tmp)
+        else:
+            torch.save(ck, path)
     if multi:
         dist.barrier()
+
+
+def load_train_state(path_or_dict):
+    """``(checkpoint dict, ck['train_state'])`` of a path or an already loaded checkpoint; a checkpoint written without
+    ``opt.save_train_state`` -- the reference's three keys -- is refused in words: it does not say where the run was."""
+    ck = path_or_dict
+    if not isinstance(ck, dict):
+        ck = torch.load(os.fspath(ck), map_location='cpu', weights_only=False)
+    if 'train_state' not in ck:
+        raise ValueError('this checkpoint holds no train state (keys: %s): it was written without opt.save_train_state and can '
+                         'start a run, not continue one -- training(resume=) needs ck[\'train_state\']' % sorted(ck))
+    return ck, ck['train_state']
 
 
 def load_model(name=None, path=None, ema=False):
