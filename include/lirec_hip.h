@@ -1265,6 +1265,15 @@ int lirec_memset_zero(void* p, int64_t bytes, lirec_stream_t stream);
 /* One kernel: zero `bytes` bytes at `p` (16-byte aligned) and ctr[i] += inc[i] for i < n <= 4 (n = 0: no counters).  The
  * first launch of a replayed step: optimizer.zero_grad() and lirec_counter_add() without a second launch between them. */
 int lirec_zero_count(void* p, int64_t bytes, int64_t* ctr, const int64_t* inc, int32_t n, lirec_stream_t stream);
+/* Device snapshot (the cut of an asynchronous checkpoint: lirec_amd.util.AsyncCheckpointer).  ONE kernel launch copies n <= 8
+ * ranges, src[i] -> dst[i], bytes[i] bytes each, bit for bit, and in the same pass leaves in digests[i] the sum of range i's
+ * 32-bit words modulo 2^64 -- an integer sum: the same bits in whatever order the workgroups add.  The three arrays are HOST
+ * arrays, copied into the launch; digests: n 64-bit words in device memory, zeroed by the call itself (a memset on `stream` in
+ * front of the launch; both are recorded when a recording is open).  LIREC_EINVAL before any device call for: n outside 1..8, a
+ * null array or pointer, a src / dst pointer off a 16-byte boundary (digests: 8), bytes[i] negative or no multiple of 4, a dst
+ * range that shares a byte with any src range, another dst range or the digest words.  bytes[i] = 0 is an empty range: digest 0. */
+int lirec_snapshot(const void* const* src, void* const* dst, const int64_t* bytes, int32_t n, uint64_t* digests,
+                   lirec_stream_t stream);
 
 /* Diagnostics (current context): `ablate` = k-loop ablation mask (4: no k-loop; planes kernels 16: no LDS-DMA, 32: no LDS
  * reads / MFMAs; 8: planes path off) -- results are garbage, only the timing is meaningful; 64: run-time split-K rule for the

@@ -46,6 +46,11 @@ def defaults() -> dict:
         # written whenever the kept set changes.  checkpoint_every = N > 0: the rolling <store_root>/last.pth.tar, with the train
         # state, after every N taken steps and at every epoch's end (single process; moved into place by os.replace).
         save_train_state=False, checkpoint_every=0,
+        # checkpoint_async: the rolling file of checkpoint_every is cut by ONE launch (lirec_snapshot: the state's flat buffers into
+        # a device arena) and copied to pinned memory, checked and written behind the next steps by a writer thread
+        # (lirec_amd.util.AsyncCheckpointer).  The same file; one more stream; arena + pinned copy of the state's size.
+        # Does nothing with checkpoint_every = 0.  The final and the kept-best checkpoints stay synchronous.
+        checkpoint_async=False,
         # loop control of testing() / predict(), not in the reference (no step's numbers depend on it; tests/test_gpu_recorded_eval.py):
         # over a resident block store, single GPU, device-side counters, the forward-only iteration (draw, forward, loss, counters /
         # predictions) is recorded on the second full batch and replayed for every further one (lirec_amd.graph.RecordedEvalStep);

@@ -1313,6 +1313,64 @@ __global__ __launch_bounds__(256) void accum_begin_kernel(uint4* __restrict__ p,
   }
 }
 
+// lirec_snapshot: up to SNAPSHOT_MAX_RANGES ranges src[r] -> dst[r] copied bit for bit in ONE launch (the state a checkpoint is
+// made of: a handful of flat buffers), and in the same pass digest[r] += the sum of the range's 32-bit words, modulo 2^64 -- an
+// integer sum, so the order of the additions does not show in the bits.  The host has zeroed the digest words on the same
+// stream in front of the launch.  Every workgroup walks every range: zero_count_kernel's grid-stride loops over 16-byte words
+// (four loads in flight, then single ones), the up to three 32-bit words behind the last 16-byte word by workgroup 0, then the
+// wave's shuffles, the four waves through LDS and one device-scope atomic per workgroup and range it had a word of.
+#define SNAPSHOT_MAX_RANGES 8
+struct SnapshotRanges {
+  const uint4* src[SNAPSHOT_MAX_RANGES];
+  uint4* dst[SNAPSHOT_MAX_RANGES];
+  long n16[SNAPSHOT_MAX_RANGES];           // whole 16-byte words
+  int ntail[SNAPSHOT_MAX_RANGES];          // 32-bit words behind them, 0 .. 3
+  int count;
+};
+
+__device__ __forceinline__ unsigned long long sum_words(const uint4 a) {
+  return (unsigned long long)a.x + a.y + a.z + a.w;
+}
+
+__global__ __launch_bounds__(256) void snapshot_kernel(const SnapshotRanges t, unsigned long long* __restrict__ digests) {
+  __shared__ unsigned long long part[4];
+  const long stride = (long)gridDim.x * blockDim.x;
+  const long first = (long)blockIdx.x * blockDim.x;         // (uniform: the first 16-byte word of this workgroup)
+  for (int r = 0; r < t.count; ++r) {
+    const uint4* __restrict__ src = t.src[r];
+    uint4* __restrict__ dst = t.dst[r];
+    const long n16 = t.n16[r];
+    const int ntail = t.ntail[r];
+    const bool mine = first < n16 || (blockIdx.x == 0 && ntail > 0);      // (uniform)
+    if (!mine) continue;
+    unsigned long long s = 0;
+    long i = first + threadIdx.x;
+    for (; i + 3 * stride < n16; i += 4 * stride) {
+      const uint4 a = src[i], b = src[i + stride], c = src[i + 2 * stride], d = src[i + 3 * stride];
+      dst[i] = a; dst[i + stride] = b; dst[i + 2 * stride] = c; dst[i + 3 * stride] = d;
+      s += sum_words(a) + sum_words(b) + sum_words(c) + sum_words(d);
+    }
+    for (; i < n16; i += stride) {
+      const uint4 a = src[i];
+      dst[i] = a;
+      s += sum_words(a);
+    }
+    if (blockIdx.x == 0 && (int)threadIdx.x < ntail) {
+      const unsigned w = reinterpret_cast<const unsigned*>(src + n16)[threadIdx.x];
+      reinterpret_cast<unsigned*>(dst + n16)[threadIdx.x] = w;
+      s += w;
+    }
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const unsigned long long all = part[0] + part[1] + part[2] + part[3];
+      if (all) __hip_atomic_fetch_add(digests + r, all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();                                          // (part[] is written again for the next range)
+  }
+}
+
 // loader-typed reads: the pointer is declared fp32 / int32 in the ABI; with loader_types it is f64 / i64
 __device__ __forceinline__ float ld_f(const float* p, long i, bool f64) {
   return f64 ? (float)reinterpret_cast<const double*>(p)[i] : p[i];

@@ -3090,6 +3090,42 @@ int lirec_accum_begin(void* p, int64_t bytes, int64_t* ctr, const int64_t* every
   return LIREC_OK;
 }
 
+int lirec_snapshot(const void* const* src, void* const* dst, const int64_t* bytes, int32_t n, uint64_t* digests,
+                   lirec_stream_t stream) {
+  if (n < 1 || n > SNAPSHOT_MAX_RANGES || !src || !dst || !bytes || !digests) return LIREC_EINVAL;
+  const auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+  if (at(digests) & 7) return LIREC_EINVAL;
+  for (int i = 0; i < n; ++i)
+    if (!src[i] || !dst[i] || ((at(src[i]) | at(dst[i])) & 15) || bytes[i] < 0 || (bytes[i] & 3)) return LIREC_EINVAL;
+  // (a destination shares no byte with any source, with another destination or with the digest words; an empty range shares none)
+  const auto meet = [](uintptr_t a, uint64_t na, uintptr_t b, uint64_t nb) { return na > 0 && nb > 0 && a < b + nb && b < a + na; };
+  for (int i = 0; i < n; ++i) {
+    if (meet(at(dst[i]), (uint64_t)bytes[i], at(digests), 8u * (uint64_t)n)) return LIREC_EINVAL;
+    for (int j = 0; j < n; ++j)
+      if (meet(at(dst[i]), (uint64_t)bytes[i], at(src[j]), (uint64_t)bytes[j]) ||
+          (j != i && meet(at(dst[i]), (uint64_t)bytes[i], at(dst[j]), (uint64_t)bytes[j])))
+        return LIREC_EINVAL;
+  }
+  SnapshotRanges t;
+  memset(&t, 0, sizeof(t));
+  long most = 0;
+  for (int i = 0; i < n; ++i) {
+    t.src[i] = (const uint4*)src[i]; t.dst[i] = (uint4*)dst[i];
+    t.n16[i] = (long)(bytes[i] / 16);
+    t.ntail[i] = (int)((bytes[i] - t.n16[i] * 16) / 4);
+    if (t.n16[i] > most) most = t.n16[i];
+  }
+  t.count = (int)n;
+  long blocks = (most + 4 * 256 - 1) / (4 * 256);           // (lirec_zero_count's grid: four 16-byte words a thread, 2048 at the most)
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  const hipError_t e = lirec::memset_async(digests, 0, sizeof(uint64_t) * (size_t)n, (hipStream_t)stream);
+  if (e != hipSuccess) return (int)e;
+  lirec::launch(snapshot_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, t, (unsigned long long*)digests);
+  LIREC_CHECK_LAUNCH();
+  return LIREC_OK;
+}
+
 int lirec_cast_f64_f32(const double* src, float* dst, int64_t n, lirec_stream_t stream) {
   if (!src || !dst || n < 0) return LIREC_EINVAL;
   if (n == 0) return LIREC_OK;

@@ -1021,7 +1021,34 @@ class _HotPathModule(nn.Module):
 
     def state_dict(self, *a, **k):
         self.join_side_streams()
-        return super().state_dict(*a, **k)
+        if a or k:                      # (a destination, a prefix, keep_vars: torch's own walk)
+            return super().state_dict(*a, **k)
+        return self.state_dict_from(self._flat)
+
+    def state_dict_layout(self):
+        """what ``state_dict_from`` needs of the model, taken once: ([(key, shape, (offset, numel) in the flat buffer or None)] in
+        torch's key order, torch's metadata, {key: tensor} of the entries that are no view of the flat buffer)"""
+        sd = torch.nn.Module.state_dict(self)
+        return ([(key, tuple(v.shape), self._offsets.get(key)) for key, v in sd.items()], getattr(sd, '_metadata', None),
+                {key: v for key, v in sd.items() if key not in self._offsets})
+
+    def state_dict_from(self, flat, others=None, layout=None):
+        """``state_dict()`` over the flat buffer ``flat`` -- the model's own, or a host copy of it laid out the same: every
+        parameter a view of ``flat``, in torch's key order and with torch's metadata.  An entry that is no view of the flat
+        buffer (a buffer of a sub-module) comes from ``others[key]`` when given, else it is the model's own tensor.  With a
+        ``layout`` taken earlier (``state_dict_layout()``) the model itself is not looked at: the asynchronous checkpoint's
+        writer thread builds its dict that way."""
+        from collections import OrderedDict
+        entries, metadata, extras = self.state_dict_layout() if layout is None else layout
+        sd = OrderedDict()
+        for key, shape, place in entries:
+            if place is not None:
+                sd[key] = flat[place[0]:place[0] + place[1]].view(shape)
+            else:
+                sd[key] = others[key] if (others is not None and key in others) else extras[key]
+        if metadata is not None:
+            sd._metadata = metadata
+        return sd
 
     def named_parameters(self, *a, **k):
         """(``parameters()`` goes through here too.)  A replayed train step returns with the first bucket's update possibly still

@@ -1072,6 +1072,26 @@ def zero_count(t, ctr=None, incs=()):
           'lirec_zero_count')
 
 
+SNAPSHOT_MAX_RANGES = 8
+
+
+def snapshot(pairs, digests):
+    """lirec_snapshot: every ``(src, dst)`` of ``pairs`` (1 .. 8 pairs of contiguous device tensors of equal byte size, a multiple
+    of 4, on 16-byte boundaries; no ``dst`` sharing a byte with any ``src`` or other ``dst``) copied bit for bit by ONE launch on
+    the current stream, which leaves in ``digests[i]`` (int64 device tensor, at least ``len(pairs)`` words, zeroed by the call) the
+    sum of pair i's 32-bit words modulo 2^64 (as a signed word: ``digests.view(torch.uint64)`` / numpy ``.view('u8')`` to compare)."""
+    n = len(pairs)
+    assert digests.dtype == torch.int64 and digests.is_contiguous() and digests.numel() >= n
+    for s, d in pairs:
+        assert s.is_contiguous() and d.is_contiguous() and s.numel() * s.element_size() == d.numel() * d.element_size()
+    # (an empty view answers data_ptr() with 0: its place in its storage is what the call is given)
+    at = lambda t: t.data_ptr() or (t.untyped_storage().data_ptr() + t.storage_offset() * t.element_size())
+    src = (C.c_void_p * max(n, 1))(*[at(s) for s, _ in pairs])
+    dst = (C.c_void_p * max(n, 1))(*[at(d) for _, d in pairs])
+    nbytes = (C.c_int64 * max(n, 1))(*[s.numel() * s.element_size() for s, _ in pairs])
+    check(lib().lirec_snapshot(src, dst, nbytes, n, _p(digests), _stream()), 'lirec_snapshot')
+
+
 def cast_f64_f32(src, dst=None):
     assert src.dtype == torch.float64 and src.is_contiguous()
     if dst is None:

@@ -267,7 +267,13 @@ class FusedAdam(torch.optim.Optimizer):
         if self._accum_phase != 0:
             self._join_side()
             grads = self.model.flat_grads(attach=True).detach().cpu().clone()
-        return {'phase': int(self._accum_phase), 'k': int(self._accum_k), 'grads': grads}
+        return self.window_state_from(self._accum_phase, self._accum_k, grads)
+
+    @staticmethod
+    def window_state_from(phase, k, grads):
+        """``window_state()`` of a window at ``phase`` of ``k`` whose flat gradient buffer is the host tensor ``grads`` (kept as it
+        is given; dropped at phase 0, where no window is open)"""
+        return {'phase': int(phase), 'k': int(k), 'grads': grads if int(phase) != 0 else None}
 
     @torch.no_grad()
     def load_window_state(self, ws):
@@ -358,7 +364,15 @@ class FusedAdam(torch.optim.Optimizer):
         ``skipped_total()`` does)"""
         if self._ema_decay is None:
             return self._ema_done
-        return self._ema_done + self._ema_calls - max(0, self.skipped_total() - self._ema_skip_base)
+        return self.ema_updates_at(self.host_cut(groups=False), self._read_skipped())
+
+    @staticmethod
+    def ema_updates_at(cut, skipped):
+        """``ema_updates()`` from the host integers of ``host_cut()`` and the device count of skipped steps read elsewhere"""
+        e = cut['ema']
+        if e['decay'] is None:
+            return e['done']
+        return e['done'] + e['calls'] - max(0, cut['skipped_folded'] + (skipped if cut['guard_flags'] is not None else 0) - e['skip_base'])
 
     def _advance_ema(self):
         """one step has been issued (the eager step(), a replay: lirec_amd.graph)"""
@@ -386,7 +400,6 @@ class FusedAdam(torch.optim.Optimizer):
     def ema_state_dict(self):
         """name -> tensor, shaped like ``model.state_dict()``: the averaged parameters as views of the shadow (buffers, if the model
         has any, as the model holds them).  Loads into a fresh model with ``load_state_dict``."""
-        from collections import OrderedDict
         self._ensure_state()
         self._ensure_ema(self.model.flat_params(), force=True)
         sd = self.model.state_dict()             # (joins the side stream: its lerp may still be running behind a replayed step)
@@ -394,11 +407,18 @@ class FusedAdam(torch.optim.Optimizer):
             import warnings
             warnings.warn('FusedAdam.ema_state_dict(): sharded data-parallel update -- the shadow outside this rank\'s slices is stale; '
                           'call optimizer.consolidate_state() on EVERY rank first (a collective)', RuntimeWarning, stacklevel=2)
+        return self.ema_state_dict_from(self._ema, sd, self.model._offsets)
+
+    @staticmethod
+    def ema_state_dict_from(ema, sd, offsets):
+        """``ema_state_dict()`` over the flat shadow ``ema`` (the optimiser's, or a host copy of it), a ``model.state_dict()``
+        ``sd`` that names the entries and gives the shapes (and the values of what is no parameter) and the model's ``_offsets``"""
+        from collections import OrderedDict
         out = OrderedDict()
         for k, v in sd.items():
-            if k in self.model._offsets:
-                off, n = self.model._offsets[k]
-                out[k] = self._ema[off:off + n].view(v.shape)
+            if k in offsets:
+                off, n = offsets[k]
+                out[k] = ema[off:off + n].view(v.shape)
             else:
                 out[k] = v
         return out
@@ -1278,11 +1298,71 @@ class FusedAdam(torch.optim.Optimizer):
     def _sync_state_steps(self):
         """``state[p]['step']`` tensors are refreshed when somebody looks (state_dict), not 38 times a step."""
         S = self._read_skipped()          # (one read, behind the joined streams; every counter stays as it is)
-        flags = self._guard_flags if S else self._flags()
-        got = self.updates_received(self._step, [self._lag.get(n, 0) for n in self._names], flags, S)
+        got = self.steps_at(self._step_cut(), S)
         count = {id(p): k for p, k in zip(self.model._plist, got)}
         for p, st in self.state.items():
             st['step'] = torch.tensor(float(count.get(id(p), self._step)))
+        return got
+
+    # -- the state at a cut: host integers now, the buffers' values from wherever they were copied to ---------------------------
+    def packed_param_groups(self):
+        """``param_groups`` as ``state_dict()`` carries them: every key but ``'params'`` as it is, the parameters by their number"""
+        number, groups = {}, []
+        for grp in self.param_groups:
+            for p in grp['params']:
+                number.setdefault(id(p), len(number))
+            groups.append(dict({k: v for k, v in grp.items() if k != 'params'}, params=[number[id(p)] for p in grp['params']]))
+        return groups
+
+    def host_cut(self, groups=True):
+        """every HOST integer that, beside the values of the flat buffers and the device count of skipped steps, defines
+        ``state_dict()``, ``ema_updates()``, ``skipped_total()`` and ``window_state()`` at this moment -- no device call.  With
+        ``groups``: the packed ``param_groups``, deep-copied (a scheduler moves the learning rates on)."""
+        import copy
+        cut = self._step_cut()
+        cut['ema'] = {'decay': self._ema_decay, 'done': self._ema_done, 'calls': self._ema_calls, 'skip_base': self._ema_skip_base}
+        cut['window'] = {'phase': int(self._accum_phase), 'k': int(self._accum_k)}
+        if groups:
+            cut['param_groups'] = copy.deepcopy(self.packed_param_groups())
+        return cut
+
+    def _step_cut(self):
+        """the part of ``host_cut()`` the per-parameter steps and the skipped total are made of"""
+        return {'step': int(self._step), 'lags': [self._lag.get(n, 0) for n in self._names], 'flags': self._flags(),
+                'guard_flags': None if self._guard_flags is None or self._skipped_dev is None else tuple(self._guard_flags),
+                'skipped_folded': int(self._skipped_folded)}
+
+    @classmethod
+    def steps_at(cls, cut, skipped):
+        """the per-parameter ``step`` of ``state_dict()``, in ``model.named_parameters()`` order, from ``host_cut()`` and the
+        device count of skipped steps (counted only while a guarded step has run since the last fold)"""
+        S = skipped if cut['guard_flags'] is not None else 0
+        return cls.updates_received(cut['step'], cut['lags'], cut['guard_flags'] if S else cut['flags'], S)
+
+    @staticmethod
+    def skipped_total_at(cut, skipped):
+        return cut['skipped_folded'] + (skipped if cut['guard_flags'] is not None else 0)
+
+    def state_layout(self):
+        """what ``state_dict_from`` needs of the optimiser, taken once: [(parameter number, index in ``named_parameters()``
+        order, offset, numel, shape)] in the order of ``state``'s entries"""
+        number = {}
+        for grp in self.param_groups:
+            for p in grp['params']:
+                number.setdefault(id(p), len(number))
+        at = {id(p): (i,) + tuple(self.model._offsets[n]) for i, (n, p) in enumerate(zip(self._names, self.model._plist))}
+        return [(number[id(p)],) + at[id(p)] + (tuple(p.shape),) for p in self.state]
+
+    def state_dict_from(self, m, v, steps, param_groups, layout=None):
+        """``state_dict()`` over the flat moments ``m`` / ``v`` (this optimiser's, or host copies laid out the same), the
+        per-parameter ``steps`` (``steps_at``) and packed ``param_groups``: torch.optim.Optimizer's layout -- the state by
+        parameter number, in this optimiser's own order of entries; every tensor a view of the buffer it was given.  With a
+        ``layout`` taken earlier (``state_layout()``) the optimiser itself is not looked at."""
+        state = {}
+        for number, i, off, k, shape in (self.state_layout() if layout is None else layout):
+            state[number] = {'step': torch.tensor(float(steps[i])), 'exp_avg': m[off:off + k].view(shape),
+                             'exp_avg_sq': v[off:off + k].view(shape)}
+        return {'state': state, 'param_groups': param_groups}
 
     def consolidate_state(self):
         """COLLECTIVE (every rank must call it, at the same point): under the sharded data-parallel update a rank's moments are
@@ -1303,13 +1383,13 @@ class FusedAdam(torch.optim.Optimizer):
     def state_dict(self):
         self._ensure_state()
         self._join_side()       # (a replayed step may have left the first bucket's update running on the side stream)
-        self._sync_state_steps()
+        steps = self._sync_state_steps()
         sync = getattr(self.model, 'grad_sync', None)
         if sync is not None and sync.sharded and sync.real_world > 1 and getattr(self, '_consolidated_at', None) != self._step:
             import warnings
             warnings.warn('FusedAdam.state_dict(): sharded data-parallel update -- the moments outside this rank\'s slices are stale; '
                           'call optimizer.consolidate_state() on EVERY rank first (a collective)', RuntimeWarning, stacklevel=2)
-        return super().state_dict()
+        return self.state_dict_from(self._m, self._v, steps, self.packed_param_groups())
 
     def load_state_dict(self, state_dict):
         if any(g.get('amsgrad') for g in state_dict.get('param_groups', ())):

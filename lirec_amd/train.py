@@ -27,7 +27,7 @@ from .config import opt
 from .features import CLIP_WEIGHT, PinnedPool
 from .loader import BlockLoader, ResidentLoader, make_loader
 from .test import testing
-from .util import Averaging, ModelSaver, ema_entry, load_train_state, save_checkpoint
+from .util import AsyncCheckpointer, Averaging, ModelSaver, ema_entry, load_train_state, save_checkpoint
 
 
 _COPY_STREAMS = {}
@@ -309,7 +309,7 @@ def _check_distributed(train_dataset, model, loss, sampler, world):
 # step's numbers: the two halves of a continued run may differ in them.  Every other plain field of opt is in the fingerprint.
 _LOOP_FIELDS = frozenset((
     'epochs', 'store_root', 'resume', 'resume_train', 'resume_str', 'model_name', 'log_prefix', 'save_model', 'save_model_often',
-    'save_train_state', 'checkpoint_every', 'test', 'test_fr', 'num_workers', 'device', 'sanity_check', 'param_stats_every',
+    'save_train_state', 'checkpoint_every', 'checkpoint_async', 'test', 'test_fr', 'num_workers', 'device', 'sanity_check', 'param_stats_every',
     'tr_sum_max_flag', 'recorded_training', 'record_block_store', 'record_eval', 'device_collate', 'device_metrics', 'dp_shard_eval',
     'strict'))
 
@@ -365,13 +365,15 @@ class TrainState:
 
     @classmethod
     def capture(cls, train_dataset, model, loss, optimizer, scheduler=None, saver=None, *, epoch, batches_done, steps_taken, seen,
-                losses, epoch_rng, start):
+                losses, epoch_rng, start, device_reads=True):
+        """``device_reads=False`` (the asynchronous rolling checkpoint): the two fields that read the device -- ``skipped_total`` and
+        ``window`` -- are left None for ``AsyncCheckpointer``, which fills them in from its snapshot; everything else is taken here"""
         import numpy as np
         return cls(version=cls.VERSION, epoch=int(epoch), batches_done=int(batches_done), steps_taken=int(steps_taken), seen=int(seen),
                    loss_sum=losses.sum, loss_count=losses.count,
                    dropout_calls=int(getattr(model, 'dropout_calls', 0)), sample_calls=int(getattr(loss, 'sample_calls', 0)),
-                   skipped_total=int(optimizer.skipped_total()) if hasattr(optimizer, 'skipped_total') else 0,
-                   window=optimizer.window_state() if hasattr(optimizer, 'window_state') else None,
+                   skipped_total=(int(optimizer.skipped_total()) if hasattr(optimizer, 'skipped_total') else 0) if device_reads else None,
+                   window=(optimizer.window_state() if hasattr(optimizer, 'window_state') else None) if device_reads else None,
                    scheduler=copy.deepcopy(scheduler.state_dict()) if scheduler is not None else None,
                    rng={'torch': torch.get_rng_state(), 'numpy': np.random.get_state(), 'python': random.getstate()},
                    epoch_rng=epoch_rng, tr_sum_max_flag=bool(opt.tr_sum_max_flag), start=start,
@@ -557,9 +559,28 @@ def training(train_dataset, **kwargs):
         if opt.tr_sum_max and first_epoch > 20:           # (the flip at epoch 20 has happened, mlp/train.py:49-51)
             opt.tr_sum_max_flag = True
 
-    def capture(epoch, batches_done, seen, epoch_rng):
+    def capture(epoch, batches_done, seen, epoch_rng, device_reads=True):
         return TrainState.capture(train_dataset, model, loss, optimizer, scheduler, saver, epoch=epoch, batches_done=batches_done,
-                                  steps_taken=steps_taken, seen=seen, losses=losses, epoch_rng=epoch_rng, start=start).as_dict()
+                                  steps_taken=steps_taken, seen=seen, losses=losses, epoch_rng=epoch_rng, start=start,
+                                  device_reads=device_reads).as_dict()
+
+    # opt.checkpoint_async: the rolling file is cut by one launch and written behind the steps (lirec_amd.util.AsyncCheckpointer;
+    # DESIGN 4.j2).  Off -- or with no rolling file to write -- nothing is made: no thread, no arena, no launch.
+    writer = AsyncCheckpointer(model, optimizer) if (every and bool(getattr(opt, 'checkpoint_async', False))) else None
+
+    def write_rolling(epoch, batches_done, seen, epoch_rng):
+        if writer is not None:
+            writer.save(rolling, epoch, capture(epoch, batches_done, seen, epoch_rng, device_reads=False))
+        else:
+            save_checkpoint(rolling, epoch, model, optimizer, train_state=capture(epoch, batches_done, seen, epoch_rng), atomic=True)
+
+    def drained():
+        if writer is not None:
+            try:
+                writer.close()
+            finally:
+                stats.update(checkpoint_writes=writer.stats['writes'], checkpoint_waits=writer.stats['waits'],
+                             checkpoint_save_s=writer.stats['save_s'])
 
     def batches(it):
         while True:
@@ -569,76 +590,79 @@ def training(train_dataset, **kwargs):
             except StopIteration:
                 return
     epoch_rng = torch.get_rng_state()
-    for epoch in range(first_epoch, opt.epochs):
-        model.train()
-        train_dataset.epoch = epoch
-        if hasattr(sampler, 'set_epoch'):
-            sampler.set_epoch(epoch)
-        print('Epoch # %d' % epoch)
-        if opt.tr_sum_max and epoch == 20:            # mlp/train.py:49-51
-            opt.tr_sum_max_flag = True
-        seen, end, t_epoch = 0, time.time(), time.time()
-        pending = []
-        stepper.begin_epoch()
-        # (a run cut inside this epoch: the epoch's permutation drawn again from the RNG state it was drawn from, the batches already
-        #  stepped on passed over untouched, then the RNG as it was at the cut)
-        skip = resumed.batches_done if (resumed is not None and epoch == first_epoch) else 0
-        if skip:
-            torch.set_rng_state(resumed.epoch_rng)
-            seen = resumed.seen
-        if keep_state or every:
-            epoch_rng = torch.get_rng_state()
-        it = _iter_from(loader, skip) if skip else iter(loader)
-        if skip:
-            torch.set_rng_state(resumed.rng['torch'])
-        since_write = 0
-        for i, batch in enumerate(batches(it), skip):
-            data_time.update(time.time() - end)
-            took = stepper.step(i, batch)
-            if took is None:
-                continue
-            lval, n = took
-            # (gradient accumulation: a scheduler counts UPDATES -- after a step() the phase is 0 exactly when that call applied)
-            if getattr(optimizer, 'accum_phase', 0) == 0:
-                sched_step()
-            ev = None
-            if lval.is_cuda:
-                ev = torch.cuda.Event()
-                ev.record()
-            pending.append((lval, n, ev))
-            batch_time.update(time.time() - end)
-            end = time.time()
-            seen += n
-            steps_taken += 1
-            since_write += 1
-            if every and since_write >= every:
-                _flush_losses(pending, losses, finite_only=guarded())
-                save_checkpoint(rolling, epoch, model, optimizer, train_state=capture(epoch, i + 1, seen, epoch_rng), atomic=True)
-                since_write = 0
-            if i % 10 == 0 and i:
-                _flush_losses(pending, losses, wait=False, finite_only=guarded())
-                print('Epoch: [{0}][{1}/{2}]\tTime {bt.val:.3f} ({bt.avg:.3f})\tData {dt.val:.3f} ({dt.avg:.3f})\t'
-                      'Loss {ls.val:.4f} ({ls.avg:.4f})\t'.format(epoch, i, len(loader), bt=batch_time, dt=data_time, ls=losses))
-        _flush_losses(pending, losses, finite_only=guarded())
-        if scheduler is not None and scheduler_every == 'epoch':
-            scheduler.step()
-        print(seen)
-        print('loss: %f' % losses.avg)
-        print('train clips/s: %.1f' % (seen / max(time.time() - t_epoch, 1e-9)))
-        if guarded():
-            print('skipped steps: %d' % optimizer.skipped_total())        # (one read per epoch)
-        if stats_every and (epoch + 1) % stats_every == 0:
-            _print_param_stats(optimizer, print)
-        losses.reset()
-        if epoch % opt.test_fr == 0:
-            kept = _evaluate_and_keep(epoch, start, train_dataset, val_dataset, test_dataset, model, loss, optimizer, saver, rank, world)
-            print(getattr(opt, 'log_prefix', ''))
-            if kept and keep_state and rank == 0:
-                saver.save()              # (the kept checkpoints live in host memory until then: they survive an interruption)
-        if opt.save_model and opt.save_model_often and epoch % 30 == 0 and rank == 0:
-            saver.save()
-        if every:                         # (the epoch is over: "epoch + 1, no batch done" -- the next epoch starts)
-            save_checkpoint(rolling, epoch, model, optimizer, train_state=capture(epoch + 1, 0, 0, epoch_rng), atomic=True)
+    try:
+        for epoch in range(first_epoch, opt.epochs):
+            model.train()
+            train_dataset.epoch = epoch
+            if hasattr(sampler, 'set_epoch'):
+                sampler.set_epoch(epoch)
+            print('Epoch # %d' % epoch)
+            if opt.tr_sum_max and epoch == 20:            # mlp/train.py:49-51
+                opt.tr_sum_max_flag = True
+            seen, end, t_epoch = 0, time.time(), time.time()
+            pending = []
+            stepper.begin_epoch()
+            # (a run cut inside this epoch: the epoch's permutation drawn again from the RNG state it was drawn from, the batches already
+            #  stepped on passed over untouched, then the RNG as it was at the cut)
+            skip = resumed.batches_done if (resumed is not None and epoch == first_epoch) else 0
+            if skip:
+                torch.set_rng_state(resumed.epoch_rng)
+                seen = resumed.seen
+            if keep_state or every:
+                epoch_rng = torch.get_rng_state()
+            it = _iter_from(loader, skip) if skip else iter(loader)
+            if skip:
+                torch.set_rng_state(resumed.rng['torch'])
+            since_write = 0
+            for i, batch in enumerate(batches(it), skip):
+                data_time.update(time.time() - end)
+                took = stepper.step(i, batch)
+                if took is None:
+                    continue
+                lval, n = took
+                # (gradient accumulation: a scheduler counts UPDATES -- after a step() the phase is 0 exactly when that call applied)
+                if getattr(optimizer, 'accum_phase', 0) == 0:
+                    sched_step()
+                ev = None
+                if lval.is_cuda:
+                    ev = torch.cuda.Event()
+                    ev.record()
+                pending.append((lval, n, ev))
+                batch_time.update(time.time() - end)
+                end = time.time()
+                seen += n
+                steps_taken += 1
+                since_write += 1
+                if every and since_write >= every:
+                    _flush_losses(pending, losses, finite_only=guarded())
+                    write_rolling(epoch, i + 1, seen, epoch_rng)
+                    since_write = 0
+                if i % 10 == 0 and i:
+                    _flush_losses(pending, losses, wait=False, finite_only=guarded())
+                    print('Epoch: [{0}][{1}/{2}]\tTime {bt.val:.3f} ({bt.avg:.3f})\tData {dt.val:.3f} ({dt.avg:.3f})\t'
+                          'Loss {ls.val:.4f} ({ls.avg:.4f})\t'.format(epoch, i, len(loader), bt=batch_time, dt=data_time, ls=losses))
+            _flush_losses(pending, losses, finite_only=guarded())
+            if scheduler is not None and scheduler_every == 'epoch':
+                scheduler.step()
+            print(seen)
+            print('loss: %f' % losses.avg)
+            print('train clips/s: %.1f' % (seen / max(time.time() - t_epoch, 1e-9)))
+            if guarded():
+                print('skipped steps: %d' % optimizer.skipped_total())        # (one read per epoch)
+            if stats_every and (epoch + 1) % stats_every == 0:
+                _print_param_stats(optimizer, print)
+            losses.reset()
+            if epoch % opt.test_fr == 0:
+                kept = _evaluate_and_keep(epoch, start, train_dataset, val_dataset, test_dataset, model, loss, optimizer, saver, rank, world)
+                print(getattr(opt, 'log_prefix', ''))
+                if kept and keep_state and rank == 0:
+                    saver.save()              # (the kept checkpoints live in host memory until then: they survive an interruption)
+            if opt.save_model and opt.save_model_often and epoch % 30 == 0 and rank == 0:
+                saver.save()
+            if every:                         # (the epoch is over: "epoch + 1, no batch done" -- the next epoch starts)
+                write_rolling(epoch + 1, 0, 0, epoch_rng)
+    finally:
+        drained()            # (whatever ends the loop: no write in flight, no thread left; the writer's error is raised here)
     # (before close() drops a partial accumulation window: a run continued from the final checkpoint goes on inside it)
     final_state = capture(epoch + 1, 0, 0, epoch_rng) if (keep_state and opt.save_model) else None
     stepper.close()

@@ -127,7 +127,42 @@ def ema_entry(optimizer):
     (FusedAdam.ema_decay), else None.  The state_dict has the model's keys and shapes: it loads into a model as it is."""
     if getattr(optimizer, 'ema_decay', None) is None or not hasattr(optimizer, 'ema_state_dict'):
         return None
-    return {'decay': float(optimizer.ema_decay), 'updates': int(optimizer.ema_updates()), 'state_dict': optimizer.ema_state_dict()}
+    return ema_entry_from(optimizer.ema_decay, optimizer.ema_updates(), optimizer.ema_state_dict())
+
+
+def ema_entry_from(decay, updates, state_dict):
+    """``ema_entry`` from its three parts, wherever they were read"""
+    return {'decay': float(decay), 'updates': int(updates), 'state_dict': state_dict}
+
+
+def checkpoint_dict(epoch, state_dict, optimizer_state, group_names=None, ema=None, train_state=None):
+    """the checkpoint's dict from its parts, in the order of keys ``save_checkpoint`` has always written"""
+    ck = {'epoch': epoch, 'state_dict': state_dict, 'optimizer': optimizer_state}
+    if group_names is not None:
+        ck['param_group_names'] = group_names       # (who is in which group: checkpoint_to_flat needs it)
+    if ema is not None:
+        ck['ema'] = ema                 # (beside the optimizer state, which stays what a stock Adam loads)
+    if train_state is not None:
+        ck['train_state'] = train_state
+    return ck
+
+
+def _group_names(optimizer):
+    if len(getattr(optimizer, 'param_groups', ())) > 1 and hasattr(optimizer, 'group_names'):
+        return optimizer.group_names()
+    return None
+
+
+def write_atomic(ck, path):
+    """``torch.save`` under a temporary name beside ``path``, moved into place by ``os.replace``: an interruption -- or an error --
+    during the write leaves the previous file as it was"""
+    tmp = '%s.tmp.%d' % (path, os.getpid())
+    try:
+        torch.save(ck, tmp)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
 
 
 def save_checkpoint(path, epoch, model, optimizer, train_state=None, atomic=False):
@@ -142,26 +177,195 @@ def save_checkpoint(path, epoch, model, optimizer, train_state=None, atomic=Fals
         optimizer.consolidate_state()
     if not multi or dist.get_rank() == 0:
         dir_check(os.path.dirname(path))
-        ck = {'epoch': epoch, 'state_dict': model.state_dict(), 'optimizer': optimizer.state_dict()}
-        if len(getattr(optimizer, 'param_groups', ())) > 1 and hasattr(optimizer, 'group_names'):
-            ck['param_group_names'] = optimizer.group_names()       # (who is in which group: checkpoint_to_flat needs it)
-        ema = ema_entry(optimizer)
-        if ema is not None:
-            ck['ema'] = ema                 # (beside the optimizer state, which stays what a stock Adam loads)
-        if train_state is not None:
-            ck['train_state'] = train_state
+        ck = checkpoint_dict(epoch, model.state_dict(), optimizer.state_dict(), _group_names(optimizer), ema_entry(optimizer), train_state)
         if atomic:
-            tmp = '%s.tmp.%d' % (path, os.getpid())
-            try:
-                torch.save(ck, tmp)
-                os.replace(tmp, path)
-            finally:
-                if os.path.exists(tmp):
-                    os.remove(tmp)
+            write_atomic(ck, path)
         else:
             torch.save(ck, path)
     if multi:
         dist.barrier()
+
+
+class AsyncCheckpointer:
+    """The rolling checkpoint written BEHIND the steps (``opt.checkpoint_async``).  ``save(path, epoch, train_state)``
+    costs the loop one launch: it joins what ``state_dict()`` joins, copies the state's flat device buffers -- parameters, both
+    moments, the average when on, the open accumulation window's gradients, the count of skipped steps -- into a device arena
+    with ONE ``lirec_snapshot`` on the current stream, has a copy stream of its own bring the arena to pinned host memory behind
+    an event, and returns.  A writer thread waits for that copy, checks every range against the digest the snapshot left on the
+    device (a mismatch means arena or pinned memory was reused too early: RuntimeError), builds the dict ``save_checkpoint``
+    builds -- through the same builders (``Model.state_dict_from``, ``FusedAdam.state_dict_from`` / ``steps_at`` /
+    ``ema_updates_at`` / ``window_state_from``) over the host copies and the host integers taken at the cut -- and writes it
+    under a temporary name moved into place.  The file loads (``map_location='cpu'``) to the tree of the synchronous file; its
+    tensors were saved from host memory.  ``train_state``: the dict of ``TrainState.capture(..., device_reads=False)``; its two
+    device-side fields (``skipped_total``, ``window``) are filled in from the snapshot.
+
+    At most one write is in flight: a ``save()`` that finds the last one still running waits for it first (``stats['waits']``).
+    An exception in the writer is raised from the next ``save()``, ``wait()`` or ``close()``; the previous file stays.
+    ``close()`` drains, joins the thread and frees arena and pinned memory; idempotent.  The thread issues no launch and looks at
+    neither model nor optimiser -- keys, shapes, offsets and host integers are taken in ``save()`` --, and none is alive between
+    a ``wait()`` and the next ``save()``.  Single process only."""
+
+    ALIGN = 256
+
+    def __init__(self, model, optimizer):
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise RuntimeError('AsyncCheckpointer: single process only (under torch.distributed the rolling checkpoint is not written)')
+        if not (hasattr(model, 'state_dict_layout') and hasattr(optimizer, 'state_layout') and hasattr(optimizer, 'host_cut')):
+            raise TypeError('AsyncCheckpointer needs a lirec_amd model over a flat parameter buffer and a FusedAdam, not %s / %s'
+                            % (type(model).__name__, type(optimizer).__name__))
+        self.model, self.optimizer = model, optimizer
+        self.stats = {'writes': 0, 'waits': 0, 'save_s': 0.0, 'writer_s': 0.0}
+        self._arena = self._digests = self._host_digests = self._copy_stream = self._thread = self._error = None
+        self._host, self._closed = {}, False
+
+    # -- what a cut copies -------------------------------------------------------------------------------------------------
+    def _ranges(self, cut, extras):
+        """[(name, device tensor)] of this cut: at most the 8 ranges of one ``lirec_snapshot``"""
+        from . import ops
+        model, optimizer = self.model, self.optimizer
+        ranges = [('params', model.flat_params()), ('exp_avg', optimizer._m), ('exp_avg_sq', optimizer._v)]
+        if cut['ema']['decay'] is not None:
+            ranges.append(('ema', optimizer.ema))
+        if cut['window']['phase'] != 0:
+            ranges.append(('grads', model.flat_grads(attach=True)))
+        if cut['guard_flags'] is not None:
+            ranges.append(('skipped', optimizer._skipped_dev))
+        ranges += [('extra:' + key, t.detach()) for key, t in extras.items()]
+        if len(ranges) > ops.SNAPSHOT_MAX_RANGES:
+            raise ValueError('AsyncCheckpointer: %d ranges, one snapshot carries %d' % (len(ranges), ops.SNAPSHOT_MAX_RANGES))
+        for name, t in ranges:
+            nbytes = t.numel() * t.element_size()
+            if not (t.is_cuda and t.is_contiguous() and nbytes % 4 == 0 and t.data_ptr() % 16 == 0):
+                raise ValueError('AsyncCheckpointer: %s (%d bytes at %#x) is no range lirec_snapshot copies: a contiguous device '
+                                 'tensor of a multiple of 4 bytes on a 16-byte boundary' % (name, nbytes, t.data_ptr()))
+        return ranges
+
+    def _place(self, ranges, cut):
+        """the arena's views for ``ranges``, the pinned twins and the digest words.  The arena is allocated at the first cut, with
+        room for the window's gradient buffer whenever accumulate_steps > 1 (open at most cuts, closed at some), and again only
+        when a later cut needs more (the average switched on in the middle of a run)"""
+        up = lambda n: (n + self.ALIGN - 1) // self.ALIGN * self.ALIGN
+        sizes = [t.numel() * t.element_size() for _, t in ranges]
+        need = sum(up(n) for n in sizes)
+        if cut['window']['k'] > 1 and cut['window']['phase'] == 0:
+            need += up(sizes[0])
+        dev = ranges[0][1].device
+        if self._arena is None or self._arena.numel() < need or self._arena.device != dev:
+            self._arena = torch.empty(need, dtype=torch.uint8, device=dev)
+        if self._digests is None or self._digests.device != dev:
+            self._digests = torch.zeros(8, dtype=torch.int64, device=dev)
+            self._host_digests = torch.zeros(8, dtype=torch.int64, pin_memory=True)
+        if self._copy_stream is None or self._copy_stream.device != dev:
+            self._copy_stream = torch.cuda.Stream(device=dev)
+        views, at = [], 0
+        for (name, t), n in zip(ranges, sizes):
+            views.append(self._arena[at:at + n].view(t.dtype))
+            at += up(n)
+            h = self._host.get(name)
+            if h is None or h.numel() != t.numel() or h.dtype != t.dtype:
+                self._host[name] = torch.empty(t.numel(), dtype=t.dtype, pin_memory=True)
+        return views
+
+    # -- the loop's side ---------------------------------------------------------------------------------------------------
+    def save(self, path, epoch, train_state=None):
+        from . import ops
+        t0 = time.perf_counter()
+        if self._closed:
+            raise RuntimeError('AsyncCheckpointer.save(): closed')
+        if self._thread is not None and self._thread.is_alive():
+            self.stats['waits'] += 1
+        self.wait()
+        if ops.CommandList.mark() >= 0:
+            raise RuntimeError('AsyncCheckpointer.save(): not while a step is being recorded')
+        model, optimizer = self.model, self.optimizer
+        optimizer._ensure_state()
+        model.join_side_streams()       # (a replayed step may still be updating bucket 0 on lane 0: what state_dict() joins)
+        optimizer._join_side()
+        # (everything the writer needs of model and optimiser is taken HERE, on the loop's thread: host integers, keys, shapes,
+        #  offsets, metadata -- the thread looks at neither object again)
+        cut = optimizer.host_cut()
+        model_layout, state_layout = model.state_dict_layout(), optimizer.state_layout()
+        ranges = self._ranges(cut, model_layout[2])
+        views = self._place(ranges, cut)
+        ops.snapshot([(t.reshape(-1), v) for (_, t), v in zip(ranges, views)], self._digests)
+        taken = torch.cuda.Event()
+        taken.record()
+        self._copy_stream.wait_event(taken)
+        with torch.cuda.stream(self._copy_stream):
+            for (name, _), v in zip(ranges, views):
+                self._host[name].copy_(v, non_blocking=True)
+            self._host_digests.copy_(self._digests, non_blocking=True)
+            copied = torch.cuda.Event()
+            copied.record()
+        self._arena.record_stream(self._copy_stream)
+        self._digests.record_stream(self._copy_stream)
+        dir_check(os.path.dirname(path))
+        job = {'path': path, 'epoch': epoch, 'train_state': train_state, 'cut': cut, 'names': [name for name, _ in ranges],
+               'copied': copied, 'group_names': _group_names(optimizer), 'model_layout': model_layout, 'state_layout': state_layout,
+               'offsets': dict(model._offsets)}
+        import threading
+        self._thread = threading.Thread(target=self._run, args=(job,), name='lirec-checkpoint-writer', daemon=False)
+        self._thread.start()
+        self.stats['save_s'] += time.perf_counter() - t0
+
+    def wait(self):
+        """until no write is in flight; raises what the writer raised"""
+        if self._thread is not None:
+            self._thread.join()
+            self._thread = None
+        if self._error is not None:
+            e, self._error = self._error, None
+            raise e
+
+    def close(self):
+        if self._closed:
+            return
+        self._closed = True
+        try:
+            self.wait()
+        finally:
+            self._arena = self._digests = self._host_digests = self._copy_stream = None
+            self._host = {}
+
+    # -- the writer's side: no launch, no device read -----------------------------------------------------------------------
+    def _run(self, job):
+        t0 = time.perf_counter()
+        try:
+            job['copied'].synchronize()
+            write_atomic(self._build(job), job['path'])
+            self.stats['writes'] += 1
+        except BaseException as e:        # (never lost: raised from the next save(), wait() or close())
+            self._error = e
+        finally:
+            self.stats['writer_s'] += time.perf_counter() - t0
+
+    def _build(self, job):
+        import numpy as np
+        host = {name: self._host[name] for name in job['names']}
+        want = self._host_digests.numpy().view(np.uint64)
+        for i, name in enumerate(job['names']):
+            got = host[name].numpy().reshape(-1).view(np.uint32).sum(dtype=np.uint64)
+            if int(got) != int(want[i]):
+                raise RuntimeError('AsyncCheckpointer: the host copy of %s does not carry the digest the snapshot left on the device '
+                                   '(%#x, not %#x): arena or pinned memory was reused before the copy had finished'
+                                   % (name, int(got), int(want[i])))
+        A = type(self.optimizer)
+        cut, layout = job['cut'], job['model_layout']
+        skipped = int(host['skipped'][0]) if 'skipped' in host else 0
+        shapes = {key: shape for key, shape, _ in layout[0]}
+        extras = {name[len('extra:'):]: h.view(shapes[name[len('extra:'):]]) for name, h in host.items() if name.startswith('extra:')}
+        sd = self.model.state_dict_from(host['params'], extras, layout=layout)
+        osd = self.optimizer.state_dict_from(host['exp_avg'], host['exp_avg_sq'], A.steps_at(cut, skipped), cut['param_groups'],
+                                             layout=job['state_layout'])
+        ema = None
+        if 'ema' in host:
+            ema = ema_entry_from(cut['ema']['decay'], A.ema_updates_at(cut, skipped), A.ema_state_dict_from(host['ema'], sd, job['offsets']))
+        ts = job['train_state']
+        if ts is not None:
+            ts = dict(ts, skipped_total=A.skipped_total_at(cut, skipped),
+                      window=A.window_state_from(cut['window']['phase'], cut['window']['k'], host.get('grads')))
+        return checkpoint_dict(job['epoch'], sd, osd, job['group_names'], ema, ts)
 
 
 def load_train_state(path_or_dict):
